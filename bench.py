@@ -498,9 +498,30 @@ def published_curve(with_cpu):
             "points": points}, ok
 
 
-def run_workload(name, args, steps, warmup, rank, local_rank, world, dist, cpu_budget, latency_probes):
-    """Build the workload, time `steps` steps, derive the figures.  Returns (line dict or None on
-    ranks > 0, parity_ok)."""
+DUMP_BYTES = 64 * 10**6
+
+
+def dump_outputs(directory, rows, counts, limit):
+    """What the timed path handed its caller in the last timed step, as float64 .npy files under `directory` (at most
+    DUMP_BYTES in all): rows[i, k] = (reference, matches, weight) of needle i's k-th match, the slots past counts[i]
+    zeroed, and counts[i]; a batch too large for the budget is represented by a fixed, seeded sample of its needles
+    (needle_index: which).  The inputs are seeded, so two builds run with the same arguments can be compared file for
+    file."""
+    n_q = len(counts)
+    per_needle = 8 * (3 * limit + 2)                                # rows, count, index
+    k = min(n_q, (DUMP_BYTES - 3 * 1024) // per_needle)           # (three .npy headers)
+    idx = np.arange(n_q) if k == n_q else np.sort(np.random.default_rng(0).choice(n_q, size=k, replace=False))
+    live = np.arange(limit)[None, :] < counts[idx][:, None]
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "rows.npy"), np.where(live[:, :, None], rows[idx], 0).astype(np.float64))
+    np.save(os.path.join(directory, "counts.npy"), counts[idx].astype(np.float64))
+    np.save(os.path.join(directory, "needle_index.npy"), idx.astype(np.float64))
+    log(f"outputs of the last timed step: {k} of {n_q} needles in {directory}")
+
+
+def run_workload(name, args, steps, warmup, rank, local_rank, world, dist, cpu_budget, latency_probes, dump_dir=None):
+    """Build the workload, time `steps` steps, derive the figures; with `dump_dir`, write what the last timed step
+    computed there (dump_outputs).  Returns (line dict or None on ranks > 0, parity_ok)."""
     import workloads as W
     from blurrily_amd import _native
     from blurrily_amd.sharding import ResultBlock, gather_blocks
@@ -661,6 +682,8 @@ def run_workload(name, args, steps, warmup, rank, local_rank, world, dist, cpu_b
     # rows of the LAST TIMED launch, for the parity leg (every launch searches the same batch: both blocks hold them)
     gpu_rows = block.rows.cpu().numpy().view(np.uint32)
     gpu_counts = block.counts.cpu().numpy().view(np.uint32)
+    if dump_dir is not None and rank == 0:
+        dump_outputs(dump_dir, gpu_rows.reshape(n_q, limit, 3), gpu_counts, limit)
     nb = d_nb.cpu().numpy().astype(np.uint32).astype(np.int64)
     sum_nb, sum_rows = int(nb.sum()), int(gpu_counts.astype(np.int64).sum())
     algo_bytes = 8 * sum_nb + 8 * sum_T + 12 * sum_rows + 4 * n_q            # SURVEY.md 8(d), one launch
@@ -994,10 +1017,15 @@ def main():
                          "measurement would say (PMC passes of the sweep a bench run chose: tools/collect_profiles.sh)")
     ap.add_argument("--detail", default=DETAIL_PATH, metavar="PATH",
                     help="where the full record goes (the stdout line is the short one the driver parses)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed (its rows and counts, a seeded sample of at most "
+                         "64 MB) as DIR/<name>.npy, float64")
     ap.add_argument("--static-choice", action="store_true",
                     help="the sweep by the static rule, not by measuring both on the first batch (PMC passes: "
                          "every find call of the run then launches the same kernels)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -1031,7 +1059,7 @@ def main():
     main_name = args.workload or "geonames"
     budget = 0.0 if args.no_cpu_baseline else args.cpu_budget
     out, ok = run_workload(main_name, args, args.steps, args.warmup, rank, local_rank, world, dist, budget,
-                           args.latency_probes)
+                           args.latency_probes, dump_dir=args.dump_outputs)
     if world == 1 and args.workload is None and not args.no_extra and not args.in_process:
         extra = {}
         for name in EXTRA_CONFIGS:

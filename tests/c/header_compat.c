@@ -1,10 +1,10 @@
 /* header_compat.c -- the reference's ext/blurrily/storage.h and include/blurrily_storage.h in ONE translation
- * unit, compiled with -std=c99 -Wall -Wextra -Werror by tests/test_header_compat.py (only where /root/reference
- * exists: the header is never copied).  The nine functions of storage.h:36-117 are declared by both; C accepts
- * the second declaration only if it is compatible with the first -- same return type, same parameter types --
- * so a drift between the two headers is a compile error here.  The types are the reference's own (our header
- * sees __STORAGE_H__ and leaves them alone); their layout is pinned below. */
-#include "storage.h"             /* the reference's: -I/root/reference/ext/blurrily */
+ * unit, compiled with -std=c99 -Wall -Wextra -Werror by tests/test_header_compat.py.  "storage.h" is the stand-in
+ * made from what tests/golden/ref_abi.json recorded of the reference's header (the header is never copied): the
+ * nine functions of storage.h:36-117 with the reference's own prototypes, its typedefs and row layout held to
+ * ours.  C accepts the second declaration only if it is compatible with the first -- same return type, same
+ * parameter types -- so a drift between the two headers is a compile error here.  The layout is pinned below. */
+#include "storage.h"             /* the recorded reference header: -I<directory of the stand-in> */
 #include "blurrily_storage.h"    /* this repository's */
 
 #include <stddef.h>

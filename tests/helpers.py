@@ -264,3 +264,123 @@ def load_golden(name):
 
 def golden_find_files():
     return sorted(f for f in os.listdir(GOLDEN) if f.startswith("ref_find_") and f.endswith(".json"))
+
+
+# ---- the reference's answers, recorded (tests/golden/ref_recorded.json, ref_abi.json: tools/make_golden.py) ----
+# The inputs below are rebuilt from seeds by the generator and the tests alike; the fixtures hold only what the
+# reference's own C answered for them, so that no test needs the reference tree or oracle/_ref.
+
+RECORDED = "ref_recorded.json"
+ABI = "ref_abi.json"
+
+
+def rows_digest(rows):
+    """First 16 hex digits of the SHA-256 of find rows [[reference, matches, weight], ...] as little-endian u32."""
+    import hashlib
+    return hashlib.sha256(np.asarray(rows, dtype="<u4").reshape(-1, 3).tobytes()).hexdigest()[:16]
+
+
+def codes_digest(codes):
+    """The same for a tokeniser's codes, as little-endian u16."""
+    import hashlib
+    return hashlib.sha256(np.asarray(codes, dtype="<u2").tobytes()).hexdigest()[:16]
+
+
+def tokeniser_needles():
+    """2000 seeded needles over a small alphabet with spaces, '*', capitals and a UTF-8 lead byte."""
+    rng = np.random.default_rng(3)
+    alphabet = np.frombuffer(b"abcdefghijklmnopqrstuvwxyz   *Q\xc3", dtype=np.uint8)
+    return [bytes(rng.choice(alphabet, size=int(rng.integers(0, 60))).tolist()) for _ in range(2000)]
+
+
+# (kind, strings, limit) of the oracle's seeded comparisons and of the HIP path's larger ones
+ORACLE_CASES = [("words", 5000, 10), ("geonames", 30000, 10), ("skewed", 20000, 100)]
+HIP_CASES = [("geonames", 300000, 10), ("skewed", 200000, 100), ("words", 235886, 10)]
+
+
+def case_key(kind, n, limit):
+    return f"{kind}-{n}-{limit}"
+
+
+def oracle_case_inputs(kind, n):
+    """Haystack (seed 7) and needles (150 queries, seed 8, the empty needle and one letter) of ORACLE_CASES."""
+    import workloads as W
+    hay, off = {"words": W.words, "skewed": W.skewed}.get(kind, lambda n, s: W.geonames(n, 2000, s))(n, 7)
+    q, qo = W.queries(hay, off, 150, 8)
+    return hay, off, W.unpack(q, qo) + [b"", b"q"]
+
+
+def hip_case_inputs(kind, n):
+    """Haystack (seed 17) and needles (300 queries, seed 18) of HIP_CASES."""
+    import workloads as W
+    hay, off = {"words": W.words, "skewed": W.skewed}.get(kind, lambda n, s: W.geonames(n, 30000, s))(n, 17)
+    q, qo = W.queries(hay, off, 300, 18)
+    return hay, off, W.unpack(q, qo)
+
+
+HEAD_LIMITS = (1, 10, 64)
+
+
+def head_case_inputs(kind):
+    """Haystack and 400 needles (seed 19) of the limit-head check (tests/test_oracle_pinning.py); the reference's
+    rows are recorded for the first 60 needles at each of HEAD_LIMITS."""
+    import workloads as W
+    hay, off = W.geonames(30000, 4000, 17) if kind == "geonames" else W.skewed(30000, 18)
+    q, qo = W.queries(hay, off, 400, 19)
+    return hay, off, q, qo
+
+
+def tiny_haystack_cases(count=200, seed=5):
+    """Tiny adversarial haystacks: up to 40 distinct strings of up to 12 bytes over alphabets of 2, 3, 5 or 26
+    letters (the last with spaces), weights 0..5 -- near-duplicates, tiny weights, ties everywhere -- a needle of up
+    to 10 letters and a limit of 1..12.  Returns [(entries [(string, weight)], needle, limit)]."""
+    rng = np.random.default_rng(seed)
+    cases = []
+    for _ in range(count):
+        k = int(rng.choice([2, 3, 5, 27]))
+        entries, seen = [], set()
+        for _ in range(int(rng.integers(1, 41))):
+            raw = rng.integers(0, 256, size=int(rng.integers(0, 13))).tolist()
+            s = bytes(32 if x % k == 26 else 97 + x % k for x in raw)
+            w = int(rng.integers(0, 6))
+            if s not in seen:
+                seen.add(s)
+                entries.append((s, w))
+        needle = bytes(97 + x % min(k, 26) for x in rng.integers(0, 256, size=int(rng.integers(0, 11))).tolist())
+        cases.append((entries, needle, int(rng.integers(1, 13))))
+    return cases
+
+
+def resave_haystack():
+    """The map whose saved file the reference loads and saves again (tests/test_host_index.py): 20 000 seeded
+    geonames strings, every seventh reference deleted, one put after the deletions."""
+    import workloads as W
+    from blurrily_amd import RawMap
+    hay, off = W.geonames(20000, 2000, 3)
+    m = RawMap()
+    m.put_many_packed(hay, off, np.arange(1, 20001, dtype=np.uint32))
+    for r in range(1, 20001, 7):                   # deletions leave 0xFF-scribbled tail slots
+        m.delete(r)
+    m.put("after the deletions", 900001, 0)
+    return m
+
+
+def write_recorded_storage_h(directory):
+    """A stand-in for the gem's ext/blurrily/storage.h, made from what tests/golden/ref_abi.json recorded of it:
+    this repository's types, held to the recorded typedefs and row layout, and the nine functions declared with the
+    reference's own prototypes.  C accepts a second declaration only if it is compatible with the first, so a
+    translation unit that includes it compiles only while include/blurrily_storage.h agrees with the reference."""
+    abi = load_golden(ABI)
+    lines = ["#ifndef BLURRILY_RECORDED_STORAGE_H", "#define BLURRILY_RECORDED_STORAGE_H",
+             '#include "blurrily_storage.h"', "#include <stddef.h>",
+             "#define RECORDED_ASSERT(cond, name) typedef char recorded_##name[(cond) ? 1 : -1]"]
+    for i, (name, target) in enumerate(sorted(abi["typedefs"].items())):
+        lines.append(f"RECORDED_ASSERT(__builtin_types_compatible_p({name}, {target}), typedef_{i});")
+    for i, (expr, value) in enumerate(sorted(abi["layout"].items())):
+        lines.append(f"RECORDED_ASSERT(({expr}) == {value}, layout_{i});")
+    lines += abi["prototypes"]
+    lines.append("#endif")
+    path = os.path.join(str(directory), "storage.h")
+    with open(path, "w") as f:
+        f.write("\n".join(lines) + "\n")
+    return path

@@ -96,3 +96,28 @@ def test_multi_rank_line_names_the_collective(bench, canned):
     back = json.loads(bench.compact_line(full))
     assert back["collective"] == {"backend": "nccl", "world": 8, "rccl_version": "2.22.3", "distinct_devices": 8}
     assert len(back["per_rank_kernel_ms"]) == 8
+
+
+def test_dumped_outputs_are_the_rows_within_the_budget(bench, tmp_path, monkeypatch):
+    """--dump-outputs: float64 rows (slots past the count zeroed) and counts; a batch over the budget is a fixed,
+    seeded, sorted sample of its needles, the same every time."""
+    import numpy as np
+    rng = np.random.default_rng(1)
+    n, limit = 1000, 4
+    rows = rng.integers(1, 2**32, size=(n, limit, 3), dtype=np.uint64).astype(np.uint32)
+    counts = rng.integers(0, limit + 1, size=n).astype(np.uint32)
+    bench.dump_outputs(str(tmp_path / "all"), rows, counts, limit)
+    got = {k: np.load(tmp_path / "all" / f"{k}.npy") for k in ("rows", "counts", "needle_index")}
+    assert all(v.dtype == np.float64 for v in got.values())
+    assert np.array_equal(got["needle_index"], np.arange(n)) and np.array_equal(got["counts"], counts)
+    live = np.arange(limit)[None, :] < counts[:, None]
+    assert np.array_equal(got["rows"], np.where(live[:, :, None], rows, 0))       # u32 values exact in float64
+    monkeypatch.setattr(bench, "DUMP_BYTES", 100 * 8 * (3 * limit + 2) + 3 * 1024)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), rows, counts, limit)
+    idx = np.load(tmp_path / "a" / "needle_index.npy")
+    assert len(idx) == 100 and np.all(np.diff(idx) > 0)
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= bench.DUMP_BYTES
+    for k in ("rows", "counts", "needle_index"):
+        assert np.array_equal(np.load(tmp_path / "a" / f"{k}.npy"), np.load(tmp_path / "b" / f"{k}.npy"))
+    assert np.array_equal(np.load(tmp_path / "a" / "rows.npy"), got["rows"][idx.astype(np.int64)])

@@ -354,3 +354,29 @@ def test_bench_in_process_over_two_logical_devices():
     assert d["config"]["needles_per_gpu"] == 50000 and "in-process" in d["config"]["parallelism"]
     assert abs(d["value"] - 2 * 50000 * 2 / (d["ms_per_step"] * 2e-3)) / d["value"] < 1e-6
     assert d["cpu_baseline"]["parity_mismatches"] == 0 and d["parity_checked"] >= 64 and "extra_configs" not in d
+
+
+def test_bench_dump_outputs_are_what_the_timed_path_computed(tmp_path):
+    """`--dump-outputs DIR`: the rows and counts of the last timed step, checked against a direct find of the same
+    seeded batch on a map built the way bench.py builds it; `--steps` is the number of timed steps in the line."""
+    import numpy as np
+    import workloads as W
+    from blurrily_amd import RawMap
+    out = tmp_path / "out"
+    res, d = _run_bench(["--steps", "4", "--warmup", "1", "--scale", "0.02", "--no-extra", "--no-cpu-baseline",
+                         "--latency-probes", "0", "--dump-outputs", str(out)])
+    assert res.returncode == 0, res.stderr[-1500:]
+    assert d["_line"]["steps"] == 4 and d["_line"]["ms_per_step"] > 0
+    rows, counts, idx = (np.load(out / f"{k}.npy") for k in ("rows", "counts", "needle_index"))
+    assert rows.dtype == counts.dtype == idx.dtype == np.float64
+    hay, off = W.bench_haystack("geonames", 0.02)
+    q, qo = W.bench_needles(hay, off, "geonames", 0.02)
+    limit = W.BENCH_WORKLOADS["geonames"]["limit"]
+    assert len(idx) == len(qo) - 1 and rows.shape == (len(idx), limit, 3)      # (small: every needle)
+    m = RawMap()
+    m.put_many_packed(hay, off, np.arange(1, len(off), dtype=np.uint32))
+    want_rows, want_counts = m.find_batch_packed(q, qo, limit)
+    live = np.arange(limit)[None, :] < want_counts[:, None]
+    assert np.array_equal(counts, want_counts) and counts.sum() > 0
+    assert np.array_equal(rows, np.where(live[:, :, None], want_rows, 0))
+    m.close()

@@ -1,16 +1,14 @@
 """GPU parity against data produced by the reference's own C: the committed fixtures
-(tests/golden/ref_find_*.json) and, where oracle/_ref travelled with the snapshot, the live
-reference on larger haystacks; plus size-independent properties at BASELINE.json's full
+(tests/golden/ref_find_*.json) and the reference's recorded answers on larger haystacks
+(tests/golden/ref_recorded.json); plus size-independent properties at BASELINE.json's full
 Geonames scale, with a sample checked row for row against the oracle."""
-import os
-import tempfile
-
 import numpy as np
 import pytest
 
 import workloads as W
 from blurrily_amd import RawMap
-from helpers import Oracle, Reference, golden_find_files, golden_haystack, load_golden
+import helpers as H
+from helpers import Oracle, golden_find_files, golden_haystack, load_golden
 
 pytestmark = pytest.mark.gpu
 
@@ -41,22 +39,18 @@ def test_hip_matches_reference_fixture(name):
         assert m.get_option("one_taken") - taken >= sum(1 for w in g["expected"] if w)
 
 
-@pytest.mark.skipif(not Reference.available(), reason="oracle/_ref did not travel with the snapshot")
-@pytest.mark.parametrize("kind,n,limit", [("geonames", 300000, 10), ("skewed", 200000, 100), ("words", 235886, 10)])
+@pytest.mark.parametrize("kind,n,limit", H.HIP_CASES)
 def test_hip_vs_live_reference(kind, n, limit):
-    hay, off = {"words": W.words, "skewed": W.skewed}.get(kind, lambda n, s: W.geonames(n, 30000, s))(n, 17)
+    """Seeded haystacks of up to 300 000 strings: the reference's stats and rows for 300 needles each, recorded from
+    its load of this repository's file (tests/golden/ref_recorded.json)."""
+    want = load_golden(H.RECORDED)["hip_cases"][H.case_key(kind, n, limit)]
+    hay, off, needles = H.hip_case_inputs(kind, n)
     m = RawMap()
     m.put_many_packed(hay, off, np.arange(1, n + 1, dtype=np.uint32))
-    q, qo = W.queries(hay, off, 300, 18)
-    needles = W.unpack(q, qo)
+    assert m.stats() == want["stats"]
     got = _batch(m, needles, limit)
-    with tempfile.TemporaryDirectory() as d:
-        path = os.path.join(d, "h.trigrams")
-        m.save(path)
-        ref = Reference(path)
-        for nd, rows in zip(needles, got):
-            assert rows == ref.find(nd, limit), nd
-        ref.close()
+    for nd, rows, digest in zip(needles, got, want["rows"], strict=True):
+        assert H.rows_digest(rows) == digest, nd
 
 
 def test_full_geonames_scale_properties(geonames_full):

@@ -1,16 +1,18 @@
-"""include/blurrily_storage.h against the reference's own ext/blurrily/storage.h, in one translation unit
+"""include/blurrily_storage.h against the reference's ext/blurrily/storage.h, in one translation unit
 (tests/c/header_compat.c) under -Werror: incompatible declarations of the nine functions of storage.h:36-117
-do not compile.  Needs /root/reference (this container); skipped elsewhere -- the header is never copied."""
+do not compile.  The reference's side is what tests/golden/ref_abi.json recorded of its header (the nine prototypes
+as gcc printed them, the types its typedefs name, the layout of its rows): helpers.write_recorded_storage_h turns
+that into the storage.h the translation unit includes.  The header itself is never copied."""
 import os
 import subprocess
 
 import pytest
 
+from helpers import write_recorded_storage_h
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF_EXT = "/root/reference/ext/blurrily"
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(REF_EXT, "storage.h")), reason="no reference tree on this box")
 @pytest.mark.parametrize("order", ["reference_first", "ours_alone"])
 def test_the_two_headers_agree_in_one_translation_unit(tmp_path, order):
     src = os.path.join(ROOT, "tests", "c", "header_compat.c")
@@ -19,12 +21,27 @@ def test_the_two_headers_agree_in_one_translation_unit(tmp_path, order):
         text = open(src).read().replace('#include "storage.h"', "/* (reference header left out) */")
         src = str(tmp_path / "ours_alone.c")
         open(src, "w").write(text)
+    else:
+        write_recorded_storage_h(tmp_path)
     # flags of ext/blurrily/extconf.rb:4-13
     cmd = ["gcc", "-std=c99", "-Wall", "-Wextra", "-Werror", "-DPLATFORM_LINUX", "-D_XOPEN_SOURCE=700", "-D_GNU_SOURCE=1",
-           "-D_FILE_OFFSET_BITS=64", "-I", REF_EXT, "-I", os.path.join(ROOT, "include"), "-c", src,
+           "-D_FILE_OFFSET_BITS=64", "-I", str(tmp_path), "-I", os.path.join(ROOT, "include"), "-c", src,
            "-o", str(tmp_path / "compat.o")]
     r = subprocess.run(cmd, capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
+
+
+def test_a_drifted_prototype_does_not_compile(tmp_path):
+    """the check bites: one parameter type of a recorded prototype changed, and the translation unit fails"""
+    path = write_recorded_storage_h(tmp_path)
+    text = open(path).read()
+    drifted = text.replace("extern int blurrily_storage_delete (trigram_map, uint32_t);",
+                           "extern int blurrily_storage_delete (trigram_map, uint16_t);")
+    assert drifted != text
+    open(path, "w").write(drifted)
+    cmd = ["gcc", "-std=c99", "-Wall", "-Wextra", "-Werror", "-I", str(tmp_path), "-I", os.path.join(ROOT, "include"),
+           "-c", os.path.join(ROOT, "tests", "c", "header_compat.c"), "-o", str(tmp_path / "compat.o")]
+    assert subprocess.run(cmd, capture_output=True, text=True).returncode != 0
 
 
 def test_the_ruby_shim_is_committed_as_files():

@@ -1,6 +1,6 @@
 """Host side of the map through the C ABI (no GPU needed): put / delete / stats / save / load /
 close, written after spec/blurrily/map_spec.rb, plus byte-level checks of the file format
-against the reference's own loader/saver where oracle/_ref is present."""
+against what the reference's own loader/saver made of it (tests/golden/ref_recorded.json)."""
 import errno
 import hashlib
 import os
@@ -10,7 +10,7 @@ import pytest
 
 import workloads as W
 from blurrily_amd import ClosedError, Map, RawMap
-from helpers import Oracle, Reference
+from helpers import RECORDED, Oracle, load_golden, resave_haystack
 
 PAGE = 4096
 HEADER = 32 + 25 * 21952            # packed trigram_map_t (storage.c:62-74): 548 832 bytes
@@ -306,27 +306,17 @@ def test_put_many_equals_puts():
 
 # ---- byte compatibility with the reference's own load / save -------------------------------
 
-needs_ref = pytest.mark.skipif(not Reference.available(), reason="oracle/_ref not built (no reference tree)")
-
-
-@needs_ref
 def test_reference_loads_and_resaves_our_file_byte_identically(tmp_path):
-    hay, off = W.geonames(20000, 2000, 3)
-    m = RawMap()
-    m.put_many_packed(hay, off, np.arange(1, 20001, dtype=np.uint32))
-    for r in range(1, 20001, 7):                   # deletions leave 0xFF-scribbled tail slots
-        m.delete(r)
-    m.put("after the deletions", 900001, 0)
+    """The reference loaded this map's file and saved it again: its stats and the MD5 of what it wrote are recorded
+    (tests/golden/ref_recorded.json).  Our file must be that file, byte for byte, and we re-save it identically."""
+    want = load_golden(RECORDED)["resave"]
+    m = resave_haystack()
     ours = tmp_path / "ours.trigrams"
     m.save(ours)
-    ref = Reference(ours)
-    assert ref.stats() == m.stats()
-    theirs = tmp_path / "theirs.trigrams"
-    assert ref.save(theirs) == 0
-    ref.close()
-    assert md5(ours) == md5(theirs)
+    assert want["stats"] == m.stats()
+    assert md5(ours) == want["md5"]
     again = tmp_path / "again.trigrams"
-    RawMap.load(theirs).save(again)                # and we re-save the reference's file identically
+    RawMap.load(ours).save(again)                  # and we re-save the reference's file identically
     assert md5(again) == md5(ours)
 
 

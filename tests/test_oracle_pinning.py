@@ -3,19 +3,16 @@
 (a) every known-answer vector the reference's specs hold for the find path
     (tests/golden/spec_vectors.json);
 (b) fixtures emitted by the reference's own C (tests/golden/ref_*.json, tools/make_golden.py);
-(c) where oracle/_ref is present, the live reference on seeded random haystacks.
+(c) the reference's answers on seeded random haystacks and tiny adversarial ones (tests/golden/ref_recorded.json).
 CPU only.
 """
-import os
-import tempfile
-
 import numpy as np
 import pytest
-from hypothesis import given, settings, strategies as st
 
 import workloads as W
 from blurrily_amd import RawMap
-from helpers import Oracle, Reference, golden_find_files, golden_haystack, load_golden
+import helpers as H
+from helpers import Oracle, golden_find_files, golden_haystack, load_golden
 
 SPEC = load_golden("spec_vectors.json")
 
@@ -74,59 +71,42 @@ def test_oracle_matches_reference_find_fixture(name):
         assert o.find(bytes.fromhex(hexed), g["limit"]) == want
 
 
-needs_ref = pytest.mark.skipif(not Reference.available(), reason="oracle/_ref not built (no reference tree)")
+RECORDED = load_golden(H.RECORDED)
+TINY = H.tiny_haystack_cases()
 
 
-@needs_ref
 def test_oracle_tokeniser_vs_live_reference():
-    rng = np.random.default_rng(3)
-    alphabet = np.frombuffer(b"abcdefghijklmnopqrstuvwxyz   *Q\xc3", dtype=np.uint8)
-    for _ in range(2000):
-        nd = bytes(rng.choice(alphabet, size=int(rng.integers(0, 60))).tolist())
-        assert Oracle.tokenise(nd) == Reference.tokenise(nd), nd
+    """2000 seeded needles against the reference tokeniser's codes for them (tests/golden/ref_recorded.json)."""
+    for nd, want in zip(H.tokeniser_needles(), RECORDED["tokeniser"], strict=True):
+        assert H.codes_digest(Oracle.tokenise(nd)) == want, nd
 
 
-@needs_ref
-@pytest.mark.parametrize("kind,n,limit", [("words", 5000, 10), ("geonames", 30000, 10), ("skewed", 20000, 100)])
+@pytest.mark.parametrize("kind,n,limit", H.ORACLE_CASES)
 def test_oracle_vs_live_reference(kind, n, limit):
-    hay, off = {"words": W.words, "skewed": W.skewed}.get(kind, lambda n, s: W.geonames(n, 2000, s))(n, 7)
-    refs = np.arange(1, n + 1, dtype=np.uint32)
+    """Seeded haystacks: the reference's stats and rows for them, recorded from its load of this repository's file."""
+    want = RECORDED["oracle_cases"][H.case_key(kind, n, limit)]
+    hay, off, needles = H.oracle_case_inputs(kind, n)
     m = RawMap()
-    m.put_many_packed(hay, off, refs)
+    m.put_many_packed(hay, off, np.arange(1, n + 1, dtype=np.uint32))
     o = Oracle()
     o.put_many(hay, off)
-    with tempfile.TemporaryDirectory() as d:
-        path = os.path.join(d, "h.trigrams")
-        m.save(path)
-        ref = Reference(path)
-        assert ref.stats() == o.stats() == m.stats()
-        q, qo = W.queries(hay, off, 150, 8)
-        for nd in W.unpack(q, qo) + [b"", b"q"]:
-            assert o.find(nd, limit) == ref.find(nd, limit), nd
-        ref.close()
+    assert want["stats"] == o.stats() == m.stats()
+    for nd, rows in zip(needles, want["rows"], strict=True):
+        assert H.rows_digest(o.find(nd, limit)) == rows, nd
 
 
-@needs_ref
-@settings(max_examples=60, deadline=None)
-@given(st.lists(st.tuples(st.binary(min_size=0, max_size=12).map(lambda b: bytes(97 + (x % 27) if x % 27 < 26 else 32
-                                                                               for x in b)),
-                          st.integers(0, 5)), min_size=1, max_size=40, unique_by=lambda t: t[0]),
-       st.binary(min_size=0, max_size=10).map(lambda b: bytes(97 + (x % 26) for x in b)),
-       st.integers(1, 12))
-def test_oracle_vs_live_reference_hypothesis(entries, needle, limit):
-    """Tiny adversarial haystacks: duplicates of strings, tiny weights, ties everywhere."""
-    m = RawMap()
-    o = Oracle()
-    for i, (s, w) in enumerate(entries):
-        assert m.put(s, i + 1, w) == o.put(s, i + 1, w)
-    with tempfile.TemporaryDirectory() as d:
-        path = os.path.join(d, "h.trigrams")
-        m.save(path)
-        ref = Reference(path)
-        assert o.find(needle, limit) == ref.find(needle, limit)
-        for s, _ in entries[:5]:
-            assert o.find(s, limit) == ref.find(s, limit)
-        ref.close()
+def test_oracle_vs_live_reference_hypothesis():
+    """Tiny adversarial haystacks (helpers.tiny_haystack_cases, 200 of them): near-duplicate strings, tiny weights,
+    ties everywhere -- the reference's rows for the needle and for the first five strings."""
+    for case, ((entries, needle, limit), want) in enumerate(zip(TINY, RECORDED["tiny_cases"], strict=True)):
+        m = RawMap()
+        o = Oracle()
+        for i, (s, w) in enumerate(entries):
+            assert m.put(s, i + 1, w) == o.put(s, i + 1, w), (case, s)
+        assert want["stats"] == o.stats() == m.stats(), case
+        for nd, rows in zip([needle] + [s for s, _ in entries[:5]], want["rows"], strict=True):
+            assert H.rows_digest(o.find(nd, limit)) == rows, (case, nd)
+        m.close()
 
 
 def test_batch_driver_equals_single_calls():
@@ -156,11 +136,10 @@ def test_an_answer_at_a_limit_is_the_head_of_the_answer_at_a_larger_one(kind):
     """helpers.Oracle.batch_upto (the GPU tests that ask one batch at several limits run the oracle once, at the
     largest): storage.c:568-573 truncates ONE total order to the limit, so every limit's rows are the head of a larger
     limit's -- held here on every needle, incl. the skewed haystack's floods of (matches, weight) ties, and against
-    the live reference where it is built.  A mutation drops the kept answer."""
-    hay, off = W.geonames(30000, 4000, 17) if kind == "geonames" else W.skewed(30000, 18)
+    the reference's rows at three limits (tests/golden/ref_recorded.json).  A mutation drops the kept answer."""
+    hay, off, q, qo = H.head_case_inputs(kind)
     o = Oracle()
     o.put_many(hay, off)
-    q, qo = W.queries(hay, off, 400, 19)
     for limit in (149, 1, 3, 10, 64, 100):
         direct = o.batch(q, qo, limit=limit)
         cut = o.batch_upto(q, qo, limit, 149, spot=0)
@@ -172,17 +151,9 @@ def test_an_answer_at_a_limit_is_the_head_of_the_answer_at_a_larger_one(kind):
     after = o.batch_upto(q, qo, 10, 149)                        # (asked again: the first needle's best reference is gone)
     assert o._upto_key != kept
     assert np.array_equal(after["counts"], o.batch(q, qo, limit=10)["counts"])
-    if Reference.available():
-        with tempfile.TemporaryDirectory() as d:
-            path = os.path.join(d, "m.trigrams")
-            m = RawMap()
-            m.put_many_packed(hay, off, np.arange(1, len(off), dtype=np.uint32))
-            m.save(path)
-            ref = Reference(path)
-            o2 = Oracle()                                       # (unmutated)
-            o2.put_many(hay, off)
-            big = o2.batch(q, qo, limit=149)
-            for k, nd in enumerate(W.unpack(q, qo)[:60]):
-                for limit in (1, 10, 64):
-                    assert ref.find(nd, limit) == big["rows"][k, :min(int(big["counts"][k]), limit)].tolist()
-            ref.close()
+    o2 = Oracle()                                               # (unmutated)
+    o2.put_many(hay, off)
+    big = o2.batch(q, qo, limit=149)
+    for limit, recorded in zip(H.HEAD_LIMITS, RECORDED["head_cases"][kind], strict=True):
+        for k, want in enumerate(recorded):
+            assert H.rows_digest(big["rows"][k, :min(int(big["counts"][k]), limit)]) == want, (k, limit)
