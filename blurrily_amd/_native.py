@@ -113,6 +113,13 @@ def lib():
         "blurrily_storage_device_info_sized": (C.c_size_t, [vp, C.c_void_p, C.c_size_t]),
         "blurrily_storage_tune": (C.c_int, [vp, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_uint16]),
         "blurrily_storage_last_kernels": (C.c_size_t, [vp, C.c_char_p, C.c_size_t]),
+        "blurrily_storage_get": (C.c_int, [vp, C.c_uint32, C.c_void_p, C.c_int, C.c_void_p]),
+        "blurrily_storage_get_batch": (C.c_int, [vp, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                 C.c_size_t]),
+        "blurrily_storage_find_references": (C.c_int, [vp, C.c_void_p, C.c_size_t, C.c_uint16, C.c_void_p, C.c_void_p,
+                                                       C.c_void_p]),
+        "blurrily_storage_find_references_device": (C.c_int, [vp, C.c_void_p, C.c_size_t, C.c_uint16, C.c_void_p,
+                                                              C.c_void_p, C.c_void_p, C.c_void_p]),
     }
     for name, (res, args) in sig.items():
         try:
@@ -137,4 +144,8 @@ EXPORTED_SYMBOLS = (
     "blurrily_storage_set_stats", "blurrily_storage_find_stats",
     "blurrily_storage_set_option", "blurrily_storage_get_option", "blurrily_storage_find_path_flags",
     "blurrily_storage_device_info_sized", "blurrily_storage_tune", "blurrily_storage_last_kernels",
+) + (
+    # by reference (reference storage.h:72-87's commented-out get, and find by a stored reference)
+    "blurrily_storage_get", "blurrily_storage_get_batch", "blurrily_storage_find_references",
+    "blurrily_storage_find_references_device",
 )

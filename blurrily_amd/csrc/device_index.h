@@ -87,6 +87,7 @@ struct DeviceIndex {
   uint32_t* d_tomb           = nullptr;   // [(n_refs+31)/32] bit r: rank r was deleted after the build
   uint32_t  n_bitmaps        = 0;         // dense slices (each starts with its bitmap, inline in d_ent)
   uint32_t  dense_min8       = 0;         // a slice spanning at least this many entries is dense (a multiple of 8)
+  uint32_t  max_tri          = 0;         // most postings (distinct trigrams) any one reference of the image has
   // postings a needle's trigram finds in one window, on average, when needle trigrams are distributed
   // like the haystack's postings: (sum of used[t]^2 / sum of used[t]) / n_windows.  The window-major
   // sweep pays a fixed price per (needle, window) and saves in proportion to the postings it leaves
@@ -102,6 +103,10 @@ struct DeviceIndex {
   // host copies for mapping a reference to its rank (deletes after the build)
   std::vector<uint32_t> h_sorted_ref;     // references ascending
   std::vector<uint32_t> h_rank_of_pos;    // rank of h_sorted_ref[i]
+  // ... and their device copies, uploaded by the first by-reference call on the image (device_index_ensure_ref_table;
+  // counted in device_bytes from then on): an image that never serves one holds exactly what it held before
+  uint32_t* d_sorted_ref     = nullptr;   // [n_refs]
+  uint32_t* d_rank_of_pos    = nullptr;   // [n_refs]
 };
 
 // How an image is built and which of them the window-major sweep may be taken on (blurrily_storage_set_option;
@@ -129,6 +134,8 @@ void device_index_free(DeviceIndex* ix);
 // A copy of `src` on HIP device `dst_device` (which may be src's own): device to device, nothing is rebuilt on the
 // host.  The copy holds no host-side reference table (deletes are mapped to ranks on the original).  0, or -1 + errno.
 int  device_index_clone(const DeviceIndex& src, int dst_device, DeviceIndex* out);
+// Upload h_sorted_ref / h_rank_of_pos (once per image).  0, or -1 + errno (EINVAL: a clone, which has no host tables).
+int  device_index_ensure_ref_table(DeviceIndex* ix);
 // Rank of `ref` in the device image, or -1 if the image does not hold it.
 int64_t device_index_rank_of(const DeviceIndex& ix, uint32_t ref);
 

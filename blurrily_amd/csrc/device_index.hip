@@ -85,6 +85,8 @@ void device_index_free(DeviceIndex* ix) {
   if (ix->d_win_max_tri)    (void)hipFree(ix->d_win_max_tri);
   if (ix->d_start_win)      (void)hipFree(ix->d_start_win);
   if (ix->d_tomb)           (void)hipFree(ix->d_tomb);
+  if (ix->d_sorted_ref)     (void)hipFree(ix->d_sorted_ref);
+  if (ix->d_rank_of_pos)    (void)hipFree(ix->d_rank_of_pos);
   *ix = DeviceIndex();
 }
 
@@ -441,6 +443,7 @@ int device_index_build(const HostIndex& host, DeviceIndex* out, const IndexBuild
   ix.built_from = host.generation();
   ix.n_bitmaps = n_bitmaps;
   ix.dense_min8 = dense_min8;
+  ix.max_tri = n_win ? *std::max_element(win_max_tri.begin(), win_max_tri.end()) : 0u;
   std::copy(start_win.begin(), start_win.end(), ix.h_start_win);
   ix.mean_hit_slice = mean_hit_slice;
   ix.dense_share = dense_share;
@@ -478,7 +481,7 @@ int device_index_clone(const DeviceIndex& src, int dst_device, DeviceIndex* out)
   DeviceIndex ix;
   ix.device = dst_device; ix.n_refs = src.n_refs; ix.n_windows = src.n_windows; ix.nib_windows = src.nib_windows;
   ix.n_entries = src.n_entries; ix.n_slots = src.n_slots; ix.built_from = src.built_from;
-  ix.n_bitmaps = src.n_bitmaps; ix.dense_min8 = src.dense_min8;
+  ix.n_bitmaps = src.n_bitmaps; ix.dense_min8 = src.dense_min8; ix.max_tri = src.max_tri;
   ix.mean_hit_slice = src.mean_hit_slice; ix.dense_share = src.dense_share; ix.ws_gain = src.ws_gain;
   bool failed = hipSetDevice(dst_device) != hipSuccess;
   auto copy = [&](auto** dptr, const auto* from, size_t elems) {
@@ -507,6 +510,25 @@ int device_index_clone(const DeviceIndex& src, int dst_device, DeviceIndex* out)
   (void)hipSetDevice(prev);
   device_index_free(out);
   *out = std::move(ix);
+  return 0;
+}
+
+int device_index_ensure_ref_table(DeviceIndex* ix) {
+  if (ix->d_sorted_ref) return 0;
+  if (ix->h_sorted_ref.size() != ix->n_refs) { errno = EINVAL; return -1; }
+  const size_t bytes = std::max<size_t>(ix->n_refs, 1) * sizeof(uint32_t);
+  uint32_t *s = nullptr, *r = nullptr;
+  if (hipMalloc(reinterpret_cast<void**>(&s), bytes) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&r), bytes) != hipSuccess ||
+      (ix->n_refs && (hipMemcpy(s, ix->h_sorted_ref.data(), ix->n_refs * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess ||
+                      hipMemcpy(r, ix->h_rank_of_pos.data(), ix->n_refs * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess))) {
+    std::fprintf(stderr, "blurrily_hip: uploading the reference table failed\n");
+    if (s) (void)hipFree(s);
+    if (r) (void)hipFree(r);
+    errno = ENOMEM;
+    return -1;
+  }
+  ix->d_sorted_ref = s; ix->d_rank_of_pos = r;
+  ix->device_bytes += 2 * bytes;
   return 0;
 }
 

@@ -181,6 +181,54 @@ int launch_find_small(const FindArgs& a, uint32_t n_cus, hipStream_t stream);
 int launch_wsweep(const FindArgs& a, uint32_t w, uint32_t n, uint32_t n_cus, bool own_pass, hipStream_t stream);
 int launch_finalize_rows(const FindArgs& a, uint32_t n, hipStream_t stream);
 }
+// By reference (kernels/refs.inc): one image as the lookup and the extraction see it.
+struct RefImage {
+  const uint32_t* sorted_ref;      // [n_refs] references ascending (DeviceIndex::d_sorted_ref)
+  const uint32_t* rank_of_pos;     // [n_refs] rank of sorted_ref[i]
+  uint32_t        n_refs;
+  const uint32_t* tomb;            // deleted base ranks (nullptr: none)
+  const uint2*    slice_se;
+  const uint16_t* ent;
+  const uint32_t* weight_of_rank;
+  uint32_t        dense_min8;
+  uint32_t        win0;            // its first window in the numbering of both images' windows
+};
+struct RefArgs {
+  RefImage        img[2];          // the base image, then the delta image of pending puts
+  uint32_t        n_img;
+  uint32_t        n_win_all;       // windows of both images
+  const uint32_t* refs;            // [n] references asked for (device)
+  uint32_t        n;
+  uint2*          loc;             // [n] {window, in-window rank}, window ~0u: not in the map
+  uint32_t*       req;             // [n_win_all][kWindowSize / 32] requested in-window ranks
+  uint32_t*       win_cnt;         // [n_win_all] distinct ranks requested per window
+  uint64_t*       win_base;        // [n_win_all + 1] their exclusive scan: a window's first slot; [n_win_all]: slots in all
+  uint32_t*       wprefix;         // [n_win_all][kWindowSize / 32] slots in front of every request word of a window
+  uint32_t*       slot_cnt;        // [n] trigrams of every slot
+  uint32_t*       slot_fill;       // [n] write cursors
+  uint64_t*       slot_start;      // [n + 1] exclusive scan of slot_cnt
+  uint16_t*       codes;           // [n + trigrams of all slots]: a pad of n, then every slot's codes, ascending
+  uint32_t*       ntri;            // [n] out: distinct trigrams of reference i (0: not in the map)
+  uint32_t*       weight;          // [n] out: its weight
+  uint64_t*       qoff;            // [n] out: its codes at codes + qoff[i] + i
+};
+// Extract the trigrams of a.refs (several launches on `stream`; every slice of a touched window is read once).
+int launch_refs_extract(const RefArgs& a, hipStream_t stream);
+// The find path's needles when they are references: what launch_refs_extract left
+struct RefNeedles {
+  const uint16_t* codes;
+  const uint64_t* qoff;
+  const uint32_t* ntri;
+  const uint32_t* weight;
+  uint32_t        n;
+  uint64_t        code_slots;      // elements of `codes`
+};
+// ... and in place of tokenise_kernel: q_ntri, q_nb (from this image's bucket sizes), q_start (start_win[weight]), the
+// mid (65..127 distinct trigrams) and big (more than 127) lists.
+int launch_ref_needles(const RefNeedles& r, const uint32_t* code_total, const uint32_t* start_win, uint32_t* q_ntri,
+                       uint32_t* q_nb, uint32_t* q_start, uint32_t* big_list, uint32_t* big_count, uint32_t* mid_list,
+                       uint32_t* mid_count, hipStream_t stream);
+
 // Merge, per needle, two result lists that are each in result order (base image and delta image
 // hold disjoint references) into the first `limit` rows of `out`.
 int launch_merge_rows(const trigram_match_t* a_rows, const uint32_t* a_counts, const trigram_match_t* b_rows,

@@ -176,6 +176,11 @@ size_t find_lds_bytes(size_t counter_bytes, uint32_t pool_cap) {
     }                                                                                 \
   } while (0)
 
+// by reference (blurrily_storage_get / _find_references): no counted build of these
+#ifndef BLURRILY_COUNTED
+#include "kernels/refs.inc"
+#endif
+
 int launch_tokenise(const TokeniseArgs& t, hipStream_t stream) {
   if (t.n == 0) return 0;
   if (t.n <= 16384 && t.max_len && t.max_len <= 63) {          // short needles, not a huge batch: a wave per needle

@@ -192,6 +192,89 @@ class RawMap:
             _raise_errno()
         return rows[:, :limit, :], counts, flags
 
+    # -- by reference (reference storage.h:72-87's commented-out get; find what is like a stored entry) ---------
+    def _refs(self, references):
+        refs = np.asarray(references)
+        if refs.ndim != 1:
+            raise ValueError("references must be one-dimensional")
+        if refs.dtype != np.uint32:
+            refs = np.array([_u32(r, "reference") for r in refs.tolist()], dtype=np.uint32)
+        return np.ascontiguousarray(refs)
+
+    def get(self, reference):
+        """``(weight, codes)`` of a stored reference -- its trigram codes ascending, what the tokeniser gives for the
+        string it was put with -- or None when the map does not hold it (blurrily_storage_get)."""
+        self._check_open()
+        codes = np.zeros(28 * 28 * 28, dtype=np.uint16)
+        weight = C.c_uint32(0)
+        res = self._lib.blurrily_storage_get(self._h, _u32(reference, "reference"), C.byref(weight), len(codes),
+                                             codes.ctypes.data)
+        if res < 0:
+            _raise_errno()
+        if res == 0:
+            return None
+        return int(weight.value), codes[:res].tolist()
+
+    def get_batch(self, references):
+        """``get`` for every reference at once: ``(weights[n], code_offsets[n + 1], codes)`` -- reference i's codes are
+        ``codes[code_offsets[i]:code_offsets[i + 1]]``, an empty range when the map does not hold it (weight 0)."""
+        self._check_open()
+        refs = self._refs(references)
+        n = len(refs)
+        # each distinct reference once: their codes together are at most the map's trigram count (the library's
+        # extraction also reads each once), so one call always fits; np.zeros only commits the pages written
+        uniq, inv = np.unique(refs, return_inverse=True)
+        n_u = len(uniq)
+        w_u = np.zeros(n_u, dtype=np.uint32)
+        offs_u = np.zeros(n_u + 1, dtype=np.uint64)
+        cap = max(1, min(self.stats()["trigrams"], n_u * 28 * 28 * 28))
+        while True:
+            codes_u = np.zeros(cap, dtype=np.uint16)
+            res = self._lib.blurrily_storage_get_batch(self._h, uniq.ctypes.data if n_u else None, n_u, w_u.ctypes.data,
+                                                       offs_u.ctypes.data, codes_u.ctypes.data, cap)
+            if res == 0:
+                break
+            if C.get_errno() != 34 or int(offs_u[n_u]) <= cap:    # ERANGE: offs_u[n_u] holds the size needed
+                _raise_errno()
+            cap = int(offs_u[n_u])
+        # back to the caller's order, duplicates included
+        starts = offs_u[:-1].astype(np.int64)[inv]
+        lens = np.diff(offs_u.astype(np.int64))[inv]
+        offs = np.zeros(n + 1, dtype=np.uint64)
+        offs[1:] = np.cumsum(lens)
+        at = np.repeat(starts - offs[:-1].astype(np.int64), lens) + np.arange(int(offs[n]), dtype=np.int64)
+        return w_u[inv], offs, codes_u[at]
+
+    def find_batch_by_reference(self, references, limit):
+        """Find what is like each stored reference: element i is ``find(s_i, limit)`` for the string reference i was put
+        with (the reference itself among the rows, normally first; none for a reference the map does not hold).
+        Returns (rows[n, limit, 3] uint32, counts[n] uint32, nb_trigrams[n] uint32)."""
+        self._check_open()
+        refs = self._refs(references)
+        n = len(refs)
+        limit = int(limit) & 0xFFFF
+        rows = np.zeros((n, max(limit, 1), 3), dtype=np.uint32)
+        counts = np.zeros(n, dtype=np.uint32)
+        ntri = np.zeros(n, dtype=np.uint32)
+        res = self._lib.blurrily_storage_find_references(self._h, refs.ctypes.data if n else None, n, limit,
+                                                         rows.ctypes.data, counts.ctypes.data, ntri.ctypes.data)
+        if res < 0:
+            _raise_errno()
+        return rows[:, :limit, :], counts, ntri
+
+    def find_by_reference(self, reference, limit):
+        """``find``'s rows for the string `reference` was put with ([] when the map does not hold it); `limit` as find's."""
+        self._check_open()
+        limit = int(limit)
+        if not -(1 << 31) <= limit <= _U32_MAX:
+            raise OverflowError("limit out of range")
+        if limit > 0x7FFFFFFF:
+            limit -= 1 << 32
+        if limit <= 0:
+            limit = LIMIT_DEFAULT
+        rows, counts, _ = RawMap.find_batch_by_reference(self, [_u32(reference, "reference")], limit & 0xFFFF)
+        return rows[0, :counts[0]].tolist()
+
     def sync_device(self):
         self._check_open()
         if self._lib.blurrily_storage_sync_device(self._h) < 0:
@@ -344,6 +427,17 @@ class Map(RawMap):
     def put_many(self, needles, references, weights=None):
         self._clean_path = None
         return super().put_many([normalize_string(s) for s in needles], references, weights)
+
+    def find_by_reference(self, reference, limit=LIMIT_DEFAULT):
+        return super().find_by_reference(reference, limit)
+
+    def find_batch_by_reference(self, references, limit=LIMIT_DEFAULT):
+        """``[self.find_by_reference(r, limit) for r in references]`` in one GPU batch."""
+        limit = int(limit)
+        if limit <= 0:
+            limit = LIMIT_DEFAULT
+        rows, counts, _ = super().find_batch_by_reference(references, limit)
+        return [rows[i, :counts[i]].tolist() for i in range(len(counts))]
 
     def find_batch(self, needles, limit=LIMIT_DEFAULT):
         """``[self.find(s, limit) for s in needles]`` in one GPU batch."""

@@ -178,6 +178,48 @@ int blurrily_storage_sync_device(trigram_map haystack);
 int blurrily_storage_tune(trigram_map haystack, const char* packed, const uint64_t* offsets,
                           size_t n_given, size_t n, uint16_t limit);
 
+/* By reference.  A map stores trigrams, not strings; these read a stored reference's trigrams back out of the
+ * device image (a reference is a rank, its trigrams the (window, code) slices holding it) and find with them.
+ * All four see the map as it is now: pending puts are served from the delta image, deleted references are not
+ * found, a reference deleted and put again has its new string's trigrams.  Every string has at least one trigram,
+ * so a reference the map holds always has some.  Without a usable GPU they return -1 with errno ENODEV (no CPU
+ * fallback, as for find).  With "devices" > 1 the primary device alone serves them; the rows are the same. */
+
+/* storage.h:72-87 of the reference, where it stayed commented out (there it would read the whole map).  Returns
+ * < 0 on error, 0 if the map does not hold `reference`, else the number of its distinct trigrams.  If the
+ * reference is found and `weight` is not NULL, *weight = the weight it was put with (strlen for weight 0).  Up
+ * to `nb_trigrams` of its codes are copied into `trigrams` (when not NULL), ascending: exactly what
+ * blurrily_tokeniser_parse_string returns for the string it was put with. */
+int blurrily_storage_get(trigram_map haystack, uint32_t reference, uint32_t* weight,
+                         int nb_trigrams, uint16_t* trigrams);
+
+/* n calls of blurrily_storage_get in one.  Writes a CSR: reference i's codes are
+ * codes[code_offsets[i] .. code_offsets[i+1]) (n + 1 offsets), an empty range meaning "not in the map";
+ * weights (optional, n slots) as get's, 0 for a reference not found.  0, or -1 with errno; ERANGE when
+ * codes_cap is too small, code_offsets then filled and code_offsets[n] the capacity needed. */
+int blurrily_storage_get_batch(trigram_map haystack, const uint32_t* references, size_t n,
+                               uint32_t* weights, uint64_t* code_offsets,
+                               uint16_t* codes, size_t codes_cap);
+
+/* Find what is like stored references, in one batch.  Element i is exactly
+ * blurrily_storage_find(haystack, S_i, limit, ...) for any string S_i whose tokenisation is reference i's trigram
+ * set (the normalised string it was put with): the reference itself is one of its rows, normally the first --
+ * not filtered out.  A reference the map does not hold gets 0 rows.  results / counts as for
+ * blurrily_storage_find_batch; nb_trigrams (optional, n slots) receives each reference's number of distinct
+ * trigrams (0: not in the map).  The trigrams are read out of the image once and both the base and the delta
+ * image are searched with them.  0, or -1 with errno. */
+int blurrily_storage_find_references(trigram_map haystack, const uint32_t* references, size_t n,
+                                     uint16_t limit, trigram_match results, uint32_t* counts,
+                                     uint32_t* nb_trigrams);
+
+/* Device-resident variant, under the rules of blurrily_storage_find_batch_device: device pointers on the map's
+ * GPU, enqueued on `stream` (NULL = default stream), the same exceptions that block; in addition the first
+ * by-reference call on a device image uploads its reference table (synchronous copies).  d_nb_trigrams may be
+ * NULL. */
+int blurrily_storage_find_references_device(trigram_map haystack, const uint32_t* d_references, size_t n,
+                                            uint16_t limit, trigram_match d_results, uint32_t* d_counts,
+                                            uint32_t* d_nb_trigrams, void* stream);
+
 /* Tokeniser (ext/blurrily/tokeniser.h:34, tokeniser.c:59-119): `output` needs
  * strlen(input)+1 slots; returns the number of distinct codes, ascending. */
 int blurrily_tokeniser_parse_string(const char* input, uint16_t* output);

@@ -13,13 +13,15 @@
  *   RawMap#put_many(needles, refs, weights) -> trigrams added
  *   RawMap#sync_device                      -> nil        build the device image now
  *   RawMap#set_option(key, value) / #get_option(key)      tunables, "devices" among them (multi-GPU)
+ *   RawMap#find_by_reference(ref, limit)    -> [[ref, matches, weight], ...]   find with a STORED reference's trigrams
+ *   RawMap#get(ref)                         -> [weight, [codes ascending]], or nil when the map does not hold ref
  *
  * Each element of a batch is defined as exactly one RawMap#find (map_ext.c:131-162): limit <= 0 means
  * LIMIT_DEFAULT, rows are [reference, matches, weight].
  *
  * THREADING.  The reference holds the GVL for every call ("Threading"), which
  * is what makes its lock-free map safe: calls on one map are serial.  A batch of half a second should
- * not stop every other Ruby thread, so the two batched finds run WITHOUT the GVL
+ * not stop every other Ruby thread, so the two batched finds (and the two by-reference calls) run WITHOUT the GVL
  * (rb_thread_call_without_gvl) -- and the map, which has no lock of its own (its scratch buffers, its
  * mutation log and its replicas are mutated by a find), is guarded HERE instead: a batch marks its
  * RawMap busy (@blurrily_busy) for as long as the library call runs, and EVERY method that reaches the
@@ -122,6 +124,9 @@ typedef struct {
   uint32_t*       non_ascii;      /* find_batch_raw only */
   uint32_t*       refs;           /* put_many only */
   uint32_t*       weights;
+  int             by_ref;         /* find_by_reference (1) / get (2): refs[0] is the reference */
+  uint16_t*       codes;          /* get only: room for every code */
+  uint32_t        got_weight;
   int             marked_busy;
   int             res, err;
 } batch_call;
@@ -163,6 +168,7 @@ static VALUE batch_call_cleanup(VALUE p)
   if (c->non_ascii)  xfree(c->non_ascii);
   if (c->refs)       xfree(c->refs);
   if (c->weights)    xfree(c->weights);
+  if (c->codes)      xfree(c->codes);
   return Qnil;
 }
 
@@ -171,7 +177,11 @@ static VALUE batch_call_cleanup(VALUE p)
 static void* batch_call_run(void* p)
 {
   batch_call* c = (batch_call*)p;
-  c->res = c->non_ascii
+  if (c->by_ref == 1)
+    c->res = blurrily_storage_find_references(c->map, c->refs, 1, c->limit, c->rows, c->counts, NULL);
+  else if (c->by_ref == 2)
+    c->res = blurrily_storage_get(c->map, c->refs[0], &c->got_weight, 28 * 28 * 28, c->codes);
+  else c->res = c->non_ascii
     ? blurrily_storage_find_batch_raw(c->map, c->in.packed, c->in.offsets, c->in.n, c->limit, c->rows, c->counts, c->non_ascii)
     : blurrily_storage_find_batch(c->map, c->in.packed, c->in.offsets, c->in.n, c->limit, c->rows, c->counts);
   c->err = errno;
@@ -236,6 +246,60 @@ static VALUE blurrily_find_batch(VALUE self, VALUE rb_needles, VALUE rb_limit)
 static VALUE blurrily_find_batch_raw(VALUE self, VALUE rb_needles, VALUE rb_limit)
 {
   return find_batch_common(self, rb_needles, rb_limit, 1);
+}
+
+/* ---- by reference: find_by_reference / get (without the GVL, behind the busy flag, as find_batch) ---- */
+
+static VALUE by_ref_body(VALUE p)
+{
+  batch_call* c = (batch_call*)p;
+  VALUE       out = Qnil;
+  c->map = map_of(c->self);                                        /* raises when closed or busy */
+  c->refs = ALLOC_N(uint32_t, 1);
+  c->refs[0] = NUM2UINT(c->rb_refs);
+  if (c->by_ref == 1) {
+    c->limit  = limit_of(c->rb_limit);
+    c->in.n   = 1;
+    c->rows   = ALLOC_N(trigram_match_t, (size_t)c->limit + 1);
+    c->counts = ALLOC_N(uint32_t, 1);
+  } else {
+    c->codes = ALLOC_N(uint16_t, 28 * 28 * 28);
+  }
+  rb_ivar_set(c->self, rb_intern("@blurrily_busy"), Qtrue);
+  c->marked_busy = 1;
+  rb_thread_call_without_gvl(batch_call_run, c, RUBY_UBF_IO, NULL);
+  if (c->res < 0) {
+    errno = c->err;
+    rb_sys_fail(c->by_ref == 1 ? "blurrily_storage_find_references" : "blurrily_storage_get");
+  }
+  if (c->by_ref == 1) {
+    out = rb_ary_entry(rows_to_ruby(c), 0);
+  } else if (c->res > 0) {
+    VALUE codes = rb_ary_new2(c->res);
+    int   k;
+    for (k = 0; k < c->res; ++k) rb_ary_push(codes, UINT2NUM(c->codes[k]));
+    out = rb_ary_new3(2, rb_uint_new(c->got_weight), codes);
+  }
+  return out;
+}
+
+static VALUE by_ref_common(VALUE self, VALUE rb_ref, VALUE rb_limit, int which)
+{
+  batch_call c;
+  memset(&c, 0, sizeof c);
+  c.self = self; c.rb_refs = rb_ref; c.rb_limit = rb_limit; c.by_ref = which;
+  c.strings = Qnil; c.rb_needles = Qnil; c.rb_weights = Qnil;
+  return rb_ensure(by_ref_body, (VALUE)&c, batch_call_cleanup, (VALUE)&c);
+}
+
+static VALUE blurrily_find_by_reference(VALUE self, VALUE rb_ref, VALUE rb_limit)
+{
+  return by_ref_common(self, rb_ref, rb_limit, 1);
+}
+
+static VALUE blurrily_get(VALUE self, VALUE rb_ref)
+{
+  return by_ref_common(self, rb_ref, Qnil, 2);
 }
 
 /* ---- put_many (holds the GVL: host work, as the gem's put) -------------------------------------- */
@@ -312,4 +376,6 @@ void Init_map_ext(void)
   rb_define_method(cRawMap, "sync_device",    blurrily_sync_device,    0);
   rb_define_method(cRawMap, "set_option",     blurrily_set_option,     2);
   rb_define_method(cRawMap, "get_option",     blurrily_get_option,     1);
+  rb_define_method(cRawMap, "find_by_reference", blurrily_find_by_reference, 2);
+  rb_define_method(cRawMap, "get",            blurrily_get,            1);
 }
