@@ -120,6 +120,14 @@ def lib():
                                                        C.c_void_p]),
         "blurrily_storage_find_references_device": (C.c_int, [vp, C.c_void_p, C.c_size_t, C.c_uint16, C.c_void_p,
                                                               C.c_void_p, C.c_void_p, C.c_void_p]),
+        "blurrily_scope_new": (C.c_int, [vp, C.c_void_p, C.c_size_t, vpp]),
+        "blurrily_scope_close": (C.c_int, [vpp]),
+        "blurrily_scope_members": (C.c_int, [vp, C.POINTER(C.c_uint32)]),
+        "blurrily_storage_find_in": (C.c_int, [vp, vp, C.c_char_p, C.c_uint16, C.c_void_p]),
+        "blurrily_storage_find_batch_in": (C.c_int, [vp, vp, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint16,
+                                                     C.c_void_p, C.c_void_p]),
+        "blurrily_storage_find_batch_in_device": (C.c_int, [vp, vp, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                                            C.c_uint16, C.c_void_p, C.c_void_p, C.c_void_p]),
     }
     for name, (res, args) in sig.items():
         try:
@@ -148,4 +156,8 @@ EXPORTED_SYMBOLS = (
     # by reference (reference storage.h:72-87's commented-out get, and find by a stored reference)
     "blurrily_storage_get", "blurrily_storage_get_batch", "blurrily_storage_find_references",
     "blurrily_storage_find_references_device",
+) + (
+    # scoped find: a fixed set of references, and finds among them only
+    "blurrily_scope_new", "blurrily_scope_close", "blurrily_scope_members", "blurrily_storage_find_in",
+    "blurrily_storage_find_batch_in", "blurrily_storage_find_batch_in_device",
 )

@@ -183,6 +183,16 @@ struct trigram_map_t {
   hipEvent_t  ev[4] = {nullptr, nullptr, nullptr, nullptr};
   DeviceBuffer ws_codes, ws_small, ws_parts, ws_io_in, ws_io_out;
   DeviceBuffer ws_refs;                 // by reference: the extraction's arrays and the references' codes (refs_extract)
+  // scoped find: options "scope_strategy" (0 auto, 1 mask, 2 direct) and "scope_direct_max" (the
+  // scope's member codes up to which auto scores the members directly; 0: auto always takes the mask), and a pinned
+  // page the device maps, for small host batches the direct strategy serves without copies.  The default sits just
+  // above the largest scope measured where direct wins both batches and single finds (configs[2], 10^4 members, 140 544
+  // codes: 21x the mask's needles/s, 82 against 124 us a find; at 416 379 codes it still wins batches 4.5x but single
+  // finds take 193 against 122 us -- profiles/scope_geonames.json)
+  uint32_t    scope_strategy = 0;
+  uint64_t    scope_direct_max = 150000;
+  unsigned char* h_scope = nullptr;     // [kScopePageBytes in | kScopePageBytes out]
+  unsigned char* d_scope = nullptr;     // the same memory as the device addresses it
   unsigned char* h_stage = nullptr;     // pinned host staging: [kStageBytes in | kStageBytes out]
   // the single find's own launch (find_one): a stream, host-coherent pinned memory the kernel writes rows, count and a
   // sequence word into, the per-workgroup lists and the ticket on the device
@@ -353,11 +363,13 @@ int do_launch_find(bool counted_build, const FindArgs& a, bool long_needles, uin
 
 // Enqueue tokenise + find for n device-resident needles -- or, with `rn`, find for n references whose trigrams
 // launch_refs_extract has left on the device (d_packed / d_offsets unused): ref_needles_kernel in tokenise_kernel's place,
-// every launch after it the same.
+// every launch after it the same.  `scoped`: d_tomb is a scope's mask (run_find); the call neither measures nor watches
+// a class's choice of sweep -- it takes the measured one, or the static rule -- so that unscoped batches never depend
+// on scoped ones.
 int run_find_on(trigram_map m, const DeviceIndex& ix, const uint32_t* d_code_total, const uint32_t* d_tomb,
                 const char* d_packed, size_t packed_bytes, const uint64_t* d_offsets, size_t n, uint16_t limit,
                 trigram_match d_results, uint32_t* d_counts, uint32_t* d_nb, bool maybe_long, bool maybe_mid,
-                hipStream_t stream, const RefNeedles* rn = nullptr) {
+                hipStream_t stream, const RefNeedles* rn = nullptr, bool scoped = false) {
   if (n == 0) return 0;
   if (n > 0xFFFFFFF0ull) { errno = EINVAL; return -1; }
   const bool is_base = &ix == &m->dev;                 // (the delta image of pending puts is searched the same way)
@@ -582,7 +594,7 @@ int run_find_on(trigram_map m, const DeviceIndex& ix, const uint32_t* d_code_tot
       const int cls = n_cls < 16384 ? (limit > 32 ? 7 : 6) : (limit > 32 ? 3 : 0) + (n_cls < 65536 ? 0 : n_cls < 262144 ? 1 : 2);
       const bool tunable = m->ws_autotune && is_base && n_cls >= 129 && (leave_possible || ws_possible);
       // what the class's last batch took, if it has finished (never waited for): slow against the measurement?
-      if (tunable && !cb && m->watch_pending[cls] && hipEventQuery(m->watch_ev[cls][1]) == hipSuccess) {
+      if (tunable && !cb && !scoped && m->watch_pending[cls] && hipEventQuery(m->watch_ev[cls][1]) == hipSuccess) {
         float ms = 0.f;
         m->watch_pending[cls] = false;
         // (only a batch of about the size the class was measured at is held against that figure: classes 6 / 7 span 129 ..
@@ -603,13 +615,14 @@ int run_find_on(trigram_map m, const DeviceIndex& ix, const uint32_t* d_code_tot
           }
         }
       }
-      if (m->retune_holdoff[cls]) --m->retune_holdoff[cls];
+      if (m->retune_holdoff[cls] && !scoped) --m->retune_holdoff[cls];
       if (!tunable) {
         choice = static_choice;
       } else if (m->ws_choice[cls] != 0 && (m->ws_choice[cls] != 2 || ws_possible) && (m->ws_choice[cls] != 3 || leave_possible)) {
         choice = m->ws_choice[cls];
-      } else if (cb) {
-        choice = static_choice;                        // (counters must describe ONE sweep: an unmeasured class is not measured here)
+      } else if (cb || scoped) {
+        choice = static_choice;                        // (counters must describe ONE sweep: an unmeasured class is not measured here;
+                                                       // nor by a scoped call)
       } else {
         if (!m->tune_ev[0]) {
           hipEvent_t ev[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -653,7 +666,7 @@ int run_find_on(trigram_map m, const DeviceIndex& ix, const uint32_t* d_code_tot
         a.nm_cmin = 0;
         goto short_needles_done;
       }
-      const bool watch = tunable && !cb && m->ws_choice[cls] == choice && m->tuned_us_per_needle[cls] > 0.f;
+      const bool watch = tunable && !cb && !scoped && m->ws_choice[cls] == choice && m->tuned_us_per_needle[cls] > 0.f;
       if (watch) {
         if (!m->watch_ev[cls][1]) {                    // (both events or none: a half-made pair would be recorded into)
           hipEvent_t e0 = nullptr, e1 = nullptr;
@@ -700,9 +713,11 @@ int run_find_on(trigram_map m, const DeviceIndex& ix, const uint32_t* d_code_tot
 
 // Enqueue tokenise + find for n device-resident needles on the map's current contents.
 // (rn: the needles are references, extracted once: both images are searched with the same codes)
+// (sm: a scoped find's masks, in the tombstone bitmap's place: they exclude the deleted ranks too)
+struct ScopeMasks { const uint32_t* base; const uint32_t* delta; };
 int run_find(trigram_map m, const char* d_packed, size_t packed_bytes, const uint64_t* d_offsets, size_t n,
              uint16_t limit, trigram_match d_results, uint32_t* d_counts, uint32_t* d_nb, bool maybe_long,
-             bool maybe_mid, hipStream_t stream, const RefNeedles* rn = nullptr) {
+             bool maybe_mid, hipStream_t stream, const RefNeedles* rn = nullptr, const ScopeMasks* sm = nullptr) {
   if (m->collect_stats) {
     if (!m->d_stats) BLURRILY_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&m->d_stats), kStatAllSlots * 8));
     BLURRILY_HIP_TRY(hipMemsetAsync(m->d_stats, 0, kStatAllSlots * 8, stream));
@@ -712,8 +727,8 @@ int run_find(trigram_map m, const char* d_packed, size_t packed_bytes, const uin
   }
   if (apply_tombstones(m, stream) < 0) return -1;
   if (log_empty(m))
-    return run_find_on(m, m->dev, m->dev.d_code_total, nullptr, d_packed, packed_bytes, d_offsets, n, limit,
-                       d_results, d_counts, d_nb, maybe_long, maybe_mid, stream, rn);
+    return run_find_on(m, m->dev, m->dev.d_code_total, sm ? sm->base : nullptr, d_packed, packed_bytes, d_offsets, n,
+                       limit, d_results, d_counts, d_nb, maybe_long, maybe_mid, stream, rn, sm != nullptr);
   // base image (minus tombstones) and delta image hold disjoint references: find on both, merge
   const size_t row_bytes = std::max<size_t>(n * size_t(limit) * sizeof(trigram_match_t), 16);
   if (m->ws_base_rows.reserve(row_bytes, stream) < 0 || m->ws_base_counts.reserve(n * 4, stream) < 0 ||
@@ -723,13 +738,15 @@ int run_find(trigram_map m, const char* d_packed, size_t packed_bytes, const uin
   uint32_t* base_counts = static_cast<uint32_t*>(m->ws_base_counts.p);
   trigram_match delta_rows = static_cast<trigram_match>(m->ws_delta_rows.p);
   uint32_t* delta_counts = static_cast<uint32_t*>(m->ws_delta_counts.p);
-  if (run_find_on(m, m->dev, m->d_code_total_now, log_of(m)->n_tomb ? m->dev.d_tomb : nullptr, d_packed, packed_bytes,
-                  d_offsets, n, limit, base_rows, base_counts, d_nb, maybe_long, maybe_mid, stream, rn) < 0)
+  const uint32_t* base_tomb = sm ? sm->base : log_of(m)->n_tomb ? m->dev.d_tomb : nullptr;
+  if (run_find_on(m, m->dev, m->d_code_total_now, base_tomb, d_packed, packed_bytes, d_offsets, n, limit, base_rows,
+                  base_counts, d_nb, maybe_long, maybe_mid, stream, rn, sm != nullptr) < 0)
     return -1;
   if (log_of(m)->pending.empty()) {
     BLURRILY_HIP_TRY(hipMemsetAsync(delta_counts, 0, n * 4, stream));
-  } else if (run_find_on(m, m->delta, m->delta.d_code_total, nullptr, d_packed, packed_bytes, d_offsets, n, limit,
-                         delta_rows, delta_counts, nullptr, maybe_long, maybe_mid, stream, rn) < 0) {
+  } else if (run_find_on(m, m->delta, m->delta.d_code_total, sm ? sm->delta : nullptr, d_packed, packed_bytes, d_offsets,
+                         n, limit, delta_rows, delta_counts, nullptr, maybe_long, maybe_mid, stream, rn,
+                         sm != nullptr) < 0) {
     return -1;
   }
   return launch_merge_rows(base_rows, base_counts, delta_rows, delta_counts, uint32_t(n), limit, d_results,
@@ -1011,6 +1028,7 @@ int blurrily_storage_close(trigram_map* haystack) {
     m->ws_codes.release(); m->ws_small.release(); m->ws_parts.release(); m->ws_io_in.release();
     m->ws_io_out.release(); m->ws_tomb.release(); m->ws_flags.release(); m->ws_refs.release();
     if (m->h_stage) (void)hipHostFree(m->h_stage);
+    if (m->h_scope) (void)hipHostFree(m->h_scope);
     if (m->one.stream) { (void)hipStreamSynchronize(m->one.stream); (void)hipStreamDestroy(m->one.stream); }
     if (m->one.h_out) (void)hipHostFree(m->one.h_out);
     m->one.d_parts.release();
@@ -1613,6 +1631,9 @@ struct RefExtract {
   RefNeedles needles;
   const uint64_t* win_base_total;   // [1] distinct references found
   const uint64_t* slot_start;       // [n + 1]: slot_start[*win_base_total] codes in all
+  const uint2*    loc;              // [n] where each reference was found (RefArgs::loc)
+  uint32_t        win0_delta;       // the delta image's first window in loc's numbering (with_delta)
+  bool            with_delta;
 };
 static int refs_extract(trigram_map m, const uint32_t* d_refs, size_t n, hipStream_t stream, RefExtract* out) {
   if (n > 0xFFFFFFF0ull) { errno = EINVAL; return -1; }
@@ -1656,6 +1677,9 @@ static int refs_extract(trigram_map m, const uint32_t* d_refs, size_t n, hipStre
   out->needles = RefNeedles{a.codes, a.qoff, a.ntri, a.weight, uint32_t(n), code_slots};
   out->win_base_total = a.win_base + W;
   out->slot_start = a.slot_start;
+  out->loc = a.loc;
+  out->win0_delta = m->dev.n_windows;
+  out->with_delta = with_delta;
   return 0;
 }
 
@@ -1755,6 +1779,297 @@ int blurrily_storage_find_references(trigram_map m, const uint32_t* references, 
   if (limit) BLURRILY_HIP_TRY(hipMemcpyAsync(results, d_rows, row_bytes, hipMemcpyDeviceToHost, stream));
   BLURRILY_HIP_TRY(hipStreamSynchronize(stream));
   return 0;
+}
+
+}  // extern "C"
+
+// ---- scoped find (blurrily_scope_* / blurrily_storage_find_in / _find_batch_in[_device]) ---------
+// A scope keeps its references sorted and distinct.  Its device state is made at the first scoped find and whenever
+// the map has changed since (base_builds, log_version): the members are looked up and extracted as by reference
+// (refs_extract), a mask per image excludes every rank but the members held now, and -- for scopes the direct strategy
+// may serve -- the held members' codes, weights and references in (weight, reference) order are copied into the
+// scope's own buffers (ws_refs is every later by-reference call's).
+struct blurrily_scope_t {
+  trigram_map           map = nullptr;
+  std::vector<uint32_t> refs;           // sorted, distinct
+  bool         ready = false;
+  uint64_t     built_base = 0, built_log = 0;
+  uint32_t     n_held = 0;               // members held at the last preparation
+  DeviceBuffer d_refs, d_mask[2];        // masks: base image, delta image (pending puts)
+  bool         has_delta = false;
+  // direct form (n_direct members: m_off [n_direct + 1] | m_ref | m_weight | m_codes)
+  bool         direct = false;
+  uint32_t     n_direct = 0;
+  uint64_t     direct_codes = 0;
+  DeviceBuffer d_direct;
+  const uint32_t *m_off = nullptr, *m_ref = nullptr, *m_weight = nullptr;
+  const uint16_t* m_codes = nullptr;
+};
+
+namespace {
+
+constexpr size_t kScopePageBytes = size_t(1) << 16;   // small direct batches: needles in, rows out, through mapped memory
+
+// The scope's device state for the map as it is now (the image brought up to date and tombstones applied first).
+int scope_prepare(trigram_map m, blurrily_scope sc, hipStream_t stream) {
+  if (m->host->dirty_buckets()) m->host->sort_dirty_buckets();
+  if (ensure_device(m) < 0) return -1;
+  if (apply_tombstones(m, stream) < 0) return -1;
+  if (sc->ready && sc->built_base == m->base_builds && sc->built_log == log_of(m)->log_version) return 0;
+  sc->ready = false;
+  sc->direct = false;
+  sc->n_held = 0;
+  const size_t n = sc->refs.size();
+  const bool with_delta = !log_of(m)->pending.empty() && m->delta.device >= 0;
+  const uint32_t words[2] = {(m->dev.n_refs + 31u) / 32u + 1u, with_delta ? (m->delta.n_refs + 31u) / 32u + 1u : 1u};
+  for (int k = 0; k < 2; ++k)
+    if (sc->d_mask[k].reserve(size_t(words[k]) * 4, stream) < 0) return -1;
+  sc->has_delta = with_delta;
+  ScopeMaskArgs ma{};
+  ma.n_img = with_delta ? 2u : 1u;
+  ma.win0[0] = 0; ma.win0[1] = m->dev.n_windows;
+  ma.mask[0] = static_cast<uint32_t*>(sc->d_mask[0].p); ma.mask[1] = static_cast<uint32_t*>(sc->d_mask[1].p);
+  ma.mask_words[0] = words[0]; ma.mask_words[1] = words[1];
+  if (n == 0) {
+    if (launch_scope_mask(ma, stream) < 0) return -1;
+  } else {
+    if (sc->d_refs.reserve(n * sizeof(uint32_t), stream) < 0) return -1;
+    BLURRILY_HIP_TRY(hipMemcpyAsync(sc->d_refs.p, sc->refs.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    RefExtract x;
+    if (refs_extract(m, static_cast<const uint32_t*>(sc->d_refs.p), n, stream, &x) < 0) return -1;
+    ma.loc = x.loc; ma.n = uint32_t(n);
+    if (launch_scope_mask(ma, stream) < 0) return -1;
+    std::vector<uint32_t> ntri(n), wgt(n);
+    BLURRILY_HIP_TRY(hipMemcpyAsync(ntri.data(), x.needles.ntri, n * 4, hipMemcpyDeviceToHost, stream));
+    BLURRILY_HIP_TRY(hipMemcpyAsync(wgt.data(), x.needles.weight, n * 4, hipMemcpyDeviceToHost, stream));
+    BLURRILY_HIP_TRY(hipStreamSynchronize(stream));
+    std::vector<uint32_t> held;
+    uint64_t codes = 0;
+    uint32_t widest = 0;
+    for (size_t i = 0; i < n; ++i)
+      if (ntri[i]) { held.push_back(uint32_t(i)); codes += ntri[i]; widest = std::max(widest, ntri[i]); }
+    sc->n_held = uint32_t(held.size());
+    // the direct form, when the direct strategy can serve the scope at all
+    if (!held.empty() && held.size() <= kScopeMaxMembers && widest <= kScopeMaxMemberCodes) {
+      std::vector<uint64_t> qoff(n);
+      uint64_t slots = 0, total = 0;
+      BLURRILY_HIP_TRY(hipMemcpyAsync(qoff.data(), x.needles.qoff, n * 8, hipMemcpyDeviceToHost, stream));
+      BLURRILY_HIP_TRY(hipMemcpyAsync(&slots, x.win_base_total, 8, hipMemcpyDeviceToHost, stream));
+      BLURRILY_HIP_TRY(hipStreamSynchronize(stream));
+      BLURRILY_HIP_TRY(hipMemcpy(&total, x.slot_start + slots, 8, hipMemcpyDeviceToHost));
+      std::vector<uint16_t> all(total);
+      if (total) BLURRILY_HIP_TRY(hipMemcpy(all.data(), x.needles.codes + n, total * sizeof(uint16_t), hipMemcpyDeviceToHost));
+      // member order: weight ascending, then reference (the rows' order among equal matches)
+      std::sort(held.begin(), held.end(), [&](uint32_t a, uint32_t b) {
+        return wgt[a] != wgt[b] ? wgt[a] < wgt[b] : sc->refs[a] < sc->refs[b];
+      });
+      const size_t nd = held.size();
+      const size_t o_ref = align_up((nd + 1) * 4, 256), o_wgt = o_ref + align_up(nd * 4, 256);
+      const size_t o_codes = o_wgt + align_up(nd * 4, 256), bytes = o_codes + std::max<size_t>(codes * 2, 16);
+      std::vector<unsigned char> h(bytes, 0);
+      uint32_t* off = reinterpret_cast<uint32_t*>(h.data());
+      uint32_t* ref = reinterpret_cast<uint32_t*>(h.data() + o_ref);
+      uint32_t* weight = reinterpret_cast<uint32_t*>(h.data() + o_wgt);
+      uint16_t* cd = reinterpret_cast<uint16_t*>(h.data() + o_codes);
+      off[0] = 0;
+      for (size_t j = 0; j < nd; ++j) {
+        const uint32_t i = held[j];
+        std::memcpy(cd + off[j], all.data() + (qoff[i] + i - n), size_t(ntri[i]) * sizeof(uint16_t));
+        off[j + 1] = off[j] + ntri[i];
+        ref[j] = sc->refs[i];
+        weight[j] = wgt[i];
+      }
+      if (sc->d_direct.reserve(bytes, stream) < 0) return -1;
+      BLURRILY_HIP_TRY(hipMemcpy(sc->d_direct.p, h.data(), bytes, hipMemcpyHostToDevice));
+      unsigned char* d = static_cast<unsigned char*>(sc->d_direct.p);
+      sc->m_off = reinterpret_cast<const uint32_t*>(d);
+      sc->m_ref = reinterpret_cast<const uint32_t*>(d + o_ref);
+      sc->m_weight = reinterpret_cast<const uint32_t*>(d + o_wgt);
+      sc->m_codes = reinterpret_cast<const uint16_t*>(d + o_codes);
+      sc->n_direct = uint32_t(nd);
+      sc->direct_codes = codes;
+      sc->direct = true;
+    }
+  }
+  sc->built_base = m->base_builds;
+  sc->built_log = log_of(m)->log_version;
+  sc->ready = true;
+  return 0;
+}
+
+// Which strategy serves a scoped find of `limit` (the scope prepared): the direct one declines limits above its pool and
+// scopes without a direct form (above kScopeMaxMembers held members, or a member of more than 255 distinct trigrams);
+// auto takes it for scopes of at most "scope_direct_max" member codes.
+bool scope_takes_direct(const trigram_map_t* m, const blurrily_scope_t* sc, uint16_t limit) {
+  if (m->scope_strategy == 1 || !sc->direct || limit == 0 || limit > kScopeMaxKeep) return false;
+  return m->scope_strategy == 2 || sc->direct_codes <= m->scope_direct_max;
+}
+
+// Enqueue a scoped find of n device-resident needles on the prepared scope: rows of only its members.
+int scope_run(trigram_map m, blurrily_scope sc, const char* d_packed, size_t packed_bytes, const uint64_t* d_offsets,
+              size_t n, uint16_t limit, trigram_match d_results, uint32_t* d_counts, bool maybe_long, bool maybe_mid,
+              hipStream_t stream) {
+  if (n == 0) return 0;
+  if (n > 0xFFFFFFF0ull) { errno = EINVAL; return -1; }
+  if (sc->n_held == 0 || limit == 0) {                 // nothing in the scope is held: no rows
+    NameScope name_scope(&m->last_kernels);
+    m->last_kernels.clear();
+    m->last_sweep = 0;
+    BLURRILY_HIP_TRY(hipMemsetAsync(d_counts, 0, n * sizeof(uint32_t), stream));
+    return 0;
+  }
+  if (scope_takes_direct(m, sc, limit)) {
+    NameScope name_scope(&m->last_kernels);
+    m->last_kernels.clear();
+    m->last_sweep = 0;
+    ScopeFindArgs a{};
+    a.packed = d_packed; a.offsets = d_offsets; a.n = uint32_t(n);
+    a.m_off = sc->m_off; a.m_codes = sc->m_codes; a.m_ref = sc->m_ref; a.m_weight = sc->m_weight;
+    a.n_members = sc->n_direct; a.limit = limit; a.results = d_results; a.counts = d_counts;
+    return launch_scope_find(a, stream);
+  }
+  const ScopeMasks sm{static_cast<const uint32_t*>(sc->d_mask[0].p),
+                      sc->has_delta ? static_cast<const uint32_t*>(sc->d_mask[1].p) : nullptr};
+  if (m->timing && !m->ev[0])
+    for (auto& e : m->ev) BLURRILY_HIP_TRY(hipEventCreate(&e));
+  return run_find(m, d_packed, packed_bytes, d_offsets, n, limit, d_results, d_counts, nullptr, maybe_long, maybe_mid,
+                  stream, nullptr, &sm);
+}
+
+int scope_check(trigram_map m, blurrily_scope sc) {
+  if (!m || !sc || sc->map != m) { errno = EINVAL; return -1; }
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int blurrily_scope_new(trigram_map m, const uint32_t* references, size_t n, blurrily_scope* scope) {
+  if (!m || !scope || (n && !references)) { errno = EINVAL; return -1; }
+  blurrily_scope sc = new (std::nothrow) blurrily_scope_t();
+  if (!sc) { errno = ENOMEM; return -1; }
+  try {
+    sc->refs.assign(references, references + n);
+  } catch (const std::bad_alloc&) {
+    delete sc;
+    errno = ENOMEM;
+    return -1;
+  }
+  std::sort(sc->refs.begin(), sc->refs.end());
+  sc->refs.erase(std::unique(sc->refs.begin(), sc->refs.end()), sc->refs.end());
+  sc->map = m;
+  *scope = sc;
+  return 0;
+}
+
+int blurrily_scope_close(blurrily_scope* scope) {
+  if (!scope) { errno = EINVAL; return -1; }
+  blurrily_scope sc = *scope;
+  if (sc) {
+    if (sc->d_refs.p || sc->d_mask[0].p || sc->d_mask[1].p || sc->d_direct.p) (void)hipDeviceSynchronize();
+    sc->d_refs.release(); sc->d_mask[0].release(); sc->d_mask[1].release(); sc->d_direct.release();
+    delete sc;
+  }
+  *scope = nullptr;
+  return 0;
+}
+
+int blurrily_scope_members(blurrily_scope scope, uint32_t* held) {
+  if (!scope || !held || !scope->map) { errno = EINVAL; return -1; }
+  uint32_t k = 0;
+  for (uint32_t r : scope->refs) k += scope->map->host->holds(r) ? 1u : 0u;
+  *held = k;
+  return 0;
+}
+
+int blurrily_storage_find_batch_in_device(trigram_map m, blurrily_scope sc, const char* d_packed, size_t packed_bytes,
+                                          const uint64_t* d_offsets, size_t n, uint16_t limit,
+                                          trigram_match d_results, uint32_t* d_counts, void* stream) {
+  if (scope_check(m, sc) < 0) return -1;
+  DeviceScope scope(m->dev.device);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (scope_prepare(m, sc, st) < 0) return -1;
+  return scope_run(m, sc, d_packed, packed_bytes, d_offsets, n, limit, d_results, d_counts, true, true, st);
+}
+
+int blurrily_storage_find_batch_in(trigram_map m, blurrily_scope sc, const char* packed, const uint64_t* offsets,
+                                   size_t n, uint16_t limit, trigram_match results, uint32_t* counts) {
+  if (scope_check(m, sc) < 0) return -1;
+  if (n && (!packed || !offsets || !counts || (limit && !results))) { errno = EINVAL; return -1; }
+  DeviceScope scope(m->dev.device);
+  hipStream_t stream = nullptr;
+  if (scope_prepare(m, sc, stream) < 0) return -1;     // (without a GPU this is what fails, with ENODEV)
+  if (n == 0) return 0;
+  size_t max_len = 0;
+  for (size_t i = 0; i < n && max_len <= 126; ++i) {   // (what the sweeps need to know: > 63, > 126)
+    const size_t cap = size_t(offsets[i + 1] - offsets[i]);
+    if (cap <= max_len) continue;
+    const char* s = packed + offsets[i];
+    const void* nul = std::memchr(s, 0, cap);
+    max_len = std::max(max_len, nul ? size_t(static_cast<const char*>(nul) - s) : cap);
+  }
+  const size_t packed_bytes = size_t(offsets[n]);
+  const size_t off_bytes = (n + 1) * sizeof(uint64_t);
+  const size_t row_bytes = n * size_t(limit) * sizeof(trigram_match_t);
+  const size_t cnt_bytes = n * sizeof(uint32_t);
+  const size_t in_bytes = align_up(off_bytes, 256) + std::max<size_t>(packed_bytes, 16);
+  const size_t out_bytes = align_up(cnt_bytes, 256) + std::max<size_t>(row_bytes, 16);
+  // a small batch the direct strategy serves: needles read and rows written by the kernel in mapped pinned memory --
+  // one launch, no copies
+  if (in_bytes <= kScopePageBytes && out_bytes <= kScopePageBytes && sc->n_held && scope_takes_direct(m, sc, limit)) {
+    if (!m->h_scope) {
+      unsigned char *h = nullptr, *d = nullptr;
+      hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&h), 2 * kScopePageBytes, hipHostMallocMapped | hipHostMallocCoherent);
+      if (e == hipSuccess) e = hipHostGetDevicePointer(reinterpret_cast<void**>(&d), h, 0);
+      if (e != hipSuccess) {
+        std::fprintf(stderr, "blurrily_hip: the scoped find's pinned page: %s\n", hipGetErrorString(e));
+        if (h) (void)hipHostFree(h);
+        errno = (e == hipErrorOutOfMemory) ? ENOMEM : EIO;
+        return -1;
+      }
+      m->h_scope = h; m->d_scope = d;
+    }
+    unsigned char* h_in = m->h_scope;
+    unsigned char* h_out = m->h_scope + kScopePageBytes;
+    std::memcpy(h_in, offsets, off_bytes);
+    if (packed_bytes) std::memcpy(h_in + align_up(off_bytes, 256), packed, packed_bytes);
+    unsigned char* d_in = m->d_scope;
+    unsigned char* d_out = m->d_scope + kScopePageBytes;
+    if (scope_run(m, sc, reinterpret_cast<const char*>(d_in + align_up(off_bytes, 256)), packed_bytes,
+                  reinterpret_cast<const uint64_t*>(d_in), n, limit,
+                  reinterpret_cast<trigram_match>(d_out + align_up(cnt_bytes, 256)), reinterpret_cast<uint32_t*>(d_out),
+                  false, false, stream) < 0)
+      return -1;
+    BLURRILY_HIP_TRY(hipStreamSynchronize(stream));
+    std::memcpy(counts, h_out, cnt_bytes);
+    if (limit) std::memcpy(results, h_out + align_up(cnt_bytes, 256), row_bytes);
+    return 0;
+  }
+  if (m->ws_io_in.reserve(in_bytes, stream) < 0 || m->ws_io_out.reserve(out_bytes, stream) < 0) return -1;
+  unsigned char* d_in = static_cast<unsigned char*>(m->ws_io_in.p);
+  unsigned char* d_out = static_cast<unsigned char*>(m->ws_io_out.p);
+  BLURRILY_HIP_TRY(hipMemcpyAsync(d_in, offsets, off_bytes, hipMemcpyHostToDevice, stream));
+  if (packed_bytes)
+    BLURRILY_HIP_TRY(hipMemcpyAsync(d_in + align_up(off_bytes, 256), packed, packed_bytes, hipMemcpyHostToDevice, stream));
+  uint32_t* d_counts = reinterpret_cast<uint32_t*>(d_out);
+  trigram_match d_rows = reinterpret_cast<trigram_match>(d_out + align_up(cnt_bytes, 256));
+  if (scope_run(m, sc, reinterpret_cast<const char*>(d_in + align_up(off_bytes, 256)), packed_bytes,
+                reinterpret_cast<const uint64_t*>(d_in), n, limit, d_rows, d_counts, max_len > 126, max_len > 63,
+                stream) < 0)
+    return -1;
+  BLURRILY_HIP_TRY(hipMemcpyAsync(counts, d_counts, cnt_bytes, hipMemcpyDeviceToHost, stream));
+  if (limit) BLURRILY_HIP_TRY(hipMemcpyAsync(results, d_rows, row_bytes, hipMemcpyDeviceToHost, stream));
+  BLURRILY_HIP_TRY(hipStreamSynchronize(stream));
+  return 0;
+}
+
+int blurrily_storage_find_in(trigram_map m, blurrily_scope sc, const char* needle, uint16_t limit, trigram_match results) {
+  if (!needle) { errno = EINVAL; return -1; }
+  const uint64_t offsets[2] = {0, std::strlen(needle)};
+  uint32_t count = 0;
+  if (blurrily_storage_find_batch_in(m, sc, needle, offsets, 1, limit, results, &count) < 0) return -1;
+  return int(count);
 }
 
 int blurrily_storage_find_batch(trigram_map m, const char* packed, const uint64_t* offsets, size_t n,
@@ -1886,7 +2201,7 @@ constexpr OptionSlot kMapOptions[] = {
     {"tuned_leave_us", 0, 0}, {"small_sweep", 0, 1}, {"small_min_needles", 0, 1ll << 32},
     {"one_launch", 0, 1}, {"one_taken", 0, 0}, {"one_windows_per_wg", 0, 1 << 20},
     {"retunes", 0, 0}, {"tune_inject", 0, 3}, {"mid_workgroups", 64, 1 << 16}, {"few_max", 1, kMidMaxNeedles}, {"mid_max", 0, kMidMaxNeedles},
-    {"latency_tasks", 0, 16}};
+    {"latency_tasks", 0, 16}, {"scope_strategy", 0, 2}, {"scope_direct_max", 0, 1ll << 40}};
 constexpr OptionSlot kProcessOptions[] = {{"host_threads", 0, 256}, {"build_trace", 0, 1}};
 int find_option(const OptionSlot* tab, size_t n, const char* key) {
   for (size_t i = 0; i < n; ++i) if (std::strcmp(tab[i].key, key) == 0) return int(i);
@@ -1939,6 +2254,8 @@ int blurrily_storage_set_option(trigram_map m, const char* key, long long value)
     case 27: m->one.few_max = uint32_t(value); return 0;
     case 28: m->one.mid_max = uint32_t(value); return 0;
     case 29: m->latency_tasks = uint32_t(value); return 0;
+    case 30: m->scope_strategy = uint32_t(value); return 0;   // (scoped finds only: nothing to measure again)
+    case 31: m->scope_direct_max = uint64_t(value); return 0;
   }
   if (i != 6) std::fill(std::begin(m->ws_choice), std::end(m->ws_choice), 0);   // the sweep's choice is measured again
   return 0;
@@ -1988,6 +2305,8 @@ int blurrily_storage_get_option(trigram_map m, const char* key, long long* value
     case 27: *value = m->one.few_max; return 0;
     case 28: *value = m->one.mid_max; return 0;
     case 29: *value = m->latency_tasks; return 0;
+    case 30: *value = m->scope_strategy; return 0;
+    case 31: *value = (long long)m->scope_direct_max; return 0;
     default: errno = EINVAL; return -1;
   }
 }

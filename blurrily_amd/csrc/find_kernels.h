@@ -229,6 +229,38 @@ int launch_ref_needles(const RefNeedles& r, const uint32_t* code_total, const ui
                        uint32_t* q_nb, uint32_t* q_start, uint32_t* big_list, uint32_t* big_count, uint32_t* mid_list,
                        uint32_t* mid_count, hipStream_t stream);
 
+// Scoped find (kernels/scope.inc).
+// The mask strategy: what refs_lookup_kernel found of a scope's members (RefArgs::loc) becomes, per image, a bitmap of
+// the ranks a scoped find must pass over (bit set = excluded), used in the tombstone bitmap's place.
+struct ScopeMaskArgs {
+  const uint2* loc;                // [n] {window of both images, in-window rank}, window ~0u: not held
+  uint32_t     n;
+  uint32_t     n_img;
+  uint32_t     win0[2];            // first window of the base / the delta image
+  uint32_t*    mask[2];            // [ceil(n_refs / 32) + 1] per image: all set by the launch, members' ranks cleared
+  uint32_t     mask_words[2];
+};
+int launch_scope_mask(const ScopeMaskArgs& a, hipStream_t stream);
+// The direct strategy: the held members scored against each needle, one workgroup per needle.  Member i (in (weight,
+// reference) order) has the distinct codes m_codes[m_off[i] .. m_off[i+1]), at most kScopeMaxMemberCodes of them.
+constexpr uint32_t kScopeMaxKeep        = 256;     // limits the direct strategy serves (1..)
+constexpr uint32_t kScopeMaxMembers     = 57344;   // members it serves: a byte of matches each in LDS
+constexpr uint32_t kScopeMaxMemberCodes = 255;     // distinct trigrams of a member: its matches fit a byte
+struct ScopeFindArgs {
+  const char*      packed;         // needles as for the batch (device, or host memory the device maps)
+  const uint64_t*  offsets;        // [n + 1]
+  uint32_t         n;
+  const uint32_t*  m_off;          // [n_members + 1]
+  const uint16_t*  m_codes;
+  const uint32_t*  m_ref;          // [n_members]
+  const uint32_t*  m_weight;       // [n_members]
+  uint32_t         n_members;
+  uint32_t         limit;          // 1 .. kScopeMaxKeep
+  trigram_match_t* results;        // [n * limit]
+  uint32_t*        counts;         // [n]
+};
+int launch_scope_find(const ScopeFindArgs& a, hipStream_t stream);
+
 // Merge, per needle, two result lists that are each in result order (base image and delta image
 // hold disjoint references) into the first `limit` rows of `out`.
 int launch_merge_rows(const trigram_match_t* a_rows, const uint32_t* a_counts, const trigram_match_t* b_rows,

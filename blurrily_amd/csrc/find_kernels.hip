@@ -176,9 +176,10 @@ size_t find_lds_bytes(size_t counter_bytes, uint32_t pool_cap) {
     }                                                                                 \
   } while (0)
 
-// by reference (blurrily_storage_get / _find_references): no counted build of these
+// by reference (blurrily_storage_get / _find_references) and scoped find: no counted build of these
 #ifndef BLURRILY_COUNTED
 #include "kernels/refs.inc"
+#include "kernels/scope.inc"
 #endif
 
 int launch_tokenise(const TokeniseArgs& t, hipStream_t stream) {

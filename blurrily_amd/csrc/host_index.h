@@ -84,6 +84,9 @@ class HostIndex {
   int  save(const char* path);                 // 0 / -1+errno
   static HostIndex* load(const char* path);    // nullptr+errno on failure
 
+  // Whether the index holds `ref` now (the reference set storage.c:404-407 keeps for put's duplicate check).
+  bool holds(uint32_t ref) { ensure_refset(); return refs_.test(ref); }
+
   uint32_t total_refs() const     { return total_refs_; }
   uint32_t total_trigrams() const { return total_trigrams_; }
 

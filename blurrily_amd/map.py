@@ -275,6 +275,69 @@ class RawMap:
         rows, counts, _ = RawMap.find_batch_by_reference(self, [_u32(reference, "reference")], limit & 0xFFFF)
         return rows[0, :counts[0]].tolist()
 
+    # -- scoped find (no reference counterpart: the reference keeps one map per scope, map_group.rb) -----------
+    def scope(self, references):
+        """A ``Scope`` of these references (a fixed set; duplicates count once, references the map does not hold are
+        ignored).  Nothing reaches the GPU until its first scoped find."""
+        self._check_open()
+        refs = self._refs(references if isinstance(references, np.ndarray) else list(references))
+        h = C.c_void_p()
+        if self._lib.blurrily_scope_new(self._h, refs.ctypes.data if len(refs) else None, len(refs), C.byref(h)) < 0:
+            _raise_errno()
+        return Scope(self, h)
+
+    def _scope_of(self, scope):
+        """(Scope, whether it is one-shot) -- a plain iterable of references is made into a scope for one call."""
+        if isinstance(scope, Scope):
+            if scope._map is not self:
+                raise ValueError("the scope belongs to another map")
+            scope._check_open()
+            return scope, False
+        return self.scope(scope), True
+
+    def find_batch_in(self, scope, packed, offsets, limit):
+        """``find_batch_packed`` among the scope's members only.  Returns (rows[n, limit, 3] uint32, counts[n] uint32)."""
+        self._check_open()
+        sc, once = self._scope_of(scope)
+        try:
+            n = len(offsets) - 1
+            limit = int(limit) & 0xFFFF
+            rows = np.zeros((n, max(limit, 1), 3), dtype=np.uint32)
+            counts = np.zeros(n, dtype=np.uint32)
+            buf = np.frombuffer(packed, dtype=np.uint8) if not isinstance(packed, np.ndarray) else packed
+            offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+            res = self._lib.blurrily_storage_find_batch_in(
+                self._h, sc._h, buf.ctypes.data if buf.size else None, offsets.ctypes.data, n, limit,
+                rows.ctypes.data, counts.ctypes.data)
+            if res < 0:
+                _raise_errno()
+            return rows[:, :limit, :], counts
+        finally:
+            if once:
+                sc.close()
+
+    def find_in(self, scope, needle, limit):
+        """``find`` among the scope's members only (rows ``[ref, matches, weight]``); `limit` as find's."""
+        self._check_open()
+        limit = int(limit)
+        if not -(1 << 31) <= limit <= _U32_MAX:
+            raise OverflowError("limit out of range")
+        if limit > 0x7FFFFFFF:
+            limit -= 1 << 32
+        if limit <= 0:
+            limit = LIMIT_DEFAULT
+        c_limit = limit & 0xFFFF
+        sc, once = self._scope_of(scope)
+        try:
+            rows = (_native.TrigramMatch * max(c_limit, 1))()
+            res = self._lib.blurrily_storage_find_in(self._h, sc._h, _as_bytes(needle), c_limit, rows)
+            if res < 0:
+                _raise_errno()
+            return [[rows[k].reference, rows[k].matches, rows[k].weight] for k in range(res)]
+        finally:
+            if once:
+                sc.close()
+
     def sync_device(self):
         self._check_open()
         if self._lib.blurrily_storage_sync_device(self._h) < 0:
@@ -352,6 +415,52 @@ class RawMap:
     def handle(self):
         self._check_open()
         return self._h
+
+
+class Scope:
+    """A fixed set of references of one map (``RawMap.scope``): finds with ``find_in`` / ``find_batch_in`` return rows
+    of its members only.  Membership is read at each find: deleted members are not found, members put later are."""
+
+    ClosedError = ClosedError
+
+    def __init__(self, owner, handle):
+        self._lib = owner._lib
+        self._map = owner
+        self._h = handle
+        self._closed = False
+
+    def _check_open(self):
+        if self._closed:
+            raise ClosedError("Scope was closed")
+        self._map._check_open()
+
+    def members(self):
+        """How many of the scope's references the map holds now."""
+        self._check_open()
+        held = C.c_uint32()
+        if self._lib.blurrily_scope_members(self._h, C.byref(held)) < 0:
+            _raise_errno()
+        return held.value
+
+    def close(self):
+        if self._closed:
+            return None
+        self._closed = True
+        if self._lib.blurrily_scope_close(C.byref(self._h)) < 0:    # (it never touches the map)
+            _raise_errno()
+        return None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        if not getattr(self, "_closed", True):
+            self._lib.blurrily_scope_close(C.byref(self._h))
+            self._closed = True
 
 
 def set_process_option(key, value):
@@ -438,6 +547,19 @@ class Map(RawMap):
             limit = LIMIT_DEFAULT
         rows, counts, _ = super().find_batch_by_reference(references, limit)
         return [rows[i, :counts[i]].tolist() for i in range(len(counts))]
+
+    def find_in(self, scope, needle, limit=LIMIT_DEFAULT):
+        """``find`` among the references of `scope` (a ``Scope`` or an iterable of references) only."""
+        return super().find_in(scope, normalize_string(needle), limit)
+
+    def find_batch_in(self, scope, needles, limit=LIMIT_DEFAULT):
+        """``[self.find_in(scope, s, limit) for s in needles]`` in one GPU batch."""
+        limit = int(limit)
+        if limit <= 0:
+            limit = LIMIT_DEFAULT
+        packed, offsets = _pack([_as_bytes(normalize_string(s)) for s in needles])
+        rows, counts = super().find_batch_in(scope, packed, offsets, limit)
+        return [rows[i, :counts[i]].tolist() for i in range(len(needles))]
 
     def find_batch(self, needles, limit=LIMIT_DEFAULT):
         """``[self.find(s, limit) for s in needles]`` in one GPU batch."""

@@ -220,6 +220,42 @@ int blurrily_storage_find_references_device(trigram_map haystack, const uint32_t
                                             uint16_t limit, trigram_match d_results, uint32_t* d_counts,
                                             uint32_t* d_nb_trigrams, void* stream);
 
+/* Scoped find.  A scope is a set of references, fixed when it is made; a scoped find of needle s at `limit`
+ * returns exactly what blurrily_storage_find(s) at an unbounded limit would, with every row whose reference is
+ * not in the scope removed, truncated to `limit` (the same order and rows).  Membership is read against the map
+ * as it is at each find: a deleted member is not found, a member put after the scope was made is, a member
+ * deleted and put again is found with its new string's trigrams; references the map never held are ignored,
+ * duplicates count once.  A scope belongs to the map it was made from (EINVAL with any other).  Making a scope
+ * and counting its members need no GPU; a scoped find without a usable GPU returns -1 with errno ENODEV.  With
+ * "devices" > 1 the primary device alone serves a scoped find.  0, or -1 with errno. */
+typedef struct blurrily_scope_t* blurrily_scope;
+
+/* A scope of the n references (host memory; sorted and de-duplicated, nothing reaches the device yet). */
+int blurrily_scope_new(trigram_map haystack, const uint32_t* references, size_t n, blurrily_scope* scope);
+
+/* Frees the scope and NULLs *scope (a NULL *scope is a no-op).  Close scopes before their map. */
+int blurrily_scope_close(blurrily_scope* scope);
+
+/* *held = the scope's members the map holds now (host side, no GPU). */
+int blurrily_scope_members(blurrily_scope scope, uint32_t* held);
+
+/* blurrily_storage_find within the scope: the number of rows, or -1 with errno. */
+int blurrily_storage_find_in(trigram_map haystack, blurrily_scope scope, const char* needle, uint16_t limit,
+                             trigram_match results);
+
+/* blurrily_storage_find_batch within the scope. */
+int blurrily_storage_find_batch_in(trigram_map haystack, blurrily_scope scope, const char* packed,
+                                   const uint64_t* offsets, size_t n, uint16_t limit, trigram_match results,
+                                   uint32_t* counts);
+
+/* blurrily_storage_find_batch_device within the scope, under the same rules (device pointers on the map's GPU,
+ * enqueued on `stream`); the first scoped find after the map changed prepares the scope's device state
+ * (synchronous copies). */
+int blurrily_storage_find_batch_in_device(trigram_map haystack, blurrily_scope scope, const char* d_packed,
+                                          size_t packed_bytes, const uint64_t* d_offsets, size_t n,
+                                          uint16_t limit, trigram_match d_results, uint32_t* d_counts,
+                                          void* stream);
+
 /* Tokeniser (ext/blurrily/tokeniser.h:34, tokeniser.c:59-119): `output` needs
  * strlen(input)+1 slots; returns the number of distinct codes, ascending. */
 int blurrily_tokeniser_parse_string(const char* input, uint16_t* output);

@@ -15,6 +15,7 @@
  *   RawMap#set_option(key, value) / #get_option(key)      tunables, "devices" among them (multi-GPU)
  *   RawMap#find_by_reference(ref, limit)    -> [[ref, matches, weight], ...]   find with a STORED reference's trigrams
  *   RawMap#get(ref)                         -> [weight, [codes ascending]], or nil when the map does not hold ref
+ *   RawMap#find_among(needle, limit, refs)  -> [[ref, matches, weight], ...]   find among the given references only
  *
  * Each element of a batch is defined as exactly one RawMap#find (map_ext.c:131-162): limit <= 0 means
  * LIMIT_DEFAULT, rows are [reference, matches, weight].
@@ -124,7 +125,8 @@ typedef struct {
   uint32_t*       non_ascii;      /* find_batch_raw only */
   uint32_t*       refs;           /* put_many only */
   uint32_t*       weights;
-  int             by_ref;         /* find_by_reference (1) / get (2): refs[0] is the reference */
+  int             by_ref;         /* find_by_reference (1) / get (2): refs[0] is the reference; find_among (3): refs[0, n_refs) */
+  size_t          n_refs;
   uint16_t*       codes;          /* get only: room for every code */
   uint32_t        got_weight;
   int             marked_busy;
@@ -181,6 +183,15 @@ static void* batch_call_run(void* p)
     c->res = blurrily_storage_find_references(c->map, c->refs, 1, c->limit, c->rows, c->counts, NULL);
   else if (c->by_ref == 2)
     c->res = blurrily_storage_get(c->map, c->refs[0], &c->got_weight, 28 * 28 * 28, c->codes);
+  else if (c->by_ref == 3) {                                       /* a scope for this one find */
+    blurrily_scope scope = NULL;
+    c->res = blurrily_scope_new(c->map, c->refs, c->n_refs, &scope);
+    if (c->res == 0)
+      c->res = blurrily_storage_find_batch_in(c->map, scope, c->in.packed, c->in.offsets, 1, c->limit, c->rows, c->counts);
+    c->err = errno;
+    if (scope) blurrily_scope_close(&scope);
+    return NULL;
+  }
   else c->res = c->non_ascii
     ? blurrily_storage_find_batch_raw(c->map, c->in.packed, c->in.offsets, c->in.n, c->limit, c->rows, c->counts, c->non_ascii)
     : blurrily_storage_find_batch(c->map, c->in.packed, c->in.offsets, c->in.n, c->limit, c->rows, c->counts);
@@ -302,6 +313,38 @@ static VALUE blurrily_get(VALUE self, VALUE rb_ref)
   return by_ref_common(self, rb_ref, Qnil, 2);
 }
 
+/* ---- find_among: find among the given references only (a one-shot scope; without the GVL, as find_batch) ---- */
+
+static VALUE find_among_body(VALUE p)
+{
+  batch_call* c = (batch_call*)p;
+  long        i, n;
+  c->map   = map_of(c->self);                                      /* raises when closed or busy */
+  c->limit = limit_of(c->rb_limit);
+  pack_needles(c);                                                 /* rb_needles: [needle] */
+  Check_Type(c->rb_refs, T_ARRAY);
+  n = RARRAY_LEN(c->rb_refs);
+  c->refs = ALLOC_N(uint32_t, n + 1);
+  for (i = 0; i < n; ++i) c->refs[i] = NUM2UINT(rb_ary_entry(c->rb_refs, i));
+  c->n_refs = (size_t)n;
+  c->rows   = ALLOC_N(trigram_match_t, (size_t)c->limit + 1);
+  c->counts = ALLOC_N(uint32_t, 1);
+  rb_ivar_set(c->self, rb_intern("@blurrily_busy"), Qtrue);
+  c->marked_busy = 1;
+  rb_thread_call_without_gvl(batch_call_run, c, RUBY_UBF_IO, NULL);
+  if (c->res < 0) { errno = c->err; rb_sys_fail("blurrily_storage_find_batch_in"); }
+  return rb_ary_entry(rows_to_ruby(c), 0);
+}
+
+static VALUE blurrily_find_among(VALUE self, VALUE rb_needle, VALUE rb_limit, VALUE rb_refs)
+{
+  batch_call c;
+  memset(&c, 0, sizeof c);
+  c.self = self; c.rb_needles = rb_ary_new3(1, rb_needle); c.rb_limit = rb_limit; c.rb_refs = rb_refs; c.by_ref = 3;
+  c.strings = Qnil; c.rb_weights = Qnil;
+  return rb_ensure(find_among_body, (VALUE)&c, batch_call_cleanup, (VALUE)&c);
+}
+
 /* ---- put_many (holds the GVL: host work, as the gem's put) -------------------------------------- */
 
 static VALUE put_many_body(VALUE p)
@@ -378,4 +421,5 @@ void Init_map_ext(void)
   rb_define_method(cRawMap, "get_option",     blurrily_get_option,     1);
   rb_define_method(cRawMap, "find_by_reference", blurrily_find_by_reference, 2);
   rb_define_method(cRawMap, "get",            blurrily_get,            1);
+  rb_define_method(cRawMap, "find_among",     blurrily_find_among,     3);
 }
