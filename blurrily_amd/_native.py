@@ -128,6 +128,14 @@ def lib():
                                                      C.c_void_p, C.c_void_p]),
         "blurrily_storage_find_batch_in_device": (C.c_int, [vp, vp, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
                                                             C.c_uint16, C.c_void_p, C.c_void_p, C.c_void_p]),
+        "blurrily_storage_find_batch_each_in": (C.c_int, [vp, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                                          C.c_void_p, C.c_size_t, C.c_uint16, C.c_void_p, C.c_void_p]),
+        "blurrily_storage_find_batch_each_in_device": (C.c_int, [vp, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                                                 C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint16,
+                                                                 C.c_void_p, C.c_void_p, C.c_void_p]),
+        "blurrily_storage_find_references_each_in": (C.c_int, [vp, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                                               C.c_size_t, C.c_uint16, C.c_void_p, C.c_void_p,
+                                                               C.c_void_p]),
     }
     for name, (res, args) in sig.items():
         try:
@@ -160,4 +168,9 @@ EXPORTED_SYMBOLS = (
     # scoped find: a fixed set of references, and finds among them only
     "blurrily_scope_new", "blurrily_scope_close", "blurrily_scope_members", "blurrily_storage_find_in",
     "blurrily_storage_find_batch_in", "blurrily_storage_find_batch_in_device",
+) + (
+    # a scope per needle: batched scoped find and find-by-reference, each needle among its own scope
+    "blurrily_storage_find_batch_each_in", "blurrily_storage_find_batch_each_in_device",
+    "blurrily_storage_find_references_each_in",
 )
+NO_SCOPE = 0xFFFFFFFF                                  # BLURRILY_NO_SCOPE: a needle of such a batch with no scope

@@ -260,6 +260,39 @@ struct ScopeFindArgs {
   uint32_t*        counts;         // [n]
 };
 int launch_scope_find(const ScopeFindArgs& a, hipStream_t stream);
+// A batch whose needles each name a scope of their own: every needle the direct strategy serves,
+// whatever its scope, in one launch.  Workgroup b serves needle order[b].x with scope order[b].y's direct form.
+struct ScopeDirect {               // one scope's direct form, as ScopeFindArgs has it
+  const uint32_t* m_off;
+  const uint16_t* m_codes;
+  const uint32_t* m_ref;
+  const uint32_t* m_weight;
+  uint32_t        n_members;
+  uint32_t        pad;
+};
+struct ScopeEachArgs {
+  const char*        packed;       // the needles as strings (codes == nullptr) ...
+  const uint64_t*    offsets;
+  const uint16_t*    codes;        // ... or as references (RefNeedles: needle q's codes at codes + qoff[q] + q)
+  const uint64_t*    qoff;
+  const uint32_t*    ntri;
+  const uint2*       order;        // [n] {needle, scope}: the workgroups, largest scopes first
+  uint32_t           n;
+  const ScopeDirect* scopes;
+  uint32_t           max_members;  // the largest scope's members: a byte each of dynamic LDS
+  uint32_t           limit;        // 1 .. kScopeMaxKeep
+  trigram_match_t*   results;      // needle q's rows at results + q * limit
+  uint32_t*          counts;
+};
+int launch_scope_each(const ScopeEachArgs& a, hipStream_t stream);
+// The groups the sweeps serve: their needles compacted (strings: needle idx[k]'s bytes to out + out_off[k]; references:
+// the extracted descriptors, the codes left in place), and their rows and counts put back at the caller's positions.
+int launch_scope_gather_strings(const char* packed, const uint64_t* offsets, const uint32_t* idx, const uint64_t* out_off,
+                                uint32_t n, char* out, hipStream_t stream);
+int launch_scope_gather_refs(const RefNeedles& r, const uint32_t* idx, uint32_t n, uint64_t* qoff, uint32_t* ntri,
+                             uint32_t* weight, hipStream_t stream);
+int launch_scope_scatter(const trigram_match_t* rows, const uint32_t* counts, const uint32_t* idx, uint32_t n,
+                         uint32_t limit, trigram_match_t* out_rows, uint32_t* out_counts, hipStream_t stream);
 
 // Merge, per needle, two result lists that are each in result order (base image and delta image
 // hold disjoint references) into the first `limit` rows of `out`.

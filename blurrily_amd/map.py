@@ -284,7 +284,7 @@ class RawMap:
         h = C.c_void_p()
         if self._lib.blurrily_scope_new(self._h, refs.ctypes.data if len(refs) else None, len(refs), C.byref(h)) < 0:
             _raise_errno()
-        return Scope(self, h)
+        return Scope(self, h, np.unique(refs))
 
     def _scope_of(self, scope):
         """(Scope, whether it is one-shot) -- a plain iterable of references is made into a scope for one call."""
@@ -315,6 +315,97 @@ class RawMap:
         finally:
             if once:
                 sc.close()
+
+    # -- a scope per needle -----------------------------------------------------------------
+    def _scopes_of(self, scopes):
+        """(Scopes, the one-shot ones among them to close after the call) -- see ``_scope_of``."""
+        got, once = [], []
+        try:
+            for s in scopes:
+                sc, o = self._scope_of(s)
+                got.append(sc)
+                if o:
+                    once.append(sc)
+        except BaseException:
+            for sc in once:
+                sc.close()
+            raise
+        return got, once
+
+    @staticmethod
+    def _which(which, n):
+        """uint32[n]: a scope index per needle, None -> NO_SCOPE (the whole map)."""
+        if len(which) != n:
+            raise ValueError(f"which has {len(which)} elements for {n} needles")
+        if isinstance(which, np.ndarray) and which.dtype == np.uint32:
+            return np.ascontiguousarray(which)
+        return np.array([_native.NO_SCOPE if w is None else _u32(w, "scope index") for w in which], dtype=np.uint32)
+
+    def find_batch_each_in(self, scopes, which, packed, offsets, limit):
+        """``find_batch_packed`` with a scope per needle: needle i among ``scopes[which[i]]`` only, or the whole map when
+        ``which[i]`` is None.  Returns (rows[n, limit, 3] uint32, counts[n] uint32)."""
+        self._check_open()
+        n = len(offsets) - 1
+        which = self._which(which, n)
+        scs, once = self._scopes_of(scopes)
+        try:
+            limit = int(limit) & 0xFFFF
+            rows = np.zeros((n, max(limit, 1), 3), dtype=np.uint32)
+            counts = np.zeros(n, dtype=np.uint32)
+            buf = np.frombuffer(packed, dtype=np.uint8) if not isinstance(packed, np.ndarray) else packed
+            offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+            hs = (C.c_void_p * max(len(scs), 1))(*[sc._h.value for sc in scs])
+            res = self._lib.blurrily_storage_find_batch_each_in(
+                self._h, hs if scs else None, len(scs), which.ctypes.data if n else None,
+                buf.ctypes.data if buf.size else None, offsets.ctypes.data, n, limit, rows.ctypes.data,
+                counts.ctypes.data)
+            if res < 0:
+                _raise_errno()
+            return rows[:, :limit, :], counts
+        finally:
+            for sc in once:
+                sc.close()
+
+    def find_batch_by_reference_each_in(self, scopes, which, references, limit):
+        """``find_batch_by_reference`` with a scope per reference, as ``find_batch_each_in``.
+        Returns (rows[n, limit, 3] uint32, counts[n] uint32, nb_trigrams[n] uint32)."""
+        self._check_open()
+        refs = self._refs(references)
+        n = len(refs)
+        which = self._which(which, n)
+        scs, once = self._scopes_of(scopes)
+        try:
+            limit = int(limit) & 0xFFFF
+            rows = np.zeros((n, max(limit, 1), 3), dtype=np.uint32)
+            counts = np.zeros(n, dtype=np.uint32)
+            ntri = np.zeros(n, dtype=np.uint32)
+            hs = (C.c_void_p * max(len(scs), 1))(*[sc._h.value for sc in scs])
+            res = self._lib.blurrily_storage_find_references_each_in(
+                self._h, hs if scs else None, len(scs), which.ctypes.data if n else None,
+                refs.ctypes.data if n else None, n, limit, rows.ctypes.data, counts.ctypes.data, ntri.ctypes.data)
+            if res < 0:
+                _raise_errno()
+            return rows[:, :limit, :], counts, ntri
+        finally:
+            for sc in once:
+                sc.close()
+
+    def join_within(self, scopes, limit):
+        """The blocked self-join: every member of every scope searched among its own scope (``find_by_reference``
+        restricted to it), in one GPU batch.  Returns (references[k] uint32, which[k] uint32: the scope of each,
+        rows: k lists of [ref, matches, weight]) over the members the map holds, scope after scope."""
+        self._check_open()
+        scs, once = self._scopes_of(scopes)
+        try:
+            parts = [sc._refs if sc._refs is not None else np.zeros(0, np.uint32) for sc in scs]
+            refs = np.concatenate(parts).astype(np.uint32) if parts else np.zeros(0, np.uint32)
+            which = np.repeat(np.arange(len(parts), dtype=np.uint32), [len(p) for p in parts])
+            rows, counts, ntri = self.find_batch_by_reference_each_in(scs, which, refs, limit)
+        finally:
+            for sc in once:
+                sc.close()
+        held = np.nonzero(ntri)[0]
+        return refs[held], which[held], [rows[i, :counts[i]].tolist() for i in held.tolist()]
 
     def find_in(self, scope, needle, limit):
         """``find`` among the scope's members only (rows ``[ref, matches, weight]``); `limit` as find's."""
@@ -423,10 +514,11 @@ class Scope:
 
     ClosedError = ClosedError
 
-    def __init__(self, owner, handle):
+    def __init__(self, owner, handle, refs=None):
         self._lib = owner._lib
         self._map = owner
         self._h = handle
+        self._refs = refs                               # its references, sorted and distinct
         self._closed = False
 
     def _check_open(self):
@@ -560,6 +652,19 @@ class Map(RawMap):
         packed, offsets = _pack([_as_bytes(normalize_string(s)) for s in needles])
         rows, counts = super().find_batch_in(scope, packed, offsets, limit)
         return [rows[i, :counts[i]].tolist() for i in range(len(needles))]
+
+    def find_batch_each_in(self, scopes, which, needles, limit=LIMIT_DEFAULT):
+        """``[self.find_in(scopes[w], s, limit) if w is not None else self.find(s, limit) for s, w in zip(needles,
+        which)]`` in one GPU batch."""
+        limit = int(limit)
+        if limit <= 0:
+            limit = LIMIT_DEFAULT
+        packed, offsets = _pack([_as_bytes(normalize_string(s)) for s in needles])
+        rows, counts = super().find_batch_each_in(scopes, which, packed, offsets, limit)
+        return [rows[i, :counts[i]].tolist() for i in range(len(needles))]
+
+    def join_within(self, scopes, limit=LIMIT_DEFAULT):
+        return super().join_within(scopes, limit if int(limit) > 0 else LIMIT_DEFAULT)
 
     def find_batch(self, needles, limit=LIMIT_DEFAULT):
         """``[self.find(s, limit) for s in needles]`` in one GPU batch."""

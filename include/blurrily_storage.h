@@ -256,6 +256,36 @@ int blurrily_storage_find_batch_in_device(trigram_map haystack, blurrily_scope s
                                           uint16_t limit, trigram_match d_results, uint32_t* d_counts,
                                           void* stream);
 
+/* A scope per needle.  Needle i of a batch is a scoped find in scopes[which[i]] (the array may repeat a handle), or
+ * a plain blurrily_storage_find when which[i] == BLURRILY_NO_SCOPE: element i is exactly what
+ * blurrily_storage_find_in(haystack, scopes[which[i]], needle_i, limit) -- or blurrily_storage_find -- would return,
+ * under the same membership rules.  EINVAL, before anything needs a GPU: which[i] >= n_scopes (other than the
+ * sentinel), a NULL handle or a scope of another map, n_scopes > 0 with scopes NULL.  Valid arguments without a
+ * usable GPU: ENODEV.  With "devices" > 1 the primary device alone serves the call.  Every scope a call names that
+ * the map has changed under is prepared again, all of them together.  0, or -1 with errno. */
+#define BLURRILY_NO_SCOPE 0xFFFFFFFFu
+
+/* blurrily_storage_find_batch with a scope per needle: rows of needle i at results + i * limit, counts[i]. */
+int blurrily_storage_find_batch_each_in(trigram_map haystack, const blurrily_scope* scopes, size_t n_scopes,
+                                        const uint32_t* which, const char* packed, const uint64_t* offsets, size_t n,
+                                        uint16_t limit, trigram_match results, uint32_t* counts);
+
+/* The same with device pointers on the map's GPU, enqueued on `stream`.  d_which lives in device memory: the call
+ * copies it back and waits for that copy to group the needles (so a bad index is EINVAL only then), and when a scope
+ * the mask strategy serves, or BLURRILY_NO_SCOPE, is named it copies d_offsets back the same way.  Preparing a scope
+ * takes synchronous copies, as for blurrily_storage_find_batch_in_device. */
+int blurrily_storage_find_batch_each_in_device(trigram_map haystack, const blurrily_scope* scopes, size_t n_scopes,
+                                               const uint32_t* d_which, const char* d_packed, size_t packed_bytes,
+                                               const uint64_t* d_offsets, size_t n, uint16_t limit,
+                                               trigram_match d_results, uint32_t* d_counts, void* stream);
+
+/* blurrily_storage_find_references with a scope per reference: element i is blurrily_storage_find_references for
+ * references[i] restricted as above (an absent reference: 0 rows); nb_trigrams (may be NULL) as there. */
+int blurrily_storage_find_references_each_in(trigram_map haystack, const blurrily_scope* scopes, size_t n_scopes,
+                                             const uint32_t* which, const uint32_t* references, size_t n,
+                                             uint16_t limit, trigram_match results, uint32_t* counts,
+                                             uint32_t* nb_trigrams);
+
 /* Tokeniser (ext/blurrily/tokeniser.h:34, tokeniser.c:59-119): `output` needs
  * strlen(input)+1 slots; returns the number of distinct codes, ascending. */
 int blurrily_tokeniser_parse_string(const char* input, uint16_t* output);

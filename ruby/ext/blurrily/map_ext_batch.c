@@ -16,6 +16,8 @@
  *   RawMap#find_by_reference(ref, limit)    -> [[ref, matches, weight], ...]   find with a STORED reference's trigrams
  *   RawMap#get(ref)                         -> [weight, [codes ascending]], or nil when the map does not hold ref
  *   RawMap#find_among(needle, limit, refs)  -> [[ref, matches, weight], ...]   find among the given references only
+ *   RawMap#find_batch_among(needles, limit, ref_lists, which) -> one list per needle: needle i among
+ *                                           ref_lists[which[i]] only, or the whole map when which[i] is nil
  *
  * Each element of a batch is defined as exactly one RawMap#find (map_ext.c:131-162): limit <= 0 means
  * LIMIT_DEFAULT, rows are [reference, matches, weight].
@@ -125,8 +127,13 @@ typedef struct {
   uint32_t*       non_ascii;      /* find_batch_raw only */
   uint32_t*       refs;           /* put_many only */
   uint32_t*       weights;
-  int             by_ref;         /* find_by_reference (1) / get (2): refs[0] is the reference; find_among (3): refs[0, n_refs) */
+  int             by_ref;         /* find_by_reference (1) / get (2): refs[0] is the reference; find_among (3): refs[0, n_refs);
+                                     find_batch_among (4): list j is refs[list_off[j], list_off[j + 1]) */
   size_t          n_refs;
+  size_t*         list_off;       /* find_batch_among only: [n_lists + 1] */
+  size_t          n_lists;
+  uint32_t*       which;          /* [in.n] a list per needle, BLURRILY_NO_SCOPE for none */
+  blurrily_scope* scopes;         /* [n_lists]: made and closed by the call, without the GVL */
   uint16_t*       codes;          /* get only: room for every code */
   uint32_t        got_weight;
   int             marked_busy;
@@ -171,6 +178,9 @@ static VALUE batch_call_cleanup(VALUE p)
   if (c->refs)       xfree(c->refs);
   if (c->weights)    xfree(c->weights);
   if (c->codes)      xfree(c->codes);
+  if (c->list_off)   xfree(c->list_off);
+  if (c->which)      xfree(c->which);
+  if (c->scopes)     xfree(c->scopes);
   return Qnil;
 }
 
@@ -190,6 +200,19 @@ static void* batch_call_run(void* p)
       c->res = blurrily_storage_find_batch_in(c->map, scope, c->in.packed, c->in.offsets, 1, c->limit, c->rows, c->counts);
     c->err = errno;
     if (scope) blurrily_scope_close(&scope);
+    return NULL;
+  }
+  else if (c->by_ref == 4) {                                       /* a scope per list, for this one batch */
+    size_t j;
+    c->res = 0;
+    for (j = 0; j < c->n_lists && c->res == 0; ++j)
+      c->res = blurrily_scope_new(c->map, c->refs + c->list_off[j], c->list_off[j + 1] - c->list_off[j], &c->scopes[j]);
+    if (c->res == 0)
+      c->res = blurrily_storage_find_batch_each_in(c->map, c->scopes, c->n_lists, c->which, c->in.packed, c->in.offsets,
+                                                   c->in.n, c->limit, c->rows, c->counts);
+    c->err = errno;
+    for (j = 0; j < c->n_lists; ++j)
+      if (c->scopes[j]) blurrily_scope_close(&c->scopes[j]);
     return NULL;
   }
   else c->res = c->non_ascii
@@ -336,6 +359,59 @@ static VALUE find_among_body(VALUE p)
   return rb_ary_entry(rows_to_ruby(c), 0);
 }
 
+/* ---- find_batch_among: a batch, each needle among its own list of references (one-shot scopes) ---- */
+
+static VALUE find_batch_among_body(VALUE p)
+{
+  batch_call* c = (batch_call*)p;
+  long        i, j, n_lists, n_refs = 0;
+  c->map   = map_of(c->self);                                      /* raises when closed or busy */
+  c->limit = limit_of(c->rb_limit);
+  pack_needles(c);
+  Check_Type(c->rb_refs, T_ARRAY);
+  Check_Type(c->rb_weights, T_ARRAY);                              /* (the `which` list) */
+  if ((size_t)RARRAY_LEN(c->rb_weights) != c->in.n) rb_raise(rb_eArgError, "which must have one element per needle");
+  n_lists = RARRAY_LEN(c->rb_refs);
+  for (j = 0; j < n_lists; ++j) {
+    VALUE list = rb_ary_entry(c->rb_refs, j);
+    Check_Type(list, T_ARRAY);
+    n_refs += RARRAY_LEN(list);
+  }
+  c->n_lists  = (size_t)n_lists;
+  c->list_off = ALLOC_N(size_t, n_lists + 1);
+  c->refs     = ALLOC_N(uint32_t, n_refs + 1);
+  c->list_off[0] = 0;
+  for (j = 0; j < n_lists; ++j) {
+    VALUE list = rb_ary_entry(c->rb_refs, j);
+    long  k = RARRAY_LEN(list);
+    for (i = 0; i < k; ++i) c->refs[c->list_off[j] + (size_t)i] = NUM2UINT(rb_ary_entry(list, i));
+    c->list_off[j + 1] = c->list_off[j] + (size_t)k;
+  }
+  c->which = ALLOC_N(uint32_t, c->in.n + 1);
+  for (i = 0; i < (long)c->in.n; ++i) {
+    VALUE w = rb_ary_entry(c->rb_weights, i);
+    c->which[i] = NIL_P(w) ? BLURRILY_NO_SCOPE : NUM2UINT(w);
+  }
+  c->scopes = ALLOC_N(blurrily_scope, n_lists + 1);
+  memset(c->scopes, 0, sizeof(blurrily_scope) * (size_t)(n_lists + 1));
+  c->rows   = ALLOC_N(trigram_match_t, c->in.n * c->limit + 1);
+  c->counts = ALLOC_N(uint32_t, c->in.n + 1);
+  rb_ivar_set(c->self, rb_intern("@blurrily_busy"), Qtrue);
+  c->marked_busy = 1;
+  rb_thread_call_without_gvl(batch_call_run, c, RUBY_UBF_IO, NULL);
+  if (c->res < 0) { errno = c->err; rb_sys_fail("blurrily_storage_find_batch_each_in"); }
+  return rows_to_ruby(c);
+}
+
+static VALUE blurrily_find_batch_among(VALUE self, VALUE rb_needles, VALUE rb_limit, VALUE rb_ref_lists, VALUE rb_which)
+{
+  batch_call c;
+  memset(&c, 0, sizeof c);
+  c.self = self; c.rb_needles = rb_needles; c.rb_limit = rb_limit; c.rb_refs = rb_ref_lists; c.rb_weights = rb_which;
+  c.by_ref = 4; c.strings = Qnil;
+  return rb_ensure(find_batch_among_body, (VALUE)&c, batch_call_cleanup, (VALUE)&c);
+}
+
 static VALUE blurrily_find_among(VALUE self, VALUE rb_needle, VALUE rb_limit, VALUE rb_refs)
 {
   batch_call c;
@@ -422,4 +498,5 @@ void Init_map_ext(void)
   rb_define_method(cRawMap, "find_by_reference", blurrily_find_by_reference, 2);
   rb_define_method(cRawMap, "get",            blurrily_get,            1);
   rb_define_method(cRawMap, "find_among",     blurrily_find_among,     3);
+  rb_define_method(cRawMap, "find_batch_among", blurrily_find_batch_among, 4);
 }
