@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- batched trigram find on MI355X (the metric of BASELINE.json).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
 
 A *step* is one pass of the hot path (device tokeniser + find kernels) over one batch of
 synthetic needles that is already resident in HBM.  At N=1 the workload is
@@ -15,7 +15,14 @@ block; the region ends only when every gather has arrived.
 Rank 0 prints ONE SHORT JSON line (compact_line: numbers and short tokens only, at most 6 000 bytes -- what the driver
 parses; tests/test_bench_line.py) and writes the whole record -- every field described below, notes, sources, counters,
 per-sweep measurements -- to bench_detail.json beside this script (`--detail PATH`; the path goes to stderr and into the
-line's `detail`).  `value` is whole-job needles/s.  The record carries, and the line summarises,
+line's `detail`).  `value` is whole-job needles/s.
+
+A plain run does only what `value` needs: it builds the haystack, measures the sweep choice ahead of time, warms up,
+times the steps, writes --dump-outputs and prints the line -- beside `value` and `ms_per_step` only what the timed steps
+themselves yield (kernel_ms, entries per needle, and for N > 1 the collective's stamp and figures).  Everything below
+takes work of its own -- an extra launch, other haystacks, the reference on the CPU -- and runs with `--full` alone;
+--cpu-budget, --latency-probes, --no-cpu-baseline, --no-extra and --inject-failure shape that work.  With `--full` the
+record carries, and the line summarises,
 
   roofline       the position of the dominant kernel against the HBM roofline, from PHYSICAL
                  bytes measured IN THIS RUN: what the kernels requested of the memory system in one
@@ -64,7 +71,7 @@ peak / frac stay those of the HBM roof whatever `bound` says.
 `--scaling strong` (N > 1) splits configs[3]'s literal 8 M-needle batch over the ranks instead of giving
 each its own 1 M; `n_gpus` counts DISTINCT physical devices (`distinct_devices`, by UUID / PCI bus id).
 
-A leg that fails -- the CPU baseline, an extra config, a parity comparison -- is recorded in the line
+A leg of --full that fails -- the CPU baseline, an extra config, a parity comparison -- is recorded in the line
 AND makes the exit status 1: a line without its baseline is not a result.
 """
 import argparse
@@ -249,7 +256,8 @@ def compact_line(full, detail_path=None):
                                                    "limit", "index_replicated", "parallelism", "scale"))
     out.update(_pick(full, ("p50_query_us", "p99_query_us", "matched_entries_per_sec", "entries_per_query", "kernel_ms",
                             "host_buffer_queries_per_sec", "sweep_retunes", "retimed", "first_ms_per_step")))
-    out["roofline"] = compact_roofline(full.get("roofline"))
+    if "roofline" in full:
+        out["roofline"] = compact_roofline(full["roofline"])
     if "cpu_baseline" in full:
         out["cpu_baseline"] = compact_cpu_baseline(full["cpu_baseline"])
     if "extra_configs" in full:
@@ -519,9 +527,11 @@ def dump_outputs(directory, rows, counts, limit):
     log(f"outputs of the last timed step: {k} of {n_q} needles in {directory}")
 
 
-def run_workload(name, args, steps, warmup, rank, local_rank, world, dist, cpu_budget, latency_probes, dump_dir=None):
+def run_workload(name, args, steps, warmup, rank, local_rank, world, dist, cpu_budget, latency_probes, dump_dir=None,
+                 full=False):
     """Build the workload, time `steps` steps, derive the figures; with `dump_dir`, write what the last timed step
-    computed there (dump_outputs).  Returns (line dict or None on ranks > 0, parity_ok)."""
+    computed there (dump_outputs); with `full`, add the roofline (an extra, counted launch) and the parity checks
+    that go with it.  Returns (line dict or None on ranks > 0, parity_ok)."""
     import workloads as W
     from blurrily_amd import _native
     from blurrily_amd.sharding import ResultBlock, gather_blocks
@@ -679,90 +689,95 @@ def run_workload(name, args, steps, warmup, rank, local_rank, world, dist, cpu_b
         shards_verified = {"shard": r, "needles": int(n2), "equal": bool(same)}
         if not same:
             raise RuntimeError(f"rank 0's gathered rows of shard {r} differ from a direct find of the same needles")
-    # rows of the LAST TIMED launch, for the parity leg (every launch searches the same batch: both blocks hold them)
-    gpu_rows = block.rows.cpu().numpy().view(np.uint32)
-    gpu_counts = block.counts.cpu().numpy().view(np.uint32)
+    # rows of the LAST TIMED launch, for --dump-outputs and the parity legs (every launch searches the same batch: both
+    # blocks hold them)
+    gpu_rows = gpu_counts = None
+    if full or dump_dir is not None:
+        gpu_rows = block.rows.cpu().numpy().view(np.uint32)
+        gpu_counts = block.counts.cpu().numpy().view(np.uint32)
     if dump_dir is not None and rank == 0:
         dump_outputs(dump_dir, gpu_rows.reshape(n_q, limit, 3), gpu_counts, limit)
     nb = d_nb.cpu().numpy().astype(np.uint32).astype(np.int64)
-    sum_nb, sum_rows = int(nb.sum()), int(gpu_counts.astype(np.int64).sum())
-    algo_bytes = 8 * sum_nb + 8 * sum_T + 12 * sum_rows + 4 * n_q            # SURVEY.md 8(d), one launch
+    sum_nb = int(nb.sum())
     k_ms = float(np.mean(kernel_ms))
-    sweeps = {0: "latency mode / long needles only", 1: "needle-major", 2: "window-major",
-              3: "needle-major, dense slices left out of the count",
-              4: "small haystack: four waves and one window's counters per needle"}
-    sweep = sweeps[m.get_option("last_sweep")]                               # of the timed launches
-    timed_kernels = m.last_kernels()                                         # ... and the kernels they ran (blurrily_storage_last_kernels)
-    # one more launch, untimed, with the kernels' own request counters on: the physical bytes and the
-    # LDS-atomic lanes of exactly this batch -- by the SAME sweep (a measured choice is kept while counting)
-    m.set_stats(True)
-    find()
-    torch.cuda.synchronize()
-    st = m.find_stats()
-    m.set_stats(False)
-    counted_sweep = sweeps[m.get_option("last_sweep")]
-    # what the library's own measurement of this class of batch saw (its first batch ran every sweep it can take)
-    tuned = None
-    if m.get_option("tuned_class") >= 0:
-        tuned = {"class": m.get_option("tuned_class"), "needle_major_ms": m.get_option("tuned_nm_us") / 1e3,
-                 "window_major_ms": m.get_option("tuned_ws_us") / 1e3 or None,
-                 "slices_left_out_ms": m.get_option("tuned_leave_us") / 1e3 or None}
-    stats_rows_equal = bool(np.array_equal(gpu_counts, block.counts.cpu().numpy().view(np.uint32)))
-    out_bytes = 12 * sum_rows + 4 * n_q + 4 * n_q                              # rows + counts + nb_entries
-    needle_bytes = int(qo[-1]) + 8 * (n_q + 1) + 2 * (int(qo[-1]) + n_q)       # needles, offsets, code scratch (w+r)
-    req_bytes = (2 * st["posting_entries"] + 4 * st["table_words"] + 4 * st["probes"] + out_bytes + 2 * needle_bytes)
-    # (in-process over several devices: the counted launch ran the whole batch on ONE of them; kernel_ms is the slowest
-    # shard's search, so the per-device rates take a device's share of the bytes)
-    req_gbs = req_bytes / devices / (k_ms * 1e-3) / 1e9
-    lds_lanes = st["posting_entries"] / devices / (k_ms * 1e-3)
-    # Beside it: memory-side bytes per step from the rocprofv3 --pmc passes of this workload (a SEPARATE run of
-    # this command under the profiler, profiles/traffic_latest.json): the L2's fabric-side counters, i.e. HBM +
-    # Infinity Cache.  Only as good as the build it was taken at: stamped, and stale when the sources changed.
-    pmc = None
-    tpath = os.path.join(ROOT, "profiles", "traffic_latest.json")
-    if os.path.exists(tpath) and args.scale == 1.0:
-        try:
-            prof = json.load(open(tpath))
-            if prof.get(name):
-                at, now = prof.get("kernel_source_hash"), kernel_source_hash()
-                pmc = {"bytes_per_step": prof[name], "gbs": prof[name] / (k_ms * 1e-3) / 1e9,
-                       "frac": prof[name] / (k_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                       "profiled_at_commit": prof.get("commit"), "profiled_at_source_hash": at,
-                       "stale": at != now,
-                       "source": "profiles/traffic_latest.json: (2*FETCH_SIZE + WRITE_SIZE) KiB of this workload's find "
-                                 "kernels, rocprofv3 --pmc, separate run (tools/collect_profiles.sh); Infinity-Cache hits included"}
-                if pmc["stale"]:
-                    log(f"WARNING: profiles/traffic_latest.json was profiled at kernel sources {at}, this run is {now}: "
-                        f"the PMC traffic figure of '{name}' is STALE (re-run tools/collect_profiles.sh)")
-        except Exception as e:
-            pmc = {"error": str(e)}
+    if full:
+        sum_rows = int(gpu_counts.astype(np.int64).sum())
+        algo_bytes = 8 * sum_nb + 8 * sum_T + 12 * sum_rows + 4 * n_q            # SURVEY.md 8(d), one launch
+        sweeps = {0: "latency mode / long needles only", 1: "needle-major", 2: "window-major",
+                  3: "needle-major, dense slices left out of the count",
+                  4: "small haystack: four waves and one window's counters per needle"}
+        sweep = sweeps[m.get_option("last_sweep")]                               # of the timed launches
+        timed_kernels = m.last_kernels()                                         # ... and the kernels they ran (blurrily_storage_last_kernels)
+        # one more launch, untimed, with the kernels' own request counters on: the physical bytes and the
+        # LDS-atomic lanes of exactly this batch -- by the SAME sweep (a measured choice is kept while counting)
+        m.set_stats(True)
+        find()
+        torch.cuda.synchronize()
+        st = m.find_stats()
+        m.set_stats(False)
+        counted_sweep = sweeps[m.get_option("last_sweep")]
+        # what the library's own measurement of this class of batch saw (its first batch ran every sweep it can take)
+        tuned = None
+        if m.get_option("tuned_class") >= 0:
+            tuned = {"class": m.get_option("tuned_class"), "needle_major_ms": m.get_option("tuned_nm_us") / 1e3,
+                     "window_major_ms": m.get_option("tuned_ws_us") / 1e3 or None,
+                     "slices_left_out_ms": m.get_option("tuned_leave_us") / 1e3 or None}
+        stats_rows_equal = bool(np.array_equal(gpu_counts, block.counts.cpu().numpy().view(np.uint32)))
+        out_bytes = 12 * sum_rows + 4 * n_q + 4 * n_q                              # rows + counts + nb_entries
+        needle_bytes = int(qo[-1]) + 8 * (n_q + 1) + 2 * (int(qo[-1]) + n_q)       # needles, offsets, code scratch (w+r)
+        req_bytes = (2 * st["posting_entries"] + 4 * st["table_words"] + 4 * st["probes"] + out_bytes + 2 * needle_bytes)
+        # (in-process over several devices: the counted launch ran the whole batch on ONE of them; kernel_ms is the slowest
+        # shard's search, so the per-device rates take a device's share of the bytes)
+        req_gbs = req_bytes / devices / (k_ms * 1e-3) / 1e9
+        lds_lanes = st["posting_entries"] / devices / (k_ms * 1e-3)
+        # Beside it: memory-side bytes per step from the rocprofv3 --pmc passes of this workload (a SEPARATE run of
+        # this command under the profiler, profiles/traffic_latest.json): the L2's fabric-side counters, i.e. HBM +
+        # Infinity Cache.  Only as good as the build it was taken at: stamped, and stale when the sources changed.
+        pmc = None
+        tpath = os.path.join(ROOT, "profiles", "traffic_latest.json")
+        if os.path.exists(tpath) and args.scale == 1.0:
+            try:
+                prof = json.load(open(tpath))
+                if prof.get(name):
+                    at, now = prof.get("kernel_source_hash"), kernel_source_hash()
+                    pmc = {"bytes_per_step": prof[name], "gbs": prof[name] / (k_ms * 1e-3) / 1e9,
+                           "frac": prof[name] / (k_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                           "profiled_at_commit": prof.get("commit"), "profiled_at_source_hash": at,
+                           "stale": at != now,
+                           "source": "profiles/traffic_latest.json: (2*FETCH_SIZE + WRITE_SIZE) KiB of this workload's find "
+                                     "kernels, rocprofv3 --pmc, separate run (tools/collect_profiles.sh); Infinity-Cache hits included"}
+                    if pmc["stale"]:
+                        log(f"WARNING: profiles/traffic_latest.json was profiled at kernel sources {at}, this run is {now}: "
+                            f"the PMC traffic figure of '{name}' is STALE (re-run tools/collect_profiles.sh)")
+            except Exception as e:
+                pmc = {"error": str(e)}
 
-    # ... and how busy the LDS array was under this workload's dominant kernel (SQ_LDS_IDX_ACTIVE over SQ_BUSY_CU_CYCLES,
-    # tools/lds_pipe.sh: a separate run of this command under rocprofv3 --pmc, stamped like the traffic figure): the
-    # counters, their scan's reads and clears and the bank-conflict replays all pass through it -- the one resource the
-    # workgroups of a CU share, and the roof `lds.frac` (atomic lanes alone) understates
-    lds_pipe = None
-    lpath = os.path.join(ROOT, "profiles", "lds_pipe_latest.json")
-    if os.path.exists(lpath) and args.scale == 1.0:
-        try:
-            prof = json.load(open(lpath))
-            if prof.get(name, {}).get("lds_busy_frac") is not None:
-                at, now = prof.get("kernel_source_hash"), kernel_source_hash()
-                lp = prof[name]
-                lds_pipe = {"busy_frac": lp["lds_busy_frac"], "bank_conflict_share": lp.get("conflict_frac"),
-                            "wave_cycles_waiting_on_lds": lp.get("wait_lds_frac"), "kernel": lp.get("kernel"),
-                            # the VALU's issue slots beside it (a wave64 instruction holds one of a CU's four SIMDs for
-                            # four cycles): what the step's ~4 000 VALU instructions take of the CU
-                            "valu_busy_frac": lp.get("valu_busy_frac"), "salu_busy_frac": lp.get("salu_busy_frac"),
-                            "wave_cycles_waiting": lp.get("wait_any_frac"),
-                            "profiled_at_commit": prof.get("commit"), "profiled_at_source_hash": at, "stale": at != now,
-                            "source": "profiles/lds_pipe_latest.json: SQ_LDS_IDX_ACTIVE / SQ_BUSY_CU_CYCLES of the kernel over one "
-                                      "timed step, rocprofv3 --pmc, separate run (tools/lds_pipe.sh)"}
-                if lds_pipe["stale"]:
-                    log(f"WARNING: profiles/lds_pipe_latest.json was profiled at kernel sources {at}, this run is {now}: "
-                        f"the LDS-pipe figure of '{name}' is STALE (re-run tools/lds_pipe.sh)")
-        except Exception as e:
-            lds_pipe = {"error": str(e)}
+        # ... and how busy the LDS array was under this workload's dominant kernel (SQ_LDS_IDX_ACTIVE over SQ_BUSY_CU_CYCLES,
+        # tools/lds_pipe.sh: a separate run of this command under rocprofv3 --pmc, stamped like the traffic figure): the
+        # counters, their scan's reads and clears and the bank-conflict replays all pass through it -- the one resource the
+        # workgroups of a CU share, and the roof `lds.frac` (atomic lanes alone) understates
+        lds_pipe = None
+        lpath = os.path.join(ROOT, "profiles", "lds_pipe_latest.json")
+        if os.path.exists(lpath) and args.scale == 1.0:
+            try:
+                prof = json.load(open(lpath))
+                if prof.get(name, {}).get("lds_busy_frac") is not None:
+                    at, now = prof.get("kernel_source_hash"), kernel_source_hash()
+                    lp = prof[name]
+                    lds_pipe = {"busy_frac": lp["lds_busy_frac"], "bank_conflict_share": lp.get("conflict_frac"),
+                                "wave_cycles_waiting_on_lds": lp.get("wait_lds_frac"), "kernel": lp.get("kernel"),
+                                # the VALU's issue slots beside it (a wave64 instruction holds one of a CU's four SIMDs for
+                                # four cycles): what the step's ~4 000 VALU instructions take of the CU
+                                "valu_busy_frac": lp.get("valu_busy_frac"), "salu_busy_frac": lp.get("salu_busy_frac"),
+                                "wave_cycles_waiting": lp.get("wait_any_frac"),
+                                "profiled_at_commit": prof.get("commit"), "profiled_at_source_hash": at, "stale": at != now,
+                                "source": "profiles/lds_pipe_latest.json: SQ_LDS_IDX_ACTIVE / SQ_BUSY_CU_CYCLES of the kernel over one "
+                                          "timed step, rocprofv3 --pmc, separate run (tools/lds_pipe.sh)"}
+                    if lds_pipe["stale"]:
+                        log(f"WARNING: profiles/lds_pipe_latest.json was profiled at kernel sources {at}, this run is {now}: "
+                            f"the LDS-pipe figure of '{name}' is STALE (re-run tools/lds_pipe.sh)")
+            except Exception as e:
+                lds_pipe = {"error": str(e)}
 
     totals = torch.tensor([float(sum_nb), k_ms, float(np.mean(gather_ms)) if gather_ms else 0.0],
                           dtype=torch.float64, device=coll_dev)
@@ -865,11 +880,6 @@ def run_workload(name, args, steps, warmup, rank, local_rank, world, dist, cpu_b
                        "parallelism": (f"query-shard x{devices}, in-process: replicas behind the C ABI (option \"devices\"), "
                                        f"rows sent into device 0's buffers by peer copies" if devices > 1 else f"query-shard x{world}"),
                        "scale": args.scale},
-            "p50_query_us": p50_us,
-            "p99_query_us": p99_us,
-            "latency_probes": int(latency_probes),
-            "host_buffer_queries_per_sec": host_rate,
-            "mid_batch": mid if latency_probes else None,
             "matched_entries_per_sec": total_entries * steps / elapsed,
             "entries_per_query": sum_nb / n_q,
             "kernel_ms": k_ms,
@@ -879,7 +889,11 @@ def run_workload(name, args, steps, warmup, rank, local_rank, world, dist, cpu_b
             "retimed": first_attempt is not None,
             "first_ms_per_step": first_attempt["ms_per_step"] if first_attempt else None,
             "sweep_retunes_first_attempt": first_attempt["sweep_retunes"] if first_attempt else 0,
-            "roofline": {
+        }
+        if full:
+            out.update(p50_query_us=p50_us, p99_query_us=p99_us, latency_probes=int(latency_probes),
+                       host_buffer_queries_per_sec=host_rate, mid_batch=mid if latency_probes else None)
+            out["roofline"] = {
                 # what the kernels asked of the memory system in one launch sequence of this batch, counted exactly
                 # in-kernel (blurrily_storage_set_stats) in an extra untimed launch of THIS run; L2 hits included
                 # `bound`: what the profile supports.  "hbm" where the requested bytes are memory-side bytes and reach
@@ -941,9 +955,8 @@ def run_workload(name, args, steps, warmup, rank, local_rank, world, dist, cpu_b
                 "lds_pipe": lds_pipe,
                 "counters": st,
                 "counted_launch_rows_equal_timed": stats_rows_equal,
-                "resident_index_bytes": int(info["device_bytes"])},
-        }
-        out["unpinned"] = UNPINNED
+                "resident_index_bytes": int(info["device_bytes"])}
+            out["unpinned"] = UNPINNED
         if devices > 1:
             out["in_process"] = {"replicas": devices, "distinct_devices": distinct, "n_replicas_made": int(info["n_replicas"]),
                                  "peer_access_mask": int(info["peer_access_mask"]), "same_device_mask": int(info["same_device_mask"]),
@@ -966,10 +979,10 @@ def run_workload(name, args, steps, warmup, rank, local_rank, world, dist, cpu_b
             out["gather_overlapped"] = True     # gather_ms = what a step saw of the collective (issue + waits)
             out["gather_checked"] = gather_checked
             out["shards_verified"] = shards_verified
-        if not stats_rows_equal:
+        if full and not stats_rows_equal:
             log(f"PARITY: the counted launch of '{name}' wrote other rows than the timed one")
             parity_ok = False
-        if counted_sweep != sweep:
+        if full and counted_sweep != sweep:
             log(f"the counted launch of '{name}' took the {counted_sweep} sweep, the timed ones the {sweep} sweep: "
                 f"the roofline block does not describe what was timed")
             parity_ok = False
@@ -995,12 +1008,15 @@ def main():
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--workload", default=None, choices=sorted(W.BENCH_WORKLOADS),
-                    help="default: geonames (configs[2]) plus, at N=1, configs[1] and [4] as extra_configs")
+                    help="default: geonames (configs[2]) plus, with --full at N=1, configs[1] and [4] as extra_configs")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what `value` does not need: roofline (an extra, counted launch), latency "
+                         "probes, cpu_baseline with its parity check, extra_configs and published_curve")
     ap.add_argument("--scale", type=float, default=1.0, help="shrink haystack and batch (debug only)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip extra_configs")
-    ap.add_argument("--cpu-budget", type=float, default=15.0, help="seconds of CPU baseline work")
-    ap.add_argument("--latency-probes", type=int, default=200)
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without cpu_baseline")
+    ap.add_argument("--no-extra", action="store_true", help="--full without extra_configs")
+    ap.add_argument("--cpu-budget", type=float, default=15.0, help="seconds of CPU baseline work (--full)")
+    ap.add_argument("--latency-probes", type=int, default=200, help="single finds timed for p50_query_us (--full)")
     ap.add_argument("--scaling", default="weak", choices=("weak", "strong"),
                     help="N > 1: weak = every rank its own batch of the workload's size (1 M needles per GPU at configs[2]); "
                          "strong = configs[3]'s literal batch, 8 M needles in all at Geonames scale (8 x the workload's), cut "
@@ -1026,6 +1042,8 @@ def main():
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.inject_failure and not args.full:
+        ap.error("--inject-failure fails a leg of --full: pass --full")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -1057,15 +1075,15 @@ def main():
             dist.init_process_group(backend=backend)
 
     main_name = args.workload or "geonames"
-    budget = 0.0 if args.no_cpu_baseline else args.cpu_budget
+    budget = 0.0 if args.no_cpu_baseline or not args.full else args.cpu_budget
     out, ok = run_workload(main_name, args, args.steps, args.warmup, rank, local_rank, world, dist, budget,
-                           args.latency_probes, dump_dir=args.dump_outputs)
-    if world == 1 and args.workload is None and not args.no_extra and not args.in_process:
+                           args.latency_probes if args.full else 0, dump_dir=args.dump_outputs, full=args.full)
+    if args.full and world == 1 and args.workload is None and not args.no_extra and not args.in_process:
         extra = {}
         for name in EXTRA_CONFIGS:
             try:
                 line, ok_x = run_workload(name, args, max(3, min(args.steps, 10)), 1, rank, local_rank, world, dist,
-                                          min(budget, 4.0), min(args.latency_probes, 50))
+                                          min(budget, 4.0), min(args.latency_probes, 50), full=True)
                 ok = ok and ok_x
                 extra[name] = {k: line[k] for k in ("value", "unit", "steps", "ms_per_step", "config", "p50_query_us", "p99_query_us",
                                                     "matched_entries_per_sec", "entries_per_query", "kernel_ms", "sweep_retunes",
@@ -1082,7 +1100,8 @@ def main():
                                    "note": "absent on this box: `words` above is its seeded stand-in"}
         else:
             try:
-                line, ok_x = run_workload("dict_words", args, 3, 1, rank, local_rank, world, dist, min(budget, 4.0), 50)
+                line, ok_x = run_workload("dict_words", args, 3, 1, rank, local_rank, world, dist, min(budget, 4.0), 50,
+                                          full=True)
                 ok = ok and ok_x
                 extra["dict_words"] = {k: line[k] for k in ("value", "unit", "steps", "ms_per_step", "config", "p50_query_us",
                                                             "kernel_ms", "sweep_retunes", "roofline", "cpu_baseline", "parity_checked") if k in line}

@@ -79,6 +79,20 @@ def test_a_failed_leg_stays_visible_and_short(bench, canned):
     assert "error" in back["extra_configs"]["skewed"]
 
 
+def test_a_plain_line_carries_no_leg_of_full(bench, canned):
+    """Without --full the record holds no roofline, CPU baseline, latency probes or extra configs: the line names none
+    of them, and keeps every headline key."""
+    plain = {k: v for k, v in canned.items() if k not in ("roofline", "cpu_baseline", "extra_configs", "mid_batch",
+                                                            "p50_query_us", "p99_query_us", "latency_probes",
+                                                            "host_buffer_queries_per_sec", "unpinned", "parity_checked")}
+    back = json.loads(bench.compact_line(plain))
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "config"):
+        assert k in back, k
+    for k in ("roofline", "cpu_baseline", "extra_configs", "p50_query_us", "host_buffer_queries_per_sec"):
+        assert k not in back, k
+    assert back["value"] == pytest.approx(canned["value"], rel=1e-3)
+
+
 def test_a_line_that_outgrows_the_limit_is_refused(bench, canned):
     full = json.loads(json.dumps(canned))
     full["config"]["workload"] = "w" * 7000

@@ -269,7 +269,7 @@ def test_bench_n1_under_the_launcher_is_the_plain_n1_line():
         port = s.getsockname()[1]
     detail = f"/tmp/blurrily_n1_detail_{os.getpid()}.json"
     tail = [os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--scale", "0.05",
-            "--no-extra", "--no-cpu-baseline", "--latency-probes", "0", "--detail", detail]
+            "--full", "--no-extra", "--no-cpu-baseline", "--latency-probes", "0", "--detail", detail]
     lines = []
     for launcher in ([], ["-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
                           "--master-port", str(port)]):
@@ -321,7 +321,7 @@ def _run_bench(args, timeout=900):
 def test_bench_fails_loudly_when_a_leg_fails():
     """A bench line without its CPU baseline, or with a dead extra config, is not a result: the line is still
     printed, carries the error, and the exit status is 1 (VERDICT r03 "weak" #6)."""
-    res, d = _run_bench(["--steps", "2", "--warmup", "1", "--scale", "0.02", "--cpu-budget", "1", "--latency-probes", "0",
+    res, d = _run_bench(["--full", "--steps", "2", "--warmup", "1", "--scale", "0.02", "--cpu-budget", "1", "--latency-probes", "0",
                          "--inject-failure", "words"])
     assert res.returncode == 1, (res.returncode, res.stderr[-1500:])
     assert d is not None and "injected failure" in d["extra_configs"]["words"]["cpu_baseline"]["error"]
@@ -333,7 +333,7 @@ def test_bench_fails_loudly_when_a_leg_fails():
         x = d["extra_configs"][name]
         assert "error" not in x and x["parity_checked"] >= 64 and x["cpu_baseline"]["parity_mismatches"] == 0, (name, x)
         assert x["roofline"]["counted_launch_rows_equal_timed"] is True and x["roofline"]["sweep"] == x["roofline"]["counted_sweep"]
-    res, d = _run_bench(["--steps", "2", "--warmup", "1", "--scale", "0.02", "--cpu-budget", "1", "--latency-probes", "0",
+    res, d = _run_bench(["--full", "--steps", "2", "--warmup", "1", "--scale", "0.02", "--cpu-budget", "1", "--latency-probes", "0",
                          "--no-extra", "--inject-failure", "geonames"])
     assert res.returncode == 1 and "injected failure" in d["cpu_baseline"]["error"]
     assert "injected failure" in d["_line"]["cpu_baseline"]["error"]
@@ -343,8 +343,8 @@ def test_bench_in_process_over_two_logical_devices():
     """`--gpus 2 --in-process`: one process, option "devices" 2 (with one GPU on the box both replicas live on it), the
     two ranks' needles in one call.  Plumbing, not a measurement: the line's bookkeeping, and rows equal to the
     reference's on the checked prefix."""
-    res, d = _run_bench(["--gpus", "2", "--in-process", "--steps", "2", "--warmup", "1", "--scale", "0.05", "--cpu-budget", "1",
-                         "--latency-probes", "0"])
+    res, d = _run_bench(["--full", "--gpus", "2", "--in-process", "--steps", "2", "--warmup", "1", "--scale", "0.05",
+                         "--cpu-budget", "1", "--latency-probes", "0"])
     assert res.returncode == 0, res.stderr[-2000:]
     # with one GPU on the box both replicas share it: the line does not call that two GPUs
     import torch
@@ -358,15 +358,19 @@ def test_bench_in_process_over_two_logical_devices():
 
 def test_bench_dump_outputs_are_what_the_timed_path_computed(tmp_path):
     """`--dump-outputs DIR`: the rows and counts of the last timed step, checked against a direct find of the same
-    seeded batch on a map built the way bench.py builds it; `--steps` is the number of timed steps in the line."""
+    seeded batch on a map built the way bench.py builds it; `--steps` is the number of timed steps in the line.  A
+    plain run (no --full) is lean: no counted launch, no latency probes, no CPU baseline, no extra configs."""
     import numpy as np
     import workloads as W
     from blurrily_amd import RawMap
     out = tmp_path / "out"
-    res, d = _run_bench(["--steps", "4", "--warmup", "1", "--scale", "0.02", "--no-extra", "--no-cpu-baseline",
-                         "--latency-probes", "0", "--dump-outputs", str(out)])
+    res, d = _run_bench(["--steps", "4", "--warmup", "1", "--scale", "0.02", "--dump-outputs", str(out)])
     assert res.returncode == 0, res.stderr[-1500:]
     assert d["_line"]["steps"] == 4 and d["_line"]["ms_per_step"] > 0
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype"):
+        assert k in d["_line"], k
+    for k in ("roofline", "cpu_baseline", "extra_configs", "p50_query_us", "host_buffer_queries_per_sec", "unpinned"):
+        assert k not in d and k not in d["_line"], k
     rows, counts, idx = (np.load(out / f"{k}.npy") for k in ("rows", "counts", "needle_index"))
     assert rows.dtype == counts.dtype == idx.dtype == np.float64
     hay, off = W.bench_haystack("geonames", 0.02)

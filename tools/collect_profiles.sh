@@ -1,8 +1,8 @@
 #!/bin/bash
 # usage (on the GPU box, from the repo root): tools/collect_profiles.sh <round-tag>
 # Produces under gpurun_out/<tag>/ everything profiles/ is refreshed from:
-#   bench.json / bench.log             python bench.py (configs[2] with cpu_baseline + extra_configs)
-#   stats/                             rocprofv3 --kernel-trace --stats of `python bench.py --no-cpu-baseline --no-extra`
+#   bench.json / bench.log             python bench.py --full (configs[2] with cpu_baseline + extra_configs)
+#   stats/                             rocprofv3 --kernel-trace --stats of `python bench.py --full --no-cpu-baseline --no-extra`
 #   stats_skewed/, stats_x4/           the same for --workload skewed (the window-major sweep's kernels) and geonames_x4 (the
 #                                      needle-major sweep that leaves slices out: an image seven times the Infinity Cache)
 #   pmc_{fetch,write,tcc}_<workload>/  rocprofv3 --pmc passes, one counter group per run, per workload
@@ -13,15 +13,15 @@ root=${GRAFT_REPO_ROOT:-$PWD}
 out=$root/gpurun_out/$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
-python $root/bench.py --detail $out/bench_detail.json > $out/bench.json 2> $out/bench.log   # (bench.json: the short line; bench_detail.json: the record)
+python $root/bench.py --full --detail $out/bench_detail.json > $out/bench.json 2> $out/bench.log   # (bench.json: the short line; bench_detail.json: the record)
 # (--latency-probes 0: no single finds, no host-buffer batch -- whose chunks are launches of the same kernel --
 #  so that the kernel's average duration in the summary is the timed steps' and the warm-up's; --force-sweep 3: the sweep
 #  the bench run's measurement picks, without the measurement -- since round 6 the plain sweep and the one that leaves
 #  slices out are ONE kernel symbol, and the measurement's plain runs would be averaged in)
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -o bench -- python $root/bench.py --force-sweep 3 --no-cpu-baseline --no-extra --latency-probes 0 --detail $out/stats_bench_detail.json > $out/stats_bench.json 2> $out/stats_bench.log
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats_skewed -o bench -- python $root/bench.py --workload skewed --force-sweep 3 --no-cpu-baseline --latency-probes 0 --detail $out/stats_skewed_detail.json > $out/stats_skewed.json 2> $out/stats_skewed.log
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats_x4 -o bench -- python $root/bench.py --workload geonames_x4 --force-sweep 3 --no-cpu-baseline --latency-probes 0 --detail $out/stats_x4_detail.json > $out/stats_x4.json 2> $out/stats_x4.log
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats_words -o bench -- python $root/bench.py --workload words --no-cpu-baseline --latency-probes 0 --detail $out/stats_words_detail.json > $out/stats_words.json 2> $out/stats_words.log
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -o bench -- python $root/bench.py --full --force-sweep 3 --no-cpu-baseline --no-extra --latency-probes 0 --detail $out/stats_bench_detail.json > $out/stats_bench.json 2> $out/stats_bench.log
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats_skewed -o bench -- python $root/bench.py --full --workload skewed --force-sweep 3 --no-cpu-baseline --latency-probes 0 --detail $out/stats_skewed_detail.json > $out/stats_skewed.json 2> $out/stats_skewed.log
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats_x4 -o bench -- python $root/bench.py --full --workload geonames_x4 --force-sweep 3 --no-cpu-baseline --latency-probes 0 --detail $out/stats_x4_detail.json > $out/stats_x4.json 2> $out/stats_x4.log
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats_words -o bench -- python $root/bench.py --full --workload words --no-cpu-baseline --latency-probes 0 --detail $out/stats_words_detail.json > $out/stats_words.json 2> $out/stats_words.log
 # the sweep the bench run above took for a workload (its measured choice): the PMC passes force the same one
 sweep_of() { python - "$out/bench_detail.json" "$1" <<'PY'
 import json, sys

@@ -8,7 +8,7 @@ cd /tmp && export TMPDIR=/tmp
 for lib in "${@:-libblurrily_hip.so}"; do
   d=$out/insts_$lib; mkdir -p $d
   BLURRILY_LIB=$root/blurrily_amd/$lib timeout 300 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_BUSY_CU_CYCLES --kernel-trace -d $d -o pmc -- \
-    python $root/bench.py --workload geonames --steps 1 --warmup 0 --force-sweep 3 --no-cpu-baseline --no-extra --latency-probes 0 --detail $d/detail.json > $d/bench.json 2> $d/bench.log
+    python $root/bench.py --full --workload geonames --steps 1 --warmup 0 --force-sweep 3 --no-cpu-baseline --no-extra --latency-probes 0 --detail $d/detail.json > $d/bench.json 2> $d/bench.log
   python - "$d" "$lib" <<'P'
 import glob, os, sqlite3, sys, json
 d, lib = sys.argv[1], sys.argv[2]
