@@ -136,6 +136,12 @@ def lib():
         "blurrily_storage_find_references_each_in": (C.c_int, [vp, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
                                                                C.c_size_t, C.c_uint16, C.c_void_p, C.c_void_p,
                                                                C.c_void_p]),
+        "blurrily_storage_find_batch_above": (C.c_int, [vp, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32,
+                                                        C.c_void_p, C.c_uint64, C.c_void_p]),
+        "blurrily_storage_find_above": (C.c_int, [vp, C.c_char_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64,
+                                                  C.POINTER(C.c_uint64)]),
+        "blurrily_storage_find_references_above": (C.c_int, [vp, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32,
+                                                             C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     }
     for name, (res, args) in sig.items():
         try:
@@ -172,5 +178,8 @@ EXPORTED_SYMBOLS = (
     # a scope per needle: batched scoped find and find-by-reference, each needle among its own scope
     "blurrily_storage_find_batch_each_in", "blurrily_storage_find_batch_each_in_device",
     "blurrily_storage_find_references_each_in",
+) + (
+    # threshold find: every row at or above a bar of matches
+    "blurrily_storage_find_batch_above", "blurrily_storage_find_above", "blurrily_storage_find_references_above",
 )
 NO_SCOPE = 0xFFFFFFFF                                  # BLURRILY_NO_SCOPE: a needle of such a batch with no scope

@@ -19,6 +19,7 @@ from . import _native
 from .defaults import LIMIT_DEFAULT
 
 _U32_MAX = 0xFFFFFFFF
+_NO_BYTES = C.create_string_buffer(1)
 
 
 class ClosedError(RuntimeError):
@@ -429,6 +430,82 @@ class RawMap:
             if once:
                 sc.close()
 
+    # -- threshold find (no reference counterpart): every row at or above a bar of matches -------------------------
+    @staticmethod
+    def _bar(min_matches, min_permille):
+        mm, mp = _u32(min_matches, "min_matches"), _u32(min_permille, "min_permille")
+        if mp > 1000:
+            raise ValueError(f"min_permille {min_permille!r} above 1000")
+        return mm, mp
+
+    def _above(self, call, n):
+        """One threshold call with room for a guessed number of rows, and once more with the exact room on ERANGE
+        (the library then reports what it needs).  Returns (rows[R, 3] uint32, row_off[n + 1] uint64)."""
+        row_off = np.zeros(n + 1, dtype=np.uint64)
+        cap = max(1024, 16 * n)
+        while True:
+            rows = np.empty((cap, 3), dtype=np.uint32)
+            if call(rows.ctypes.data, cap, row_off.ctypes.data) == 0:
+                return rows[:int(row_off[n])], row_off
+            if C.get_errno() != 34 or int(row_off[n]) <= cap:      # ERANGE: row_off[n] holds the room needed
+                _raise_errno()
+            cap = int(row_off[n])
+
+    def find_batch_above_packed(self, packed, offsets, min_matches=0, min_permille=0):
+        """Every row of each needle with at least its bar of matches, bar = max(1, min_matches, ceil(min_permille * T /
+        1000)) for a needle of T distinct trigrams, in find's order.  Returns (rows[R, 3] uint32, row_off[n + 1]
+        uint64): needle i's rows are rows[row_off[i]:row_off[i + 1]]."""
+        self._check_open()
+        mm, mp = self._bar(min_matches, min_permille)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = len(offsets) - 1
+        buf = np.frombuffer(packed, dtype=np.uint8) if not isinstance(packed, np.ndarray) else packed
+        data = buf.ctypes.data if buf.size else (None if n == 0 else C.addressof(_NO_BYTES))   # (n empty needles)
+        return self._above(lambda rows, cap, off: self._lib.blurrily_storage_find_batch_above(
+            self._h, data, offsets.ctypes.data, n, mm, mp, rows, cap, off), n)
+
+    def find_above(self, needle, min_matches=0, min_permille=0):
+        """``find_batch_above_packed`` for one needle: a list of ``[ref, matches, weight]``."""
+        self._check_open()
+        mm, mp = self._bar(min_matches, min_permille)
+        s = _as_bytes(needle)
+        total = C.c_uint64(0)
+        cap = 1024
+        while True:
+            rows = np.empty((cap, 3), dtype=np.uint32)
+            if self._lib.blurrily_storage_find_above(self._h, s, mm, mp, rows.ctypes.data, cap, C.byref(total)) == 0:
+                return rows[:total.value].tolist()
+            if C.get_errno() != 34 or total.value <= cap:
+                _raise_errno()
+            cap = total.value
+
+    def find_batch_by_reference_above(self, references, min_matches=0, min_permille=0):
+        """``find_batch_above_packed`` for stored references (each among its own rows; none for a reference the map
+        does not hold).  Returns (rows[R, 3] uint32, row_off[n + 1] uint64, nb_trigrams[n] uint32)."""
+        self._check_open()
+        mm, mp = self._bar(min_matches, min_permille)
+        refs = self._refs(references)
+        n = len(refs)
+        ntri = np.zeros(n, dtype=np.uint32)
+        rows, row_off = self._above(lambda rows, cap, off: self._lib.blurrily_storage_find_references_above(
+            self._h, refs.ctypes.data if n else None, n, mm, mp, rows, cap, off, ntri.ctypes.data), n)
+        return rows, row_off, ntri
+
+    def join_above(self, references, min_matches=0, min_permille=0):
+        """The threshold self-join: every held reference's rows at or above its bar, as arrays.  Returns (refs[k]
+        uint32: the references the map holds, in the order given; row_off[k + 1] uint64; rows[R, 3] uint32)."""
+        rows, row_off, ntri = self.find_batch_by_reference_above(references, min_matches, min_permille)
+        refs = self._refs(references)
+        held = np.nonzero(ntri)[0]
+        counts = np.diff(row_off.astype(np.int64))[held]
+        off = np.zeros(len(held) + 1, dtype=np.uint64)
+        off[1:] = np.cumsum(counts)
+        if len(held) == len(refs):
+            return refs, off, rows
+        at = np.repeat(row_off[:-1].astype(np.int64)[held] - off[:-1].astype(np.int64), counts) + \
+            np.arange(int(off[-1]), dtype=np.int64)
+        return refs[held], off, rows[at]
+
     def sync_device(self):
         self._check_open()
         if self._lib.blurrily_storage_sync_device(self._h) < 0:
@@ -665,6 +742,16 @@ class Map(RawMap):
 
     def join_within(self, scopes, limit=LIMIT_DEFAULT):
         return super().join_within(scopes, limit if int(limit) > 0 else LIMIT_DEFAULT)
+
+    def find_above(self, needle, min_matches=0, min_permille=0):
+        """Every row of the normalised needle at or above its bar (``RawMap.find_above``)."""
+        return super().find_above(normalize_string(needle), min_matches, min_permille)
+
+    def find_batch_above(self, needles, min_matches=0, min_permille=0):
+        """``[self.find_above(s, min_matches, min_permille) for s in needles]`` in one GPU batch."""
+        packed, offsets = _pack([_as_bytes(normalize_string(s)) for s in needles])
+        rows, row_off = super().find_batch_above_packed(packed, offsets, min_matches, min_permille)
+        return [rows[int(row_off[i]):int(row_off[i + 1])].tolist() for i in range(len(needles))]
 
     def find_batch(self, needles, limit=LIMIT_DEFAULT):
         """``[self.find(s, limit) for s in needles]`` in one GPU batch."""

@@ -286,6 +286,30 @@ int blurrily_storage_find_references_each_in(trigram_map haystack, const blurril
                                              uint16_t limit, trigram_match results, uint32_t* counts,
                                              uint32_t* nb_trigrams);
 
+/* Threshold find: every row with at least the needle's bar of matches, not the best `limit`.  With T the needle's
+ * distinct trigrams (what blurrily_tokeniser_parse_string returns for it), the bar is
+ * t = max(1, min_matches, ceil(min_permille * T / 1000)).  A needle's rows are every row blurrily_storage_find would
+ * return at an unbounded limit whose matches are >= t, in that order (matches descending, weight ascending,
+ * reference ascending); a needle with T == 0 or t > T has none.  The map is read as find reads it.  With "devices" > 1
+ * the primary device alone serves the call.
+ * Rows of needle i are results[row_off[i] .. row_off[i+1]) (n + 1 offsets, always filled on success or ERANGE).
+ * results == NULL: count only -- row_off filled, 0 returned.  capacity < row_off[n]: -1, errno ERANGE, results
+ * untouched.  0, or -1 with errno (EINVAL before anything needs a GPU: min_permille > 1000, row_off NULL, packed or
+ * offsets NULL with n > 0; ENODEV without a usable GPU). */
+int blurrily_storage_find_batch_above(trigram_map haystack, const char* packed, const uint64_t* offsets, size_t n,
+                                      uint32_t min_matches, uint32_t min_permille,
+                                      trigram_match results, uint64_t capacity, uint64_t* row_off);
+/* One needle: the same with n == 1; *total (optional) = its row count, also on ERANGE. */
+int blurrily_storage_find_above(trigram_map haystack, const char* needle, uint32_t min_matches,
+                                uint32_t min_permille, trigram_match results, uint64_t capacity, uint64_t* total);
+/* By reference: element i is blurrily_storage_find_batch_above of any string whose tokenisation is reference i's
+ * trigram set; the reference itself is among its rows (matches == T).  An absent reference: no rows,
+ * nb_trigrams[i] == 0 (nb_trigrams may be NULL).  EINVAL also for references NULL with n > 0. */
+int blurrily_storage_find_references_above(trigram_map haystack, const uint32_t* references, size_t n,
+                                           uint32_t min_matches, uint32_t min_permille,
+                                           trigram_match results, uint64_t capacity, uint64_t* row_off,
+                                           uint32_t* nb_trigrams);
+
 /* Tokeniser (ext/blurrily/tokeniser.h:34, tokeniser.c:59-119): `output` needs
  * strlen(input)+1 slots; returns the number of distinct codes, ascending. */
 int blurrily_tokeniser_parse_string(const char* input, uint16_t* output);

@@ -461,6 +461,30 @@ static VALUE blurrily_sync_device(VALUE self)
   return Qnil;
 }
 
+/* find_above(needle, min_matches, min_permille): every row at or above the needle's bar, [[ref, matches, weight], ...].
+ * Holds the GVL: the count and the fill see the same map. */
+static VALUE blurrily_find_above(VALUE self, VALUE rb_needle, VALUE rb_min_matches, VALUE rb_min_permille)
+{
+  trigram_map   map = map_of(self);
+  const char*   needle = StringValueCStr(rb_needle);
+  uint32_t      mm = NUM2UINT(rb_min_matches), mp = NUM2UINT(rb_min_permille);
+  uint64_t      total = 0, k;
+  trigram_match rows;
+  VALUE         out;
+  if (blurrily_storage_find_above(map, needle, mm, mp, NULL, 0, &total) < 0) rb_sys_fail("blurrily_storage_find_above");
+  rows = ALLOC_N(trigram_match_t, total + 1);
+  if (blurrily_storage_find_above(map, needle, mm, mp, rows, total, &total) < 0) {
+    xfree(rows);
+    rb_sys_fail("blurrily_storage_find_above");
+  }
+  out = rb_ary_new2((long)total);
+  for (k = 0; k < total; ++k)
+    rb_ary_push(out, rb_ary_new3(3, rb_uint_new(rows[k].reference), rb_uint_new(rows[k].matches),
+                                 rb_uint_new(rows[k].weight)));
+  xfree(rows);
+  return out;
+}
+
 static VALUE blurrily_set_option(VALUE self, VALUE rb_key, VALUE rb_value)
 {
   if (blurrily_storage_set_option(map_of(self), StringValueCStr(rb_key), NUM2LL(rb_value)) < 0)
@@ -499,4 +523,5 @@ void Init_map_ext(void)
   rb_define_method(cRawMap, "get",            blurrily_get,            1);
   rb_define_method(cRawMap, "find_among",     blurrily_find_among,     3);
   rb_define_method(cRawMap, "find_batch_among", blurrily_find_batch_among, 4);
+  rb_define_method(cRawMap, "find_above",     blurrily_find_above,     3);
 }
