@@ -142,6 +142,11 @@ def lib():
                                                   C.POINTER(C.c_uint64)]),
         "blurrily_storage_find_references_above": (C.c_int, [vp, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32,
                                                              C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+        "blurrily_storage_find_batch_similar": (C.c_int, [vp, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint16,
+                                                          C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+        "blurrily_storage_find_similar": (C.c_int, [vp, C.c_char_p, C.c_uint16, C.c_uint32, C.c_void_p, C.c_void_p]),
+        "blurrily_storage_find_references_similar": (C.c_int, [vp, C.c_void_p, C.c_size_t, C.c_uint16, C.c_uint32,
+                                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     }
     for name, (res, args) in sig.items():
         try:
@@ -181,5 +186,8 @@ EXPORTED_SYMBOLS = (
 ) + (
     # threshold find: every row at or above a bar of matches
     "blurrily_storage_find_batch_above", "blurrily_storage_find_above", "blurrily_storage_find_references_above",
+) + (
+    # similarity find: the best rows by trigram Jaccard similarity
+    "blurrily_storage_find_batch_similar", "blurrily_storage_find_similar", "blurrily_storage_find_references_similar",
 )
 NO_SCOPE = 0xFFFFFFFF                                  # BLURRILY_NO_SCOPE: a needle of such a batch with no scope

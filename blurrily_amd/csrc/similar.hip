@@ -1,0 +1,412 @@
+// similar.hip -- the similarity find's entry points (include/blurrily_storage.h).  Compiled as
+// one translation unit with above.hip and c_abi.hip, whose map internals (the mutation log, the device images, the
+// string and by-reference front ends) they drive; the kernels are similar_kernels.hip's.
+#include "above.hip"
+
+#include <mutex>
+
+#include "similar.h"
+
+namespace {
+
+constexpr size_t   kSimChunkNeedles = size_t(1) << 20;   // needles per sweep launch
+constexpr uint64_t kSimChunkKeys    = uint64_t(1) << 24; // keys (16 B, twice: keys and sorted keys) or rows per chunk
+
+// device scratch of one call, freed on the way out
+struct SimilarScratch {
+  DeviceBuffer b[10];
+  ~SimilarScratch() { for (auto& x : b) x.release(); }
+};
+
+// ---- per-rank trigram counts, one table per device image -------------------------------------------------------------
+// A table is built at the first similarity call on an image and kept beside it: an image that never serves one holds
+// what it held before.  An image is known by the allocation of its postings, under the runtime's process-wide buffer
+// id -- a rebuilt image (new postings), or a closed map's, no longer matches, and its table is freed at the next
+// similarity call on any map.  Where the runtime gives no ids, a call builds the tables it needs and frees them.
+struct SimilarTableEntry {
+  const DeviceIndex* ix;
+  const void*        ent;
+  unsigned long long ent_id;
+  int                device;
+  SimilarTable       t;
+  size_t             bytes;
+};
+std::mutex                     g_sim_mu;
+std::vector<SimilarTableEntry> g_sim_tables;
+
+bool buffer_id(const void* p, unsigned long long* id) {
+  unsigned long long v = 0;
+  if (hipPointerGetAttribute(&v, HIP_POINTER_ATTRIBUTE_BUFFER_ID, const_cast<void*>(p)) != hipSuccess) {
+    (void)hipGetLastError();                            // (a freed allocation: not an error of this call)
+    return false;
+  }
+  *id = v;
+  return true;
+}
+
+void free_table(SimilarTableEntry& e) {
+  DeviceScope scope(e.device);
+  if (e.t.ntri_of_rank) (void)hipFree(e.t.ntri_of_rank);
+  if (e.t.win_min_tri) (void)hipFree(e.t.win_min_tri);
+  e.t = SimilarTable();
+}
+
+// A call's tables: those it found kept, and those it built and keeps -- or, without buffer ids, frees on the way out.
+struct SimilarTables {
+  std::vector<SimilarTableEntry> own;
+  ~SimilarTables() { for (auto& e : own) free_table(e); }
+};
+
+int similar_table(DeviceIndex* ix, hipStream_t stream, SimilarTables& call, SimilarTable* out) {
+  std::lock_guard<std::mutex> lock(g_sim_mu);
+  for (size_t i = 0; i < g_sim_tables.size();) {             // tables of images that are gone
+    unsigned long long id = 0;
+    SimilarTableEntry& e = g_sim_tables[i];
+    if (buffer_id(e.ent, &id) && id == e.ent_id) { ++i; continue; }
+    free_table(e);
+    g_sim_tables[i] = g_sim_tables.back();
+    g_sim_tables.pop_back();
+  }
+  unsigned long long id = 0, other = 0;
+  // ids are usable when two allocations of the image have different ones
+  const bool keep = buffer_id(ix->d_ent, &id) && buffer_id(ix->d_slice_se, &other) && id != other;
+  if (keep)
+    for (const SimilarTableEntry& e : g_sim_tables)
+      if (e.ix == ix && e.ent == ix->d_ent && e.ent_id == id) { *out = e.t; return 0; }
+  SimilarTableEntry e{ix, ix->d_ent, id, ix->device, SimilarTable(), 0};
+  const size_t b_ntri = std::max<size_t>(ix->n_refs, 1) * 2, b_win = std::max<size_t>(ix->n_windows, 1) * 4;
+  if (hipMalloc(reinterpret_cast<void**>(&e.t.ntri_of_rank), b_ntri) != hipSuccess ||
+      hipMalloc(reinterpret_cast<void**>(&e.t.win_min_tri), b_win) != hipSuccess) {
+    (void)hipGetLastError();
+    free_table(e);
+    errno = ENOMEM;
+    return -1;
+  }
+  e.bytes = b_ntri + b_win;
+  if (launch_similar_ntri(*ix, e.t, stream) < 0) { free_table(e); return -1; }
+  *out = e.t;
+  if (keep) {
+    g_sim_tables.push_back(e);
+    ix->device_bytes += e.bytes;
+  } else {
+    call.own.push_back(e);
+  }
+  return 0;
+}
+
+// ---- the search -----------------------------------------------------------------------------------------------------
+// The sorted segments of a chunk's needles, one per image: sort what is not sorted yet (tiles in LDS, then merge passes
+// over the segments longer than a tile), then write the rows.  off[i]: nc + 1 offsets into keys[i] (device and host).
+int similar_finish(uint32_t n_img, SimilarKey* const keys[2], SimilarKey* const sorted[2], const uint32_t* const d_off[2],
+                   const std::vector<uint32_t>* const h_off, const bool need_sort[2], size_t nc, uint32_t limit,
+                   SimilarScratch& S, trigram_match d_rows, uint32_t* d_rntri, uint32_t* d_counts, hipStream_t stream) {
+  std::vector<SimilarTile> tiles[2];
+  std::vector<uint32_t> longs[2];                             // seg_start | seg_len | elem_off, each of n_long (+1)
+  uint32_t max_len[2] = {0, 0};
+  for (uint32_t i = 0; i < n_img; ++i) {
+    if (!need_sort[i]) continue;
+    const std::vector<uint32_t>& o = h_off[i];
+    std::vector<uint32_t> st, ln, eo{0};
+    for (size_t q = 0; q < nc; ++q) {
+      const uint32_t len = o[q + 1] - o[q];
+      if (len < 2) continue;
+      for (uint32_t t0 = 0; t0 < len; t0 += kSimTile) tiles[i].push_back(SimilarTile{o[q] + t0, std::min(kSimTile, len - t0)});
+      if (len > kSimTile) { st.push_back(o[q]); ln.push_back(len); eo.push_back(eo.back() + len); }
+      max_len[i] = std::max(max_len[i], len);
+    }
+    longs[i] = st;
+    longs[i].insert(longs[i].end(), ln.begin(), ln.end());
+    longs[i].insert(longs[i].end(), eo.begin(), eo.end());
+  }
+  const size_t tile_bytes = align_up((tiles[0].size() + tiles[1].size()) * sizeof(SimilarTile), 256);
+  if (S.b[4].reserve(tile_bytes + align_up((longs[0].size() + longs[1].size()) * 4, 256) + 256, stream) < 0) return -1;
+  SimilarTile* d_tiles = static_cast<SimilarTile*>(S.b[4].p);
+  uint32_t* d_longs = reinterpret_cast<uint32_t*>(static_cast<unsigned char*>(S.b[4].p) + tile_bytes);
+  SimilarRowsArgs r{};
+  for (uint32_t i = 0; i < n_img; ++i) {
+    r.keys[i] = keys[i]; r.off[i] = d_off[i]; r.n_keys[i] = h_off[i][nc];
+    if (!need_sort[i] || h_off[i][nc] == 0) continue;
+    // (the segments shorter than two keys are copied as they are)
+    BLURRILY_HIP_TRY(hipMemcpyAsync(sorted[i], keys[i], size_t(h_off[i][nc]) * sizeof(SimilarKey), hipMemcpyDeviceToDevice, stream));
+    SimilarTile* t_i = d_tiles + (i ? tiles[0].size() : 0);
+    uint32_t* l_i = d_longs + (i ? longs[0].size() : 0);
+    if (!tiles[i].empty())
+      BLURRILY_HIP_TRY(hipMemcpyAsync(t_i, tiles[i].data(), tiles[i].size() * sizeof(SimilarTile), hipMemcpyHostToDevice, stream));
+    if (!longs[i].empty())
+      BLURRILY_HIP_TRY(hipMemcpyAsync(l_i, longs[i].data(), longs[i].size() * 4, hipMemcpyHostToDevice, stream));
+    if (launch_similar_tiles(t_i, uint32_t(tiles[i].size()), keys[i], sorted[i], stream) < 0) return -1;
+    const uint32_t n_long = uint32_t((longs[i].size() - 1) / 3);
+    if (n_long) {
+      SimilarMergeArgs g{l_i, l_i + n_long, l_i + 2 * n_long, n_long, longs[i][3 * n_long], kSimTile, sorted[i], keys[i]};
+      for (; g.width < max_len[i]; g.width *= 2) {
+        if (launch_similar_merge(g, stream) < 0) return -1;
+        std::swap(const_cast<SimilarKey*&>(g.in), g.out);
+      }
+      if (g.in != sorted[i]) {                                // (an odd number of passes: copied back)
+        g.width = 1u << 31;
+        if (launch_similar_merge(g, stream) < 0) return -1;
+      }
+    }
+    r.keys[i] = sorted[i];
+  }
+  r.n_img = n_img; r.n = uint32_t(nc); r.limit = limit;
+  r.rows = d_rows; r.row_ntri = d_rntri; r.counts = d_counts;
+  return launch_similar_rows(r, stream);
+}
+
+// The top-`limit` rows of n needles over the map as it is now: results / row_ntri [n * limit], counts [n].
+int similar_run(trigram_map m, size_t n, const AboveNeedles& N, uint32_t limit, uint32_t min_permille,
+                trigram_match results, uint32_t* counts, uint32_t* row_ntri, hipStream_t stream, SimilarScratch& S) {
+  const bool with_delta = !log_of(m)->pending.empty() && m->delta.device >= 0;
+  const uint32_t n_img = with_delta ? 2u : 1u;
+  DeviceIndex* img[2] = {&m->dev, &m->delta};
+  const uint32_t* tomb[2] = {log_of(m)->n_tomb ? m->dev.d_tomb : nullptr, nullptr};
+  SimilarTables call;
+  SimilarTable tab[2];
+  for (uint32_t i = 0; i < n_img; ++i)
+    if (similar_table(img[i], stream, call, &tab[i]) < 0) return -1;
+  const bool all = limit > kSimListMax;
+  // windows per workgroup: a small batch spreads each needle's windows over the GPU, a large one gives a needle one
+  // workgroup; in list mode a needle's lists (tasks * limit keys) fit one tile
+  auto per_of = [&](const DeviceIndex& ix, size_t nc) {
+    const uint64_t want = uint64_t(std::max(m->n_cus, 1)) * 8u;
+    uint64_t per = std::max<uint64_t>(uint64_t(ix.n_windows) * nc / want, 1);
+    if (!all) per = std::max<uint64_t>(per, (ix.n_windows + kSimTile / limit - 1) / (kSimTile / limit));
+    return uint32_t(std::min<uint64_t>(per, std::max<uint32_t>(ix.n_windows, 1)));
+  };
+  auto args_of = [&](uint32_t i, size_t s, size_t nc) {
+    const DeviceIndex& ix = *img[i];
+    SimilarArgs a{};
+    a.slice_se = ix.d_slice_se; a.ent = ix.d_ent; a.win_max_tri = ix.d_win_max_tri; a.win_min_tri = tab[i].win_min_tri;
+    a.ntri_of_rank = tab[i].ntri_of_rank; a.ref_of_rank = ix.d_ref_of_rank; a.weight_of_rank = ix.d_weight_of_rank;
+    a.tomb = tomb[i]; a.n_windows = ix.n_windows; a.n_refs = ix.n_refs; a.dense_min8 = ix.dense_min8; a.per = per_of(ix, nc);
+    a.qcodes = N.codes; a.qoff = N.qoff + s; a.q_ntri = N.ntri + s; a.q_base = uint32_t(s); a.n = uint32_t(nc);
+    a.limit = limit; a.min_permille = min_permille; a.all = all;
+    return a;
+  };
+  auto tasks_of = [&](uint32_t i, size_t nc) {
+    const uint32_t per = per_of(*img[i], nc);
+    return (img[i]->n_windows + per - 1u) / per;
+  };
+  // the rows of a chunk, written on the device and copied out
+  auto rows_out = [&](size_t s, size_t nc, trigram_match* d_rows, uint32_t** d_rntri, uint32_t** d_cnt) -> int {
+    const size_t rows_bytes = align_up(nc * limit * sizeof(trigram_match_t), 256), rn_bytes = align_up(nc * limit * 4, 256);
+    if (S.b[5].reserve(rows_bytes + rn_bytes + align_up(nc * 4, 256), stream) < 0) return -1;
+    unsigned char* b = static_cast<unsigned char*>(S.b[5].p);
+    *d_rows = reinterpret_cast<trigram_match>(b);
+    *d_rntri = row_ntri ? reinterpret_cast<uint32_t*>(b + rows_bytes) : nullptr;
+    *d_cnt = reinterpret_cast<uint32_t*>(b + rows_bytes + rn_bytes);
+    BLURRILY_HIP_TRY(hipMemsetAsync(b, 0, rows_bytes + rn_bytes + nc * 4, stream));
+    (void)s;
+    return 0;
+  };
+  auto copy_out = [&](size_t s, size_t nc, trigram_match d_rows, const uint32_t* d_rntri, const uint32_t* d_cnt) -> int {
+    BLURRILY_HIP_TRY(hipMemcpyAsync(counts + s, d_cnt, nc * 4, hipMemcpyDeviceToHost, stream));
+    BLURRILY_HIP_TRY(hipMemcpyAsync(results + s * limit, d_rows, nc * limit * sizeof(trigram_match_t), hipMemcpyDeviceToHost, stream));
+    if (row_ntri) BLURRILY_HIP_TRY(hipMemcpyAsync(row_ntri + s * limit, d_rntri, nc * limit * 4, hipMemcpyDeviceToHost, stream));
+    BLURRILY_HIP_TRY(hipStreamSynchronize(stream));
+    return 0;
+  };
+
+  if (!all) {
+    // list mode: every workgroup's best `limit` rows, then per needle the best `limit` of its lists in both images
+    size_t s = 0;
+    while (s < n) {
+      size_t nc = std::min(kSimChunkNeedles, n - s);
+      auto keys_of = [&](size_t c) {
+        uint64_t k = 0;
+        for (uint32_t i = 0; i < n_img; ++i) k += uint64_t(c) * tasks_of(i, c) * limit;
+        return k;
+      };
+      while (nc > 1 && keys_of(nc) > kSimChunkKeys) nc = (nc + 1) / 2;
+      uint32_t tasks[2] = {0, 0};
+      std::vector<uint32_t> h_off[2];
+      size_t key_bytes = 0, off_bytes = 0;
+      for (uint32_t i = 0; i < n_img; ++i) {
+        tasks[i] = tasks_of(i, nc);
+        h_off[i].resize(nc + 1);
+        for (size_t q = 0; q <= nc; ++q) h_off[i][q] = uint32_t(q * tasks[i] * limit);
+        key_bytes += align_up(size_t(h_off[i][nc]) * sizeof(SimilarKey), 256);
+        off_bytes += align_up((nc + 1) * 4, 256);
+      }
+      if (S.b[1].reserve(key_bytes, stream) < 0 || S.b[2].reserve(key_bytes, stream) < 0 ||
+          S.b[3].reserve(off_bytes, stream) < 0)
+        return -1;
+      SimilarKey* keys[2] = {static_cast<SimilarKey*>(S.b[1].p), nullptr};
+      SimilarKey* sorted[2] = {static_cast<SimilarKey*>(S.b[2].p), nullptr};
+      uint32_t* d_off[2] = {static_cast<uint32_t*>(S.b[3].p), nullptr};
+      if (n_img > 1) {
+        const size_t k0 = align_up(size_t(h_off[0][nc]) * sizeof(SimilarKey), 256);
+        keys[1] = reinterpret_cast<SimilarKey*>(static_cast<unsigned char*>(S.b[1].p) + k0);
+        sorted[1] = reinterpret_cast<SimilarKey*>(static_cast<unsigned char*>(S.b[2].p) + k0);
+        d_off[1] = d_off[0] + align_up((nc + 1) * 4, 256) / 4;
+      }
+      BLURRILY_HIP_TRY(hipMemsetAsync(S.b[1].p, 0xFF, key_bytes, stream));   // (kSimNone: no row)
+      bool need_sort[2] = {false, false};
+      for (uint32_t i = 0; i < n_img; ++i) {
+        BLURRILY_HIP_TRY(hipMemcpyAsync(d_off[i], h_off[i].data(), (nc + 1) * 4, hipMemcpyHostToDevice, stream));
+        SimilarArgs a = args_of(i, s, nc);
+        a.keys = keys[i];
+        if (launch_similar_sweep(a, stream) < 0) return -1;
+        need_sort[i] = tasks[i] > 1;                          // (one list a needle: sorted already)
+      }
+      trigram_match d_rows;
+      uint32_t *d_rntri, *d_cnt;
+      if (rows_out(s, nc, &d_rows, &d_rntri, &d_cnt) < 0) return -1;
+      if (similar_finish(n_img, keys, sorted, d_off, h_off, need_sort, nc, limit, S, d_rows, d_rntri, d_cnt, stream) < 0)
+        return -1;
+      if (copy_out(s, nc, d_rows, d_rntri, d_cnt) < 0) return -1;
+      s += nc;
+    }
+    return 0;
+  }
+
+  // all mode: count every needle's rows at or above the floor, then write, sort and cut them in chunks
+  if (S.b[0].reserve(std::max<size_t>(size_t(n_img) * n * 4, 16), stream) < 0) return -1;
+  uint32_t* d_counts = static_cast<uint32_t*>(S.b[0].p);
+  BLURRILY_HIP_TRY(hipMemsetAsync(d_counts, 0, size_t(n_img) * n * 4, stream));
+  for (uint32_t i = 0; i < n_img; ++i)
+    for (size_t s = 0; s < n; s += kSimChunkNeedles) {
+      SimilarArgs a = args_of(i, s, std::min(kSimChunkNeedles, n - s));
+      a.counts = d_counts + size_t(i) * n + s;
+      if (launch_similar_sweep(a, stream) < 0) return -1;
+    }
+  std::vector<uint32_t> cnt(size_t(n_img) * n);
+  BLURRILY_HIP_TRY(hipMemcpyAsync(cnt.data(), d_counts, cnt.size() * 4, hipMemcpyDeviceToHost, stream));
+  BLURRILY_HIP_TRY(hipStreamSynchronize(stream));
+  size_t s = 0;
+  while (s < n) {
+    auto rows_of = [&](size_t q) { return uint64_t(cnt[q]) + (with_delta ? cnt[n + q] : 0u); };
+    size_t e = s + 1;
+    uint64_t rows = rows_of(s);
+    while (e < n && e - s < kSimChunkNeedles && rows + rows_of(e) <= kSimChunkKeys && (e + 1 - s) * limit <= kSimChunkKeys)
+      rows += rows_of(e++);
+    const size_t nc = e - s;
+    if (rows > 0x7FFFFFFFull) { errno = ENOMEM; return -1; }
+    std::vector<uint32_t> h_off[2];
+    size_t key_bytes = 0;
+    for (uint32_t i = 0; i < n_img; ++i) {
+      h_off[i].resize(nc + 1);
+      h_off[i][0] = 0;
+      for (size_t q = 0; q < nc; ++q) h_off[i][q + 1] = h_off[i][q] + cnt[size_t(i) * n + s + q];
+      key_bytes += align_up(std::max<size_t>(h_off[i][nc], 1) * sizeof(SimilarKey), 256);
+    }
+    const size_t off_bytes = align_up((nc + 1) * 4, 256), cur_bytes = align_up(nc * 4, 256);
+    if (S.b[1].reserve(key_bytes, stream) < 0 || S.b[2].reserve(key_bytes, stream) < 0 ||
+        S.b[3].reserve(n_img * (off_bytes + cur_bytes), stream) < 0)
+      return -1;
+    SimilarKey* keys[2] = {static_cast<SimilarKey*>(S.b[1].p), nullptr};
+    SimilarKey* sorted[2] = {static_cast<SimilarKey*>(S.b[2].p), nullptr};
+    unsigned char* ob = static_cast<unsigned char*>(S.b[3].p);
+    uint32_t* d_off[2] = {reinterpret_cast<uint32_t*>(ob), reinterpret_cast<uint32_t*>(ob + off_bytes)};
+    uint32_t* d_cur = reinterpret_cast<uint32_t*>(ob + n_img * off_bytes);
+    if (n_img > 1) {
+      const size_t k0 = align_up(std::max<size_t>(h_off[0][nc], 1) * sizeof(SimilarKey), 256);
+      keys[1] = reinterpret_cast<SimilarKey*>(static_cast<unsigned char*>(S.b[1].p) + k0);
+      sorted[1] = reinterpret_cast<SimilarKey*>(static_cast<unsigned char*>(S.b[2].p) + k0);
+    }
+    BLURRILY_HIP_TRY(hipMemsetAsync(d_cur, 0, n_img * cur_bytes, stream));
+    bool need_sort[2] = {true, true};
+    for (uint32_t i = 0; i < n_img; ++i) {
+      BLURRILY_HIP_TRY(hipMemcpyAsync(d_off[i], h_off[i].data(), (nc + 1) * 4, hipMemcpyHostToDevice, stream));
+      if (h_off[i][nc] == 0) continue;
+      SimilarArgs a = args_of(i, s, nc);
+      a.counts = d_counts + size_t(i) * n + s;
+      a.seg = d_off[i];
+      a.cursor = d_cur + size_t(i) * (cur_bytes / 4);
+      a.keys = keys[i];
+      if (launch_similar_sweep(a, stream) < 0) return -1;
+    }
+    trigram_match d_rows;
+    uint32_t *d_rntri, *d_cnt;
+    if (rows_out(s, nc, &d_rows, &d_rntri, &d_cnt) < 0) return -1;
+    if (similar_finish(n_img, keys, sorted, d_off, h_off, need_sort, nc, limit, S, d_rows, d_rntri, d_cnt, stream) < 0)
+      return -1;
+    if (copy_out(s, nc, d_rows, d_rntri, d_cnt) < 0) return -1;
+    s = e;
+  }
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int blurrily_storage_find_batch_similar(trigram_map m, const char* packed, const uint64_t* offsets, size_t n,
+                                        uint16_t limit, uint32_t min_permille, trigram_match results, uint32_t* counts,
+                                        uint32_t* row_ntri) {
+  if (!m || !counts || min_permille > 1000 || (n && limit && !results) || (n && (!packed || !offsets)) ||
+      n > 0xFFFFFFF0ull) {
+    errno = EINVAL;
+    return -1;
+  }
+  DeviceScope scope(m->dev.device);
+  hipStream_t stream = nullptr;
+  if (above_ready(m, stream) < 0) return -1;
+  if (n == 0) return 0;
+  if (limit == 0) { std::memset(counts, 0, n * 4); return 0; }
+  NameScope names(&m->last_kernels);
+  m->last_kernels.clear();
+  SimilarScratch S;
+  // the needles up, tokenised by the string path's own front end
+  const size_t packed_bytes = size_t(offsets[n]);
+  const size_t per_n = align_up(n * 4, 256), o_pk = align_up((n + 1) * 8, 256);
+  const size_t o_codes = o_pk + align_up(std::max<size_t>(packed_bytes, 16), 256);
+  const size_t o_ntri = o_codes + align_up((packed_bytes + n) * 2, 256);
+  const size_t bytes = o_ntri + 6 * per_n + 256;
+  if (S.b[6].reserve(bytes, stream) < 0) return -1;
+  unsigned char* b = static_cast<unsigned char*>(S.b[6].p);
+  uint64_t* d_offsets = reinterpret_cast<uint64_t*>(b);
+  char* d_packed = reinterpret_cast<char*>(b + o_pk);
+  uint16_t* d_codes = reinterpret_cast<uint16_t*>(b + o_codes);
+  uint32_t* q = reinterpret_cast<uint32_t*>(b + o_ntri);      // ntri | nb | big | mid | start | (spare) | scalars
+  uint32_t* scalars = reinterpret_cast<uint32_t*>(b + o_ntri + 6 * per_n);
+  BLURRILY_HIP_TRY(hipMemcpyAsync(d_offsets, offsets, (n + 1) * 8, hipMemcpyHostToDevice, stream));
+  if (packed_bytes) BLURRILY_HIP_TRY(hipMemcpyAsync(d_packed, packed, packed_bytes, hipMemcpyHostToDevice, stream));
+  BLURRILY_HIP_TRY(hipMemsetAsync(scalars, 0, 256, stream));
+  const size_t w = per_n / 4;
+  TokeniseArgs t{d_packed, d_offsets, uint32_t(n), m->dev.d_code_total, d_codes, q, q + w, q + 2 * w, scalars,
+                 q + 3 * w, scalars + 1, m->dev.d_start_win, q + 4 * w, 0u};
+  note_launch("tokenise_kernel");
+  if (launch_tokenise(t, stream) < 0) return -1;
+  return similar_run(m, n, AboveNeedles{d_codes, d_offsets, q}, limit, min_permille, results, counts, row_ntri, stream, S);
+}
+
+int blurrily_storage_find_similar(trigram_map m, const char* needle, uint16_t limit, uint32_t min_permille,
+                                  trigram_match results, uint32_t* row_ntri) {
+  if (!needle) { errno = EINVAL; return -1; }
+  const uint64_t offsets[2] = {0, std::strlen(needle)};
+  uint32_t count = 0;
+  if (blurrily_storage_find_batch_similar(m, needle, offsets, 1, limit, min_permille, results, &count, row_ntri) < 0)
+    return -1;
+  return int(count);
+}
+
+int blurrily_storage_find_references_similar(trigram_map m, const uint32_t* references, size_t n, uint16_t limit,
+                                             uint32_t min_permille, trigram_match results, uint32_t* counts,
+                                             uint32_t* row_ntri, uint32_t* nb_trigrams) {
+  if (!m || !counts || min_permille > 1000 || (n && limit && !results) || (n && !references) || n > 0xFFFFFFF0ull) {
+    errno = EINVAL;
+    return -1;
+  }
+  DeviceScope scope(m->dev.device);
+  hipStream_t stream = nullptr;
+  if (above_ready(m, stream) < 0) return -1;
+  if (n == 0) return 0;
+  NameScope names(&m->last_kernels);
+  m->last_kernels.clear();
+  SimilarScratch S;
+  if (S.b[6].reserve(n * 4, stream) < 0) return -1;
+  BLURRILY_HIP_TRY(hipMemcpyAsync(S.b[6].p, references, n * 4, hipMemcpyHostToDevice, stream));
+  RefExtract x;                                                // the by-reference front end (section 11)
+  if (refs_extract(m, static_cast<const uint32_t*>(S.b[6].p), n, stream, &x) < 0) return -1;
+  if (nb_trigrams) {
+    BLURRILY_HIP_TRY(hipMemcpyAsync(nb_trigrams, x.needles.ntri, n * 4, hipMemcpyDeviceToHost, stream));
+    BLURRILY_HIP_TRY(hipStreamSynchronize(stream));
+  }
+  if (limit == 0) { std::memset(counts, 0, n * 4); return 0; }
+  return similar_run(m, n, AboveNeedles{x.needles.codes, x.needles.qoff, x.needles.ntri}, limit, min_permille, results,
+                     counts, row_ntri, stream, S);
+}
+
+}  // extern "C"

@@ -506,6 +506,72 @@ class RawMap:
             np.arange(int(off[-1]), dtype=np.int64)
         return refs[held], off, rows[at]
 
+    # -- similarity find (no reference counterpart): the best rows by trigram Jaccard similarity --------------------
+    @staticmethod
+    def _floor(min_permille):
+        mp = _u32(min_permille, "min_permille")
+        if mp > 1000:
+            raise ValueError(f"min_permille {min_permille!r} above 1000")
+        return mp
+
+    def find_batch_similar_packed(self, packed, offsets, limit, min_permille=0):
+        """The best `limit` rows of each needle by trigram Jaccard similarity J = m / (T + R - m), at or above
+        min_permille / 1000; J descending, then find's order.  Returns (rows[n, limit, 3] uint32, counts[n] uint32,
+        row_ntri[n, limit] uint32: each row's R)."""
+        self._check_open()
+        mp = self._floor(min_permille)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = len(offsets) - 1
+        limit = int(limit) & 0xFFFF
+        rows = np.zeros((n, max(limit, 1), 3), dtype=np.uint32)
+        counts = np.zeros(n, dtype=np.uint32)
+        ntri = np.zeros((n, max(limit, 1)), dtype=np.uint32)
+        buf = np.frombuffer(packed, dtype=np.uint8) if not isinstance(packed, np.ndarray) else packed
+        data = buf.ctypes.data if buf.size else (None if n == 0 else C.addressof(_NO_BYTES))   # (n empty needles)
+        if self._lib.blurrily_storage_find_batch_similar(self._h, data, offsets.ctypes.data, n, limit, mp,
+                                                         rows.ctypes.data, counts.ctypes.data, ntri.ctypes.data) < 0:
+            _raise_errno()
+        return rows[:, :limit, :], counts, ntri[:, :limit]
+
+    def find_similar(self, needle, limit, min_permille=0):
+        """``find_batch_similar_packed`` for one needle: a list of ``[ref, matches, weight, R]``; `limit` as find's."""
+        self._check_open()
+        mp = self._floor(min_permille)
+        limit = int(limit)
+        if not -(1 << 31) <= limit <= _U32_MAX:
+            raise OverflowError("limit out of range")
+        if limit > 0x7FFFFFFF:
+            limit -= 1 << 32
+        if limit <= 0:
+            limit = LIMIT_DEFAULT
+        c_limit = limit & 0xFFFF
+        rows = np.zeros((max(c_limit, 1), 3), dtype=np.uint32)
+        ntri = np.zeros(max(c_limit, 1), dtype=np.uint32)
+        res = self._lib.blurrily_storage_find_similar(self._h, _as_bytes(needle), c_limit, mp, rows.ctypes.data,
+                                                      ntri.ctypes.data)
+        if res < 0:
+            _raise_errno()
+        return [[int(r[0]), int(r[1]), int(r[2]), int(t)] for r, t in zip(rows[:res].tolist(), ntri[:res].tolist())]
+
+    def find_batch_by_reference_similar(self, references, limit, min_permille=0):
+        """``find_batch_similar_packed`` for stored references (each its own row at similarity 1; none for a reference
+        the map does not hold).  Returns (rows[n, limit, 3] uint32, counts[n] uint32, row_ntri[n, limit] uint32,
+        nb_trigrams[n] uint32)."""
+        self._check_open()
+        mp = self._floor(min_permille)
+        refs = self._refs(references)
+        n = len(refs)
+        limit = int(limit) & 0xFFFF
+        rows = np.zeros((n, max(limit, 1), 3), dtype=np.uint32)
+        counts = np.zeros(n, dtype=np.uint32)
+        ntri = np.zeros((n, max(limit, 1)), dtype=np.uint32)
+        nb = np.zeros(n, dtype=np.uint32)
+        if self._lib.blurrily_storage_find_references_similar(self._h, refs.ctypes.data if n else None, n, limit, mp,
+                                                              rows.ctypes.data, counts.ctypes.data, ntri.ctypes.data,
+                                                              nb.ctypes.data) < 0:
+            _raise_errno()
+        return rows[:, :limit, :], counts, ntri[:, :limit], nb
+
     def sync_device(self):
         self._check_open()
         if self._lib.blurrily_storage_sync_device(self._h) < 0:
@@ -752,6 +818,21 @@ class Map(RawMap):
         packed, offsets = _pack([_as_bytes(normalize_string(s)) for s in needles])
         rows, row_off = super().find_batch_above_packed(packed, offsets, min_matches, min_permille)
         return [rows[int(row_off[i]):int(row_off[i + 1])].tolist() for i in range(len(needles))]
+
+    def find_similar(self, needle, limit=LIMIT_DEFAULT, min_permille=0):
+        """The best rows of the normalised needle by trigram Jaccard similarity (``RawMap.find_similar``): a list of
+        ``[ref, matches, weight, R]``."""
+        return super().find_similar(normalize_string(needle), limit, min_permille)
+
+    def find_batch_similar(self, needles, limit=LIMIT_DEFAULT, min_permille=0):
+        """``[self.find_similar(s, limit, min_permille) for s in needles]`` in one GPU batch."""
+        limit = int(limit)
+        if limit <= 0:
+            limit = LIMIT_DEFAULT
+        packed, offsets = _pack([_as_bytes(normalize_string(s)) for s in needles])
+        rows, counts, ntri = super().find_batch_similar_packed(packed, offsets, limit, min_permille)
+        return [[r + [t] for r, t in zip(rows[i, :counts[i]].tolist(), ntri[i, :counts[i]].tolist())]
+                for i in range(len(needles))]
 
     def find_batch(self, needles, limit=LIMIT_DEFAULT):
         """``[self.find(s, limit) for s in needles]`` in one GPU batch."""

@@ -310,6 +310,32 @@ int blurrily_storage_find_references_above(trigram_map haystack, const uint32_t*
                                            trigram_match results, uint64_t capacity, uint64_t* row_off,
                                            uint32_t* nb_trigrams);
 
+/* Similarity find: the best `limit` rows by trigram Jaccard similarity J = m / (T + R - m), with T the needle's
+ * distinct trigrams (as for find), R the reference's (what blurrily_storage_get returns for it now) and m the matches
+ * find reports for the pair.  A reference is a row iff m >= 1 and 1000 * m >= min_permille * (T + R - m) (exact, 64-bit
+ * integers).  Order: J descending (m_a * u_b > m_b * u_a, u = T + R - m: no floating point), then find's order
+ * (matches descending, weight ascending, reference ascending); cut at `limit`.  Dice similarity, 2m / (T + R), is a
+ * monotone function of J: it gives the same rows in the same order.  T == 0 or limit == 0: no rows.  The map is read
+ * as find reads it; with "devices" > 1 the primary device alone serves the call.
+ * 0, or -1 with errno (EINVAL before anything needs a GPU: min_permille > 1000, counts NULL, results NULL with
+ * limit > 0 and n > 0, packed or offsets NULL with n > 0; ENODEV without a usable GPU). */
+/* Top-`limit` rows by trigram Jaccard similarity at or above min_permille / 1000.
+ * results: n * limit rows (needle i owns [i*limit, i*limit + counts[i])); row_ntri (optional, n * limit slots):
+ * each row's R, so the caller can compute the similarity exactly.  0, or -1 with errno. */
+int blurrily_storage_find_batch_similar(trigram_map haystack, const char* packed, const uint64_t* offsets, size_t n,
+                                        uint16_t limit, uint32_t min_permille,
+                                        trigram_match results, uint32_t* counts, uint32_t* row_ntri);
+/* One needle: the row count, or -1 with errno. */
+int blurrily_storage_find_similar(trigram_map haystack, const char* needle, uint16_t limit, uint32_t min_permille,
+                                  trigram_match results, uint32_t* row_ntri);
+/* By stored reference (section 11's front end): element i is find_batch_similar of any string whose tokenisation is
+ * reference i's trigram set; the reference itself is a row with similarity 1 (first unless another reference has the
+ * same set).  Absent reference: 0 rows, nb_trigrams[i] == 0 (nb_trigrams may be NULL).  EINVAL also for references
+ * NULL with n > 0. */
+int blurrily_storage_find_references_similar(trigram_map haystack, const uint32_t* references, size_t n,
+                                             uint16_t limit, uint32_t min_permille, trigram_match results,
+                                             uint32_t* counts, uint32_t* row_ntri, uint32_t* nb_trigrams);
+
 /* Tokeniser (ext/blurrily/tokeniser.h:34, tokeniser.c:59-119): `output` needs
  * strlen(input)+1 slots; returns the number of distinct codes, ascending. */
 int blurrily_tokeniser_parse_string(const char* input, uint16_t* output);

@@ -485,6 +485,37 @@ static VALUE blurrily_find_above(VALUE self, VALUE rb_needle, VALUE rb_min_match
   return out;
 }
 
+/* find_similar(needle, limit, min_permille): the best rows by trigram Jaccard similarity, [[ref, matches, weight, R],
+ * ...]; limit <= 0 means LIMIT_DEFAULT, as for find. */
+static VALUE blurrily_find_similar(VALUE self, VALUE rb_needle, VALUE rb_limit, VALUE rb_min_permille)
+{
+  trigram_map   map = map_of(self);
+  const char*   needle = StringValueCStr(rb_needle);
+  int           limit = (int)NUM2UINT(rb_limit);           /* (as the gem's find: map_ext.c:135) */
+  uint32_t      mp = NUM2UINT(rb_min_permille);
+  uint32_t*     ntri;
+  trigram_match rows;
+  VALUE         out;
+  int           got, k;
+  if (limit <= 0) limit = 10;
+  if (limit > 0xFFFF) limit = 0xFFFF;
+  rows = ALLOC_N(trigram_match_t, limit);
+  ntri = ALLOC_N(uint32_t, limit);
+  got = blurrily_storage_find_similar(map, needle, (uint16_t)limit, mp, rows, ntri);
+  if (got < 0) {
+    xfree(rows);
+    xfree(ntri);
+    rb_sys_fail("blurrily_storage_find_similar");
+  }
+  out = rb_ary_new2(got);
+  for (k = 0; k < got; ++k)
+    rb_ary_push(out, rb_ary_new3(4, rb_uint_new(rows[k].reference), rb_uint_new(rows[k].matches),
+                                 rb_uint_new(rows[k].weight), rb_uint_new(ntri[k])));
+  xfree(rows);
+  xfree(ntri);
+  return out;
+}
+
 static VALUE blurrily_set_option(VALUE self, VALUE rb_key, VALUE rb_value)
 {
   if (blurrily_storage_set_option(map_of(self), StringValueCStr(rb_key), NUM2LL(rb_value)) < 0)
@@ -524,4 +555,5 @@ void Init_map_ext(void)
   rb_define_method(cRawMap, "find_among",     blurrily_find_among,     3);
   rb_define_method(cRawMap, "find_batch_among", blurrily_find_batch_among, 4);
   rb_define_method(cRawMap, "find_above",     blurrily_find_above,     3);
+  rb_define_method(cRawMap, "find_similar",   blurrily_find_similar,   3);
 }

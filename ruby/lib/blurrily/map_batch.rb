@@ -32,6 +32,13 @@ module Blurrily
       put_many(needles.map { |n| normalize_string(n) }, references, weights)
     end
 
+    # The best rows of the normalised needle by trigram Jaccard similarity at or above min_permille / 1000:
+    # [[ref, matches, weight, R], ...], R the reference's distinct trigrams (RawMap#find_similar; limit <= 0 means
+    # LIMIT_DEFAULT, as for find).
+    def find_similar(needle, limit = LIMIT_DEFAULT, min_permille = 0)
+      super(normalize_string(needle), limit, min_permille)
+    end
+
     # Replicate the device image on the first `n` visible GPUs and shard every later find_batch over them
     # (include/blurrily_storage.h, "devices").  The answer does not depend on n.
     def devices=(n)
