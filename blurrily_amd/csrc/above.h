@@ -8,6 +8,7 @@
 
 #include "../../include/blurrily_storage.h"
 #include "device_index.h"
+#include "segsort.h"
 
 namespace blurrily {
 
@@ -39,28 +40,22 @@ struct AboveArgs {
 };
 int launch_above_sweep(const AboveArgs& a, hipStream_t stream);
 
-// Sorting a chunk's key segments ascending (keys are distinct within a segment: the rank is in the low bits).
-// launch_above_tiles: every tile of at most kAboveTile keys, in[start, start + len), sorted into out[start, ...] in LDS
-// (a segment is cut into tiles of kAboveTile keys from its start).  launch_above_merge: one pass over the segments
-// longer than a tile -- every pair of sorted runs of `width` keys merged from in to out (a run without a partner is
-// copied); elem_off [n_segs + 1] is the exclusive scan of seg_len.
+// Sorting a chunk's key segments ascending (segsort.h; keys are distinct within a segment: the rank is in the low bits).
 constexpr uint32_t kAboveTile = 4096;
-struct AboveTile {
-  uint32_t start, len;
-};
-int launch_above_tiles(const AboveTile* tiles, uint32_t n_tiles, const unsigned long long* in, unsigned long long* out,
+int launch_above_tiles(const SegTile* tiles, uint32_t n_tiles, const unsigned long long* in, unsigned long long* out,
                        hipStream_t stream);
-struct AboveMergeArgs {
-  const uint32_t*           seg_start;
-  const uint32_t*           seg_len;
-  const uint32_t*           elem_off;
-  uint32_t                  n_segs;
-  uint32_t                  n_elems;
-  uint32_t                  width;
-  const unsigned long long* in;
-  unsigned long long*       out;
+int launch_above_merge(const SegMergeArgs<unsigned long long>& a, hipStream_t stream);
+template <>
+struct SegKey<unsigned long long> {
+  static constexpr uint32_t kTile = kAboveTile;
+  static int tiles(const SegTile* t, uint32_t n, const unsigned long long* in, unsigned long long* out, hipStream_t s) {
+    return launch_above_tiles(t, n, in, out, s);
+  }
+  static int merge(const SegMergeArgs<unsigned long long>& a, hipStream_t s) { return launch_above_merge(a, s); }
+#ifdef __HIPCC__
+  __device__ static bool less(unsigned long long a, unsigned long long b) { return a < b; }
+#endif
 };
-int launch_above_merge(const AboveMergeArgs& a, hipStream_t stream);
 
 // Rows from the sorted keys of up to two images (base, delta: disjoint references), merged per needle in result
 // order: needle q's rows at rows + off[0][q] + off[1][q], off[1][q + 1] - off[1][q] of them from the delta image.

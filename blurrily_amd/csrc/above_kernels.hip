@@ -8,26 +8,13 @@
 // bitmaps about itself, and is a row when its total reaches t and it is not deleted.  The same launch counts a
 // needle's rows (count pass) or writes its keys (emit pass, into the segment the count pass sized).
 // Each needle's keys are then sorted (above_tiles_kernel: bitonic sort of up to kAboveTile keys in LDS;
-// above_merge_kernel: merge passes over the few segments longer than a tile), and above_rows_kernel merges the base
+// segsort.h's seg_merge_kernel: merge passes over the few segments longer than a tile), and above_rows_kernel merges the base
 // and delta images' rows per needle.
 #include "above.h"
-
-#include <cerrno>
-#include <cstdio>
-
-#define BLURRILY_HIP_TRY(expr)                                                        \
-  do {                                                                                \
-    hipError_t e_ = (expr);                                                           \
-    if (e_ != hipSuccess) {                                                           \
-      std::fprintf(stderr, "blurrily_hip: %s failed: %s\n", #expr, hipGetErrorString(e_)); \
-      errno = (e_ == hipErrorOutOfMemory) ? ENOMEM : EIO;                             \
-      return -1;                                                                      \
-    }                                                                                 \
-  } while (0)
+#include "find_kernels.h"
+#include "hip_try.h"
 
 namespace blurrily {
-
-void note_launch(const char* kernel_name);   // (c_abi.hip: the map's last_kernels)
 
 namespace {
 
@@ -178,10 +165,10 @@ __global__ __launch_bounds__(kAboveThreads) void above_sweep_kernel(AboveArgs a)
 }
 
 // one tile per workgroup: bitonic sort over the next power of two at or above its length, padded with ~0
-__global__ __launch_bounds__(256) void above_tiles_kernel(const AboveTile* tiles, const unsigned long long* in,
+__global__ __launch_bounds__(256) void above_tiles_kernel(const SegTile* tiles, const unsigned long long* in,
                                                           unsigned long long* out) {
   __shared__ unsigned long long s[kAboveTile];
-  const AboveTile tl = tiles[blockIdx.x];
+  const SegTile tl = tiles[blockIdx.x];
   uint32_t P = 1;
   while (P < tl.len) P <<= 1;
   for (uint32_t i = threadIdx.x; i < P; i += 256u) s[i] = i < tl.len ? in[size_t(tl.start) + i] : ~0ull;
@@ -198,31 +185,6 @@ __global__ __launch_bounds__(256) void above_tiles_kernel(const AboveTile* tiles
       __syncthreads();
     }
   for (uint32_t i = threadIdx.x; i < tl.len; i += 256u) out[size_t(tl.start) + i] = s[i];
-}
-
-// one thread per key of the long segments: its place in the merge of its run with the partner run
-__global__ __launch_bounds__(256) void above_merge_kernel(AboveMergeArgs a) {
-  const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= a.n_elems) return;
-  uint32_t lo = 0, hi = a.n_segs;                             // the segment: the last k with elem_off[k] <= e
-  while (hi - lo > 1u) {
-    const uint32_t mid = (lo + hi) / 2u;
-    if (a.elem_off[mid] <= e) lo = mid; else hi = mid;
-  }
-  const uint32_t base = a.seg_start[lo], len = a.seg_len[lo], i = e - a.elem_off[lo];
-  const uint32_t b = i / a.width, p = b ^ 1u;
-  const unsigned long long x = a.in[size_t(base) + i];
-  uint32_t rank = 0;
-  if (size_t(p) * a.width < len) {
-    uint32_t f = p * a.width, l = min(len, f + a.width);
-    const uint32_t first = f;
-    while (f < l) {                                           // partner keys below x (keys are distinct)
-      const uint32_t mid = (f + l) / 2u;
-      if (a.in[size_t(base) + mid] < x) f = mid + 1u; else l = mid;
-    }
-    rank = f - first;
-  }
-  a.out[size_t(base) + min(b, p) * a.width + (i - b * a.width) + rank] = x;
 }
 
 // result order of two rows: matches descending, weight ascending, reference ascending
@@ -274,7 +236,7 @@ int launch_above_sweep(const AboveArgs& a, hipStream_t stream) {
   return 0;
 }
 
-int launch_above_tiles(const AboveTile* tiles, uint32_t n_tiles, const unsigned long long* in, unsigned long long* out,
+int launch_above_tiles(const SegTile* tiles, uint32_t n_tiles, const unsigned long long* in, unsigned long long* out,
                        hipStream_t stream) {
   if (n_tiles == 0) return 0;
   note_launch("above_tiles_kernel");
@@ -283,10 +245,10 @@ int launch_above_tiles(const AboveTile* tiles, uint32_t n_tiles, const unsigned 
   return 0;
 }
 
-int launch_above_merge(const AboveMergeArgs& a, hipStream_t stream) {
+int launch_above_merge(const SegMergeArgs<unsigned long long>& a, hipStream_t stream) {
   if (a.n_elems == 0) return 0;
   note_launch("above_merge_kernel");
-  hipLaunchKernelGGL(above_merge_kernel, dim3((a.n_elems + 255u) / 256u), dim3(256), 0, stream, a);
+  hipLaunchKernelGGL(seg_merge_kernel<unsigned long long>, dim3((a.n_elems + 255u) / 256u), dim3(256), 0, stream, a);
   BLURRILY_HIP_TRY(hipGetLastError());
   return 0;
 }

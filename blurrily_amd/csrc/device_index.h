@@ -83,7 +83,7 @@ struct DeviceIndex {
   uint32_t* d_code_total     = nullptr;   // [kNumCodes]
   uint32_t* d_win_max_tri    = nullptr;   // [n_windows] most postings any one reference of the window has
   uint32_t* d_start_win      = nullptr;   // [256] window holding the first rank whose weight is >= the index
-  uint32_t  h_start_win[256] = {};        //       ... the host's copy (needles tokenised on the host: c_abi.hip, find_few)
+  uint32_t  h_start_win[256] = {};        //       ... the host's copy (needles tokenised on the host: host_batch.hip, find_few)
   uint32_t* d_tomb           = nullptr;   // [(n_refs+31)/32] bit r: rank r was deleted after the build
   uint32_t  n_bitmaps        = 0;         // dense slices (each starts with its bitmap, inline in d_ent)
   uint32_t  dense_min8       = 0;         // a slice spanning at least this many entries is dense (a multiple of 8)
@@ -91,7 +91,7 @@ struct DeviceIndex {
   // postings a needle's trigram finds in one window, on average, when needle trigrams are distributed
   // like the haystack's postings: (sum of used[t]^2 / sum of used[t]) / n_windows.  The window-major
   // sweep pays a fixed price per (needle, window) and saves in proportion to the postings it leaves
-  // out, so it is taken only where slices are big (c_abi.hip).
+  // out, so it is taken only where slices are big (find_run.hip).
   double    mean_hit_slice   = 0.0;
   // share of those postings that sit in slices of at least dense_min postings -- the ones the window-major sweep
   // can leave out of the count: sum of len^2 over dense (window, code) slices / over all slices
@@ -110,14 +110,14 @@ struct DeviceIndex {
 };
 
 // How an image is built and which of them the window-major sweep may be taken on (blurrily_storage_set_option;
-// c_abi.hip holds the per-map copy).  Every image carries the bitmaps of its dense slices (Geonames scale: 17 k of
+// map_internal.h holds the per-map copy).  Every image carries the bitmaps of its dense slices (Geonames scale: 17 k of
 // them, 143 MB, inline in `ent`).
 struct IndexBuildOptions {
   bool     ws_enabled     = true;
   uint32_t ws_min_windows = 8;      // fewer windows: the needle-major sweep is taken whatever the batch
   uint32_t ws_min_slice   = 1550;   // least DeviceIndex::mean_hit_slice of an image the sweep may be taken on at all:
                                     // below it the sweep lost on every haystack measured; above
-                                    // it c_abi.hip MEASURES the choice per class of batch on first use
+                                    // it find_run.hip MEASURES the choice per class of batch on first use
   uint32_t dense_min      = kDenseMin;
   bool ws_can_run(uint32_t n_windows, double mean_hit_slice) const {
     return ws_enabled && n_windows >= ws_min_windows && mean_hit_slice >= double(ws_min_slice);

@@ -1,5 +1,6 @@
 // device_index.hip -- build and upload the HBM-resident index (device_index.h).
 #include "device_index.h"
+#include "hip_try.h"
 
 #include <hip/hip_runtime.h>
 
@@ -16,16 +17,6 @@
 namespace blurrily {
 
 namespace {
-
-#define BLURRILY_HIP_TRY(expr)                                                        \
-  do {                                                                                \
-    hipError_t e_ = (expr);                                                           \
-    if (e_ != hipSuccess) {                                                           \
-      std::fprintf(stderr, "blurrily_hip: %s failed: %s\n", #expr, hipGetErrorString(e_)); \
-      errno = (e_ == hipErrorOutOfMemory) ? ENOMEM : EIO;                             \
-      return -1;                                                                      \
-    }                                                                                 \
-  } while (0)
 
 // Sorted view of a bucket: the bucket itself when already ascending, else a
 // sorted scratch copy (the host bucket is left untouched: only find() and

@@ -128,7 +128,7 @@ enum : uint32_t {
   kStatAllSlots       = 16,
 };
 
-// Every find-kernel launch notes its name here (c_abi.hip keeps, per map, the kernels of the last batch's short-needle
+// Every find-kernel launch notes its name here (c_abi.hip: note_launch keeps, per map, the kernels of the last batch's short-needle
 // launches in launch order: blurrily_storage_last_kernels -- what a bench line names instead of guessing).
 void note_launch(const char* kernel_name);
 

@@ -34,6 +34,7 @@
 //                     third sort key, not a property of libc's qsort.
 // All arithmetic is integer; results are bit-exact.
 #include "find_kernels.h"
+#include "hip_try.h"
 
 #include <hip/hip_runtime.h>
 
@@ -165,16 +166,6 @@ size_t find_lds_bytes(size_t counter_bytes, uint32_t pool_cap) {
 }  // namespace
 
 // ------------------------------------------------------------------ launch ---
-
-#define BLURRILY_HIP_TRY(expr)                                                        \
-  do {                                                                                \
-    hipError_t e_ = (expr);                                                           \
-    if (e_ != hipSuccess) {                                                           \
-      std::fprintf(stderr, "blurrily_hip: %s failed: %s\n", #expr, hipGetErrorString(e_)); \
-      errno = (e_ == hipErrorOutOfMemory) ? ENOMEM : EIO;                             \
-      return -1;                                                                      \
-    }                                                                                 \
-  } while (0)
 
 // by reference (blurrily_storage_get / _find_references) and scoped find: no counted build of these
 #ifndef BLURRILY_COUNTED

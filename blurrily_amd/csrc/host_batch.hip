@@ -1,0 +1,512 @@
+// host_batch.hip -- host-buffer batches: the chunked three-stream pipeline, the one-piece batch through pinned
+// staging, and a handful of needles (or ONE, the caller waiting) in one launch without copies (find_few).
+#include "map_internal.h"
+
+using namespace blurrily;
+using namespace blurrily::detail;
+
+constexpr size_t kStageBytes = 1 << 20;   // pinned staging per direction for small host-buffer batches
+
+// A large host-buffer batch in chunks through three streams: while chunk k is searched (s_run), chunk k+1's
+// needles travel to the device (s_in) and chunk k-1's rows travel back (s_out) -- both through pinned staging,
+// which the host fills / drains meanwhile.  Two slots by turns; a slot is reused only after its rows have been
+// copied out to the caller.  Each element is still exactly one blurrily_storage_find.
+static int find_batch_chunked_run(trigram_map m, const char* packed, const uint64_t* offsets, size_t n, uint16_t limit,
+                              trigram_match results, uint32_t* counts, bool raw, uint32_t* non_ascii, size_t chunk) {
+  auto& P = m->pipe;
+  if (!P.s_in) {
+    for (hipStream_t* s : {&P.s_in, &P.s_run, &P.s_out}) BLURRILY_HIP_TRY(hipStreamCreateWithFlags(s, hipStreamNonBlocking));
+    for (int i = 0; i < 2; ++i)
+      for (hipEvent_t* e : {&P.ev_in[i], &P.ev_run[i], &P.ev_out[i]})
+        BLURRILY_HIP_TRY(hipEventCreateWithFlags(e, hipEventDisableTiming));
+  }
+  // staging sizes: the largest chunk's bytes in (rebased offsets | needles) and out (counts | flags | rows)
+  size_t max_packed = 0;
+  for (size_t a = 0; a < n; a += chunk) {
+    const size_t b = std::min(n, a + chunk);
+    max_packed = std::max<size_t>(max_packed, size_t(offsets[b] - offsets[a]));
+  }
+  const size_t off_cap = align_up((chunk + 1) * sizeof(uint64_t), 256);
+  const size_t cnt_cap = align_up(chunk * sizeof(uint32_t), 256);
+  const size_t flag_cap = raw ? cnt_cap : 0;
+  const size_t in_cap = off_cap + std::max<size_t>(max_packed, 16);
+  const size_t out_cap = cnt_cap + flag_cap + std::max<size_t>(chunk * size_t(limit) * sizeof(trigram_match_t), 16);
+  if (P.h_in_bytes < in_cap || P.h_out_bytes < out_cap) {
+    BLURRILY_HIP_TRY(hipDeviceSynchronize());
+    for (int i = 0; i < 2; ++i) {
+      if (P.h_in[i]) (void)hipHostFree(P.h_in[i]);
+      if (P.h_out[i]) (void)hipHostFree(P.h_out[i]);
+      P.h_in[i] = P.h_out[i] = nullptr;
+    }
+    P.h_in_bytes = P.h_out_bytes = 0;
+    for (int i = 0; i < 2; ++i) {
+      BLURRILY_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&P.h_in[i]), in_cap));
+      BLURRILY_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&P.h_out[i]), out_cap));
+    }
+    P.h_in_bytes = in_cap; P.h_out_bytes = out_cap;
+  }
+  for (int i = 0; i < 2; ++i)
+    if (P.d_in[i].reserve(in_cap, P.s_run) < 0 || P.d_out[i].reserve(out_cap, P.s_run) < 0) return -1;
+
+  struct Span { size_t a, b; };
+  Span in_slot[2] = {{0, 0}, {0, 0}};
+  // rows of the chunk slot `i` holds, from pinned staging to the caller's buffers (behind its D2H)
+  auto drain = [&](int i) -> int {
+    const Span sp = in_slot[i];
+    if (sp.b == sp.a) return 0;
+    BLURRILY_HIP_TRY(hipEventSynchronize(P.ev_out[i]));
+    const size_t c = sp.b - sp.a;
+    std::memcpy(counts + sp.a, P.h_out[i], c * sizeof(uint32_t));
+    if (raw && non_ascii) std::memcpy(non_ascii + sp.a, P.h_out[i] + cnt_cap, c * sizeof(uint32_t));
+    if (limit)
+      std::memcpy(results + sp.a * size_t(limit), P.h_out[i] + cnt_cap + flag_cap, c * size_t(limit) * sizeof(trigram_match_t));
+    in_slot[i] = {0, 0};
+    return 0;
+  };
+  size_t k = 0;
+  for (size_t a = 0; a < n; a += chunk, ++k) {
+    const size_t b = std::min(n, a + chunk), c = b - a;
+    const int i = int(k & 1);
+    if (drain(i) < 0) return -1;                                  // chunk k-2: its staging and device blocks are free again
+    // ---- stage chunk k: offsets rebased to the chunk, its needles; how long they can be --------------
+    uint64_t* h_off = reinterpret_cast<uint64_t*>(P.h_in[i]);
+    const uint64_t base = offsets[a];
+    size_t max_len = 0;
+    for (size_t j = 0; j <= c; ++j) h_off[j] = offsets[a + j] - base;
+    const size_t bytes = size_t(offsets[b] - base);
+    if (bytes) std::memcpy(P.h_in[i] + off_cap, packed + base, bytes);
+    for (size_t j = 0; j < c && max_len <= 126; ++j) {            // (what the launches need to know: > 63, > 126)
+      const size_t cap = size_t(h_off[j + 1] - h_off[j]);
+      if (cap <= max_len) continue;
+      const char* s = packed + base + h_off[j];
+      const void* nul = std::memchr(s, 0, cap);
+      max_len = std::max(max_len, nul ? size_t(static_cast<const char*>(nul) - s) : cap);
+    }
+    unsigned char* d_in = static_cast<unsigned char*>(P.d_in[i].p);
+    unsigned char* d_out = static_cast<unsigned char*>(P.d_out[i].p);
+    BLURRILY_HIP_TRY(hipMemcpyAsync(d_in, P.h_in[i], off_cap + std::max<size_t>(bytes, 16), hipMemcpyHostToDevice, P.s_in));
+    BLURRILY_HIP_TRY(hipEventRecord(P.ev_in[i], P.s_in));
+    // ---- search it ---------------------------------------------------------------------------------
+    BLURRILY_HIP_TRY(hipStreamWaitEvent(P.s_run, P.ev_in[i], 0));
+    const uint64_t* d_offsets = reinterpret_cast<const uint64_t*>(d_in);
+    char* d_packed = reinterpret_cast<char*>(d_in + off_cap);
+    uint32_t* d_counts = reinterpret_cast<uint32_t*>(d_out);
+    uint32_t* d_flags = reinterpret_cast<uint32_t*>(d_out + cnt_cap);
+    trigram_match d_rows = reinterpret_cast<trigram_match>(d_out + cnt_cap + flag_cap);
+    if (raw && launch_normalise(d_packed, d_offsets, uint32_t(c), d_packed, d_flags, P.s_run) < 0) return -1;
+    if (run_find(m, d_packed, bytes, d_offsets, c, limit, d_rows, d_counts, nullptr, max_len > 126, max_len > 63,
+                 P.s_run) < 0)
+      return -1;
+    BLURRILY_HIP_TRY(hipEventRecord(P.ev_run[i], P.s_run));
+    // ---- and send its rows home ----------------------------------------------------------------------
+    BLURRILY_HIP_TRY(hipStreamWaitEvent(P.s_out, P.ev_run[i], 0));
+    BLURRILY_HIP_TRY(hipMemcpyAsync(P.h_out[i], d_out, cnt_cap + flag_cap + c * size_t(limit) * sizeof(trigram_match_t),
+                                    hipMemcpyDeviceToHost, P.s_out));
+    BLURRILY_HIP_TRY(hipEventRecord(P.ev_out[i], P.s_out));
+    in_slot[i] = {a, b};
+  }
+  if (drain(int(k & 1)) < 0 || drain(int((k + 1) & 1)) < 0) return -1;
+  return 0;
+}
+
+static int find_batch_chunked(trigram_map m, const char* packed, const uint64_t* offsets, size_t n, uint16_t limit,
+                              trigram_match results, uint32_t* counts, bool raw, uint32_t* non_ascii, size_t chunk) {
+  m->class_hint = n;
+  const int rc = find_batch_chunked_run(m, packed, offsets, n, limit, results, counts, raw, non_ascii, chunk);
+  m->class_hint = 0;
+  if (rc < 0) {                                       // chunks may still be in flight on the three streams: let them
+    const int e = errno;                              // finish before anybody reuses the slots
+    (void)hipDeviceSynchronize();
+    errno = e;
+  }
+  return rc;
+}
+
+// Blurrily::Map#normalize_string (lib/blurrily/map.rb:40-47) for ONE ASCII needle on the host -- normalise_kernel's two
+// passes, byte for byte (kernels/tokenise.inc: downcase; unless some line is [a-z ]+ every byte that is not a-z becomes a
+// space; whitespace runs squeezed, both ends stripped, trailing NULs too): a handful of raw needles is normalised here
+// and shares find_one_kernel's launch instead of paying a copy in, a normalising launch and the batch's way.  `out` holds
+// at least `cap` bytes; returns the normalised length (up to the first NUL: where the tokeniser stops); *high: whether
+// the needle held a byte >= 0x80 (flagged, not guessed: NFKD is the caller's).
+size_t normalise_one(const char* in, size_t cap, char* out, uint32_t* high_out) {
+  bool plain = false, line_ok = true;
+  size_t line_len = 0;
+  uint32_t high = 0;
+  for (size_t k = 0; k < cap; ++k) {
+    unsigned char c = static_cast<unsigned char>(in[k]);
+    high |= c >> 7;
+    if (c == '\n') { plain |= line_ok && line_len > 0; line_ok = true; line_len = 0; continue; }
+    if (c >= 'A' && c <= 'Z') c += 'a' - 'A';
+    line_ok &= (c >= 'a' && c <= 'z') || c == ' ';
+    ++line_len;
+  }
+  plain |= line_ok && line_len > 0;
+  size_t w = 0, keep = 0;
+  bool gap = false;
+  for (size_t k = 0; k < cap; ++k) {
+    unsigned char c = static_cast<unsigned char>(in[k]);
+    if (c >= 'A' && c <= 'Z') c += 'a' - 'A';
+    const bool letter = c >= 'a' && c <= 'z';
+    if (!plain && !letter) c = ' ';
+    if (c == ' ' || (c >= '\t' && c <= '\r')) { gap = true; continue; }
+    if (gap && w > 0) out[w++] = ' ';
+    gap = false;
+    out[w++] = static_cast<char>(c);
+    if (c != 0) keep = w;
+  }
+  if (high_out) *high_out = high;
+  const void* nul = std::memchr(out, 0, keep);
+  return nul ? size_t(static_cast<const char*>(nul) - out) : keep;
+}
+
+namespace blurrily {
+namespace detail {
+
+// Host-buffer batch: needles in, rows out.  raw = the needles are un-normalised ASCII (see
+// blurrily_storage_find_batch_raw); non_ascii (raw only, may be null) receives the per-needle flags.
+int find_batch_host(trigram_map m, const char* packed, const uint64_t* offsets, size_t n, uint16_t limit,
+                    trigram_match results, uint32_t* counts, bool raw, uint32_t* non_ascii) {
+  if (n == 0) return 0;
+  if (n <= std::max(m->one.few_max, m->one.mid_max)) { // a handful of needles: no copies (find_few; options "few_max", "mid_max")
+    const char* s[kMidMaxNeedles];
+    size_t len[kMidMaxNeedles];
+    std::vector<char> norm;                             // raw needles: normalised here, as normalise_kernel would
+    bool fits = true;
+    if (raw) {
+      if (offsets[n] - offsets[0] > (1u << 16)) fits = false;      // (a handful of very long needles: the batch's way)
+      else norm.resize(size_t(offsets[n] - offsets[0]) + 1);
+    }
+    for (size_t i = 0; fits && i < n; ++i) {
+      const size_t cap = size_t(offsets[i + 1] - offsets[i]);
+      if (raw) {
+        char* out = norm.data() + (offsets[i] - offsets[0]);
+        uint32_t high = 0;
+        len[i] = normalise_one(packed + offsets[i], cap, out, &high);
+        s[i] = out;
+        if (non_ascii) non_ascii[i] = high;
+      } else {
+        s[i] = packed + offsets[i];
+        const void* nul = std::memchr(s[i], 0, cap);
+        len[i] = nul ? size_t(static_cast<const char*>(nul) - s[i]) : cap;
+      }
+    }
+    if (fits) {
+      const int few = find_few(m, s, len, n, limit, results, counts);
+      if (few != kOneNotTaken) return few;
+    }
+  }
+  DeviceScope scope(m->dev.device);
+  // what the reference's find does first: tokenise, sort the needle's dirty buckets
+  size_t max_len = 0;
+  const bool any_dirty = m->host->dirty_buckets() != 0;
+  std::vector<uint16_t> codes;
+  for (size_t i = 0; i < n; ++i) {
+    const char* s = packed + offsets[i];
+    const size_t cap = size_t(offsets[i + 1] - offsets[i]);
+    const void* nul = std::memchr(s, 0, cap);
+    const size_t len = nul ? size_t(static_cast<const char*>(nul) - s) : cap;
+    max_len = std::max(max_len, len);
+    if (any_dirty && !raw) {
+      codes.resize(len + 1);
+      const int nt = tokenise(s, len, codes.data());
+      for (int k = 0; k < nt; ++k) m->host->sort_bucket_if_dirty(codes[k]);
+    }
+  }
+  // (raw needles are only normalised on the device: sort every dirty bucket, as the device entry does)
+  if (any_dirty && raw) m->host->sort_dirty_buckets();
+  if (ensure_device(m) < 0) return -1;
+  if (m->timing && !m->ev[0])
+    for (auto& e : m->ev) BLURRILY_HIP_TRY(hipEventCreate(&e));
+  // (timing and request counters describe ONE launch sequence: those runs stay in one piece)
+  const bool multi = wants_multi(m, n);   // (the batch then goes in one piece through the primary: its rows come home over ONE PCIe link)
+  if (!multi && m->host_chunk && n >= 2 * size_t(m->host_chunk) && !m->timing && !m->collect_stats) {
+    size_t chunk = m->host_chunk;
+    const size_t row_cap = size_t(32) << 20;                      // at most 32 MiB of rows per chunk in pinned staging
+    while (chunk > 1024 && chunk * size_t(limit) * sizeof(trigram_match_t) > row_cap) chunk >>= 1;
+    return find_batch_chunked(m, packed, offsets, n, limit, results, counts, raw, non_ascii, chunk);
+  }
+
+  hipStream_t stream = nullptr;
+  const size_t packed_bytes = size_t(offsets[n]);
+  const size_t off_bytes = (n + 1) * sizeof(uint64_t);
+  const size_t row_bytes = n * size_t(limit) * sizeof(trigram_match_t);
+  const size_t cnt_bytes = n * sizeof(uint32_t);
+  // one device block in ([offsets | needles]) and one out ([counts | rows])
+  const size_t in_bytes = align_up(off_bytes, 256) + std::max<size_t>(packed_bytes, 16);
+  const size_t flag_bytes = raw ? align_up(cnt_bytes, 256) : 0;          // [counts | flags | rows]
+  const size_t out_bytes = align_up(cnt_bytes, 256) + flag_bytes + std::max<size_t>(row_bytes, 16);
+  if (m->ws_io_in.reserve(in_bytes, stream) < 0 || m->ws_io_out.reserve(out_bytes, stream) < 0) return -1;
+  unsigned char* d_in = static_cast<unsigned char*>(m->ws_io_in.p);
+  unsigned char* d_out = static_cast<unsigned char*>(m->ws_io_out.p);
+  const uint64_t* d_offsets = reinterpret_cast<const uint64_t*>(d_in);
+  char* d_packed = reinterpret_cast<char*>(d_in + align_up(off_bytes, 256));
+  uint32_t* d_counts = reinterpret_cast<uint32_t*>(d_out);
+  uint32_t* d_flags = reinterpret_cast<uint32_t*>(d_out + align_up(cnt_bytes, 256));
+  trigram_match d_rows = reinterpret_cast<trigram_match>(d_out + align_up(cnt_bytes, 256) + flag_bytes);
+
+  // Small batches (the single blurrily_storage_find above all) go through pinned staging: one
+  // copy in, one copy out, instead of four pageable ones.
+  const bool staged = in_bytes <= kStageBytes && out_bytes <= kStageBytes;
+  if (staged && !m->h_stage) BLURRILY_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&m->h_stage), 2 * kStageBytes));
+  if (staged) {
+    unsigned char* h_in = m->h_stage;
+    std::memcpy(h_in, offsets, off_bytes);
+    if (packed_bytes) std::memcpy(h_in + align_up(off_bytes, 256), packed, packed_bytes);
+    BLURRILY_HIP_TRY(hipMemcpyAsync(d_in, h_in, in_bytes, hipMemcpyHostToDevice, stream));
+  } else {
+    BLURRILY_HIP_TRY(hipMemcpyAsync(d_in, offsets, off_bytes, hipMemcpyHostToDevice, stream));
+    if (packed_bytes)
+      BLURRILY_HIP_TRY(hipMemcpyAsync(d_in + align_up(off_bytes, 256), packed, packed_bytes, hipMemcpyHostToDevice,
+                                      stream));
+  }
+  if (raw && launch_normalise(d_packed, d_offsets, uint32_t(n), d_packed, d_flags, stream) < 0) return -1;
+  if ((multi ? run_find_multi(m, d_packed, packed_bytes, d_offsets, n, limit, d_rows, d_counts, nullptr, stream)
+             : run_find(m, d_packed, packed_bytes, d_offsets, n, limit, d_rows, d_counts, nullptr, max_len > 126,
+                        max_len > 63, stream)) < 0)
+    return -1;
+  if (staged) {
+    unsigned char* h_out = m->h_stage + kStageBytes;
+    BLURRILY_HIP_TRY(hipMemcpyAsync(h_out, d_out, out_bytes, hipMemcpyDeviceToHost, stream));
+    BLURRILY_HIP_TRY(hipStreamSynchronize(stream));
+    std::memcpy(counts, h_out, cnt_bytes);
+    if (raw && non_ascii) std::memcpy(non_ascii, h_out + align_up(cnt_bytes, 256), cnt_bytes);
+    if (limit) std::memcpy(results, h_out + align_up(cnt_bytes, 256) + flag_bytes, row_bytes);
+  } else {
+    BLURRILY_HIP_TRY(hipMemcpyAsync(counts, d_counts, cnt_bytes, hipMemcpyDeviceToHost, stream));
+    if (raw && non_ascii) BLURRILY_HIP_TRY(hipMemcpyAsync(non_ascii, d_flags, cnt_bytes, hipMemcpyDeviceToHost, stream));
+    if (limit) BLURRILY_HIP_TRY(hipMemcpyAsync(results, d_rows, row_bytes, hipMemcpyDeviceToHost, stream));
+    BLURRILY_HIP_TRY(hipStreamSynchronize(stream));
+  }
+  return 0;
+}
+
+// ---- ONE needle, the caller waiting -- or a handful: one launch, no copies (find_kernels.hip: find_one_kernel) --------
+// The reference's only call shape (ext/blurrily/map_ext.c:131-162 -> storage.c:477-580), and small host-buffer batches
+// (a server's coalesced FINDs under light load).  needle i = s[i][0 .. len[i]) (up to its first NUL).  Returns 0 with
+// counts[] and rows filled (results + i * limit), -1 with errno, or kOneNotTaken when the finds have to go the batch's
+// way: a limit of 0 or above kOneMaxKeep, more than kMidMaxNeedles needles, a needle of more than 64 distinct trigrams,
+// timing or request counters switched on, option "one_launch" 0.  Mutations the base image does not hold yet are
+// served: tombstones inside the select, pending puts by a second launch over the delta image.
+constexpr size_t kOneRowBytes = kOneMaxKeep * sizeof(trigram_match_t);
+// the pinned page per image: [kMidMaxNeedles] rows | [kMidMaxNeedles][2] count, sequence word | codes [kMidMaxNeedles][64] | T
+constexpr size_t kOneWordsAt = kMidMaxNeedles * kOneRowBytes;
+constexpr size_t kOneCodesAt = kOneWordsAt + kMidMaxNeedles * 8 + 64;
+constexpr size_t kOneTAt = kOneCodesAt + kMidMaxNeedles * 64 * sizeof(uint16_t);
+// ... | postings [kMidMaxNeedles] | start window [kMidMaxNeedles] | code offsets [kMidMaxNeedles + 1] (latency mode's needle arrays)
+constexpr size_t kMidNbAt = kOneTAt + kMidMaxNeedles * sizeof(uint32_t);
+constexpr size_t kMidStartAt = kMidNbAt + kMidMaxNeedles * sizeof(uint32_t);
+constexpr size_t kMidOffAt = (kMidStartAt + kMidMaxNeedles * sizeof(uint32_t) + 7) & ~size_t(7);
+constexpr size_t kOneHostBytes = kMidOffAt + (kMidMaxNeedles + 1) * sizeof(uint64_t) + 64;
+// lists a launch may leave: up to sixteen rows of kOneMaxGrid workgroups, or more rows of fewer (find_few aims at a
+// thousand workgroups in all)
+constexpr size_t kOneMaxLists = size_t(kOneMaxNeedles) * kOneMaxGrid;
+
+int find_few(trigram_map m, const char* const* s, const size_t* len, size_t n, uint16_t limit, trigram_match results,
+             uint32_t* counts) {
+  if (!m->one.enabled || limit == 0 || limit > kOneMaxKeep || n == 0 || n > kMidMaxNeedles || m->timing || m->collect_stats)
+    return kOneNotTaken;
+  uint16_t codes[kMidMaxNeedles * 64];
+  uint32_t T[kMidMaxNeedles];
+  {
+    uint16_t buf[256];
+    for (size_t i = 0; i < n; ++i) {
+      if (len[i] > 255) return kOneNotTaken;
+      const int t = tokenise(s[i], len[i], buf);            // tokeniser.c:59-119
+      if (t > 64) return kOneNotTaken;
+      T[i] = uint32_t(t);
+      std::memcpy(codes + i * 64, buf, size_t(t) * sizeof(uint16_t));
+    }
+  }
+  DeviceScope scope(m->dev.device);
+  // what the reference's find does first: sort the needle's dirty buckets (storage.c:516), sum their sizes (:498-503)
+  if (m->host->dirty_buckets())
+    for (size_t i = 0; i < n; ++i)
+      for (uint32_t k = 0; k < T[i]; ++k) m->host->sort_bucket_if_dirty(codes[i * 64 + k]);
+  if (ensure_device(m) < 0) return -1;
+  // Mutations the base image does not hold (DESIGN.md "Mutation and device sync"): deletes are tombstone bits the select
+  // looks at, pending puts live in a small delta image searched by a SECOND launch; the two lists of a needle are
+  // merged here (they hold disjoint references).  A log that has overflowed is folded by ensure_device above.
+  const bool with_tomb = log_of(m)->n_tomb != 0, with_delta = !log_of(m)->pending.empty() && m->delta.device >= 0;
+  // needles without a posting return no rows (storage.c:503) and take no row of the grid
+  uint32_t row_of[kMidMaxNeedles], row_nb[kMidMaxNeedles], n_rows = 0;
+  for (size_t i = 0; i < n; ++i) {
+    uint64_t nb = 0;
+    for (uint32_t k = 0; k < T[i]; ++k) nb += m->host->bucket(codes[i * 64 + k]).used;
+    counts[i] = 0;
+    if (nb == 0) continue;
+    if (n_rows != i) { std::memmove(codes + n_rows * 64, codes + i * 64, 64 * sizeof(uint16_t)); T[n_rows] = T[i]; }
+    row_nb[n_rows] = nb > 0xFFFFFFFFull ? 0xFFFFFFFFu : uint32_t(nb);
+    row_of[n_rows++] = uint32_t(i);
+  }
+  if (n_rows == 0) return 0;
+  auto& O = m->one;
+  NameScope name_scope(&m->last_kernels);                 // (the launches below note their kernels' names in the map)
+  m->last_kernels.clear();
+  m->last_sweep = 0;                                      // (no sweep of a class of batches: a single launch, or latency mode)
+  if (!O.h_out) {
+    // stream, pinned page and its device address: built in locals and kept only when ALL of them exist (a half-made set
+    // -- a stream without its page -- would have the next find skip this block and poll a null page)
+    hipStream_t st = nullptr;
+    unsigned char *h = nullptr, *d = nullptr;
+    hipError_t e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&h), 2 * kOneHostBytes, hipHostMallocMapped | hipHostMallocCoherent);
+    if (e == hipSuccess) e = hipHostGetDevicePointer(reinterpret_cast<void**>(&d), h, 0);
+    if (e != hipSuccess) {
+      std::fprintf(stderr, "blurrily_hip: the single find's stream / pinned page: %s\n", hipGetErrorString(e));
+      if (h) (void)hipHostFree(h);
+      if (st) (void)hipStreamDestroy(st);
+      errno = (e == hipErrorOutOfMemory) ? ENOMEM : EIO;
+      return -1;
+    }
+    std::memset(h, 0, 2 * kOneHostBytes);
+    O.stream = st; O.h_out = h; O.d_out = d;
+  }
+  if (with_tomb && apply_tombstones(m, O.stream) < 0) return -1;       // (deletes since the last find: their bits are set first)
+  const size_t key_bytes = kOneMaxLists * kOneMaxKeep * 8, flag_bytes = kOneMaxLists * 4, ticket_bytes = (kMidMaxNeedles + 1) * 4;   // (+ latency mode's queue word)
+  const size_t part_bytes = key_bytes + flag_bytes + ticket_bytes;
+  if (!O.d_parts.p) {
+    if (O.d_parts.reserve(2 * part_bytes, O.stream) < 0) return -1;
+    BLURRILY_HIP_TRY(hipMemsetAsync(O.d_parts.p, 0, 2 * part_bytes, O.stream));
+  }
+  // More than few_max rows: the BASE image is searched in latency mode -- find_kernel<..., RANGED>, a needle's windows cut
+  // into ranges, a task per workgroup: beyond about thirty needles its pipelined steps beat find_one_kernel's exact
+  // selects -- but without the batch path's copies: the per-needle arrays its tokeniser would have left
+  // on the device (trigram counts, postings, the window of the needle's own length class, where its codes start) are
+  // written here, into the pinned page, and read over the link by the tasks; the merge writes rows, counts and
+  // sequence words back into the page (merge_parts_pinned_kernel), where this thread polls them as it does
+  // find_one_kernel's.  Two launches, no copy, no stream synchronise (the batch path: a copy in, the tokeniser, the
+  // find, the merge, a copy out, a synchronise).  The delta image, a window or two, keeps find_one_kernel.
+  const uint32_t mid_ranges = (n_rows > O.few_max && n_rows <= O.mid_max)
+      ? latency_ranges(n_rows, limit, m->dev.n_windows, size_t(m->n_cus) * find_wgs_per_cu(), m->latency_tasks) : 1u;
+  const bool mid = mid_ranges > 1;
+  if (mid) {
+    uint32_t* h_nb = reinterpret_cast<uint32_t*>(O.h_out + kMidNbAt);
+    uint32_t* h_start = reinterpret_cast<uint32_t*>(O.h_out + kMidStartAt);
+    uint64_t* h_off = reinterpret_cast<uint64_t*>(O.h_out + kMidOffAt);
+    for (uint32_t r = 0; r < n_rows; ++r) {
+      h_nb[r] = row_nb[r];
+      h_start[r] = m->dev.h_start_win[std::min<size_t>(len[row_of[r]], 255)];   // (tokenise_kernel: start_win[len])
+      h_off[r] = uint64_t(r) * 63;                        // a needle's codes start at qcodes + offsets[q] + q: [needle][64]
+    }
+    h_off[n_rows] = uint64_t(n_rows) * 63;
+    __atomic_thread_fence(__ATOMIC_RELEASE);
+  }
+  // more than kOneMaxNeedles rows, or latency mode: the codes travel in the pinned page (both images' launches read the first image's copy)
+  const bool far = n_rows > kOneMaxNeedles;
+  if (far || mid) {
+    std::memcpy(O.h_out + kOneCodesAt, codes, size_t(n_rows) * 64 * sizeof(uint16_t));
+    std::memcpy(O.h_out + kOneTAt, T, size_t(n_rows) * sizeof(uint32_t));
+    __atomic_thread_fence(__ATOMIC_RELEASE);
+  }
+  const uint32_t seq = ++O.seq ? O.seq : ++O.seq;         // (never 0: what the words hold before the first find)
+  // one launch per image: [0] the base image, [1] the delta image of the pending puts (its own lists, flags and rows)
+  auto launch_on = [&](const DeviceIndex& ix, const uint32_t* d_tomb, int which) -> int {
+    FindArgs a{};
+    a.slice_se = ix.d_slice_se; a.ent = ix.d_ent; a.ref_of_rank = ix.d_ref_of_rank;
+    a.weight_of_rank = ix.d_weight_of_rank; a.n_refs = ix.n_refs; a.n_windows = ix.n_windows;
+    a.win_max_tri = ix.d_win_max_tri; a.nib_windows = ix.nib_windows; a.dense_min8 = ix.dense_min8;
+    a.limit = limit; a.keep = limit; a.pool_cap = 512;
+    a.tomb = d_tomb;
+#ifdef BLURRILY_TRACE
+    if (!m->d_phase) BLURRILY_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&m->d_phase), kPhaseBytes));
+    if (which == 0) a.phase_clocks = m->d_phase;       // (trace build: find_one_kernel's wall-clock marks, 16 per workgroup)
+#endif
+    unsigned char* dp = static_cast<unsigned char*>(O.d_parts.p) + which * part_bytes;
+    unsigned char* d_rows = O.d_out + which * kOneHostBytes;
+    if (mid && which == 0) {
+      const size_t wgs = size_t(m->n_cus) * find_wgs_per_cu();
+      const uint32_t tasks = n_rows * mid_ranges;           // (<= 2 wgs: far below kOneMaxLists, whose keys and flags it borrows)
+      a.offsets = reinterpret_cast<const uint64_t*>(O.d_out + kMidOffAt);
+      a.qcodes = reinterpret_cast<const uint16_t*>(O.d_out + kOneCodesAt);
+      a.q_ntri = reinterpret_cast<const uint32_t*>(O.d_out + kOneTAt);
+      a.q_nb = reinterpret_cast<const uint32_t*>(O.d_out + kMidNbAt);
+      a.q_start = reinterpret_cast<const uint32_t*>(O.d_out + kMidStartAt);
+      a.nm_dense = std::max((m->nm_dense + 7u) & ~7u, ix.dense_min8);
+      a.nm_cmin = 0;                                        // (ranges leave nothing out of a step's count: measured, slower)
+      a.n_work = tasks; a.ranges = mid_ranges; a.short_only = 1;
+      a.part_keys = reinterpret_cast<unsigned long long*>(dp);
+      a.part_count = reinterpret_cast<uint32_t*>(dp + key_bytes);
+      a.queue = reinterpret_cast<uint32_t*>(dp + key_bytes + flag_bytes) + kMidMaxNeedles;   // (zero between launches: the merge hands it back)
+      a.pool_cap = find_pool_cap(limit);
+      if (launch_find(a, false, uint32_t(std::min<size_t>(tasks, wgs)), O.stream) < 0) return -1;
+      uint32_t merge_cap = 1024;
+      while (merge_cap < mid_ranges * limit) merge_cap <<= 1;
+      a.pool_cap = merge_cap;
+      return launch_merge_parts_pinned(a, n_rows, reinterpret_cast<trigram_match_t*>(d_rows),
+                                       reinterpret_cast<uint32_t*>(d_rows + kOneWordsAt), seq, O.stream);
+    }
+    // one window per workgroup while that fills at most kOneMaxGrid of them, whole window pairs beyond; more than
+    // eight needles: about a thousand workgroups in all -- two rounds of what the chip holds --, i.e. several
+    // window pairs a workgroup (its later steps arrive with its own threshold: one_select's cheap way)
+    uint32_t per = 1;
+    if (ix.n_windows > kOneMaxGrid) { per = (ix.n_windows + kOneMaxGrid - 1) / kOneMaxGrid; per += per & 1u; }
+    if (n_rows > 8) {                                     // (from nine needles on: measured, tools/mid_probe.py)
+      const uint32_t rows_wgs = std::max<uint32_t>(2u, m->one.mid_workgroups / n_rows);     // workgroups per needle
+      const uint32_t per_far = (ix.n_windows + rows_wgs - 1) / rows_wgs;
+      per = std::max(per, per_far + (per_far > 1 ? per_far & 1u : 0u));
+    }
+    per = std::max(per, O.min_per);                       // (a test's way to the several-steps-per-workgroup path on a small image)
+    const uint32_t grid = (ix.n_windows + per - 1) / per;
+    if (size_t(grid) * n_rows > kOneMaxLists) { errno = EINVAL; return -1; }   // (cannot happen: grid <= kOneMaxGrid, far grids are small)
+    return launch_find_one(a, codes, T, n_rows, per, grid, reinterpret_cast<unsigned long long*>(dp),
+                           reinterpret_cast<uint32_t*>(dp + key_bytes), reinterpret_cast<trigram_match_t*>(d_rows),
+                           reinterpret_cast<uint32_t*>(d_rows + kOneWordsAt), seq, O.stream, uint32_t(m->n_cus),
+                           far ? reinterpret_cast<const uint16_t*>(O.d_out + kOneCodesAt) : nullptr,
+                           far ? reinterpret_cast<const uint32_t*>(O.d_out + kOneTAt) : nullptr,
+                           far ? reinterpret_cast<uint32_t*>(dp + key_bytes + flag_bytes) : nullptr);
+  };
+  if (launch_on(m->dev, with_tomb ? m->dev.d_tomb : nullptr, 0) < 0) return -1;
+  if (with_delta && launch_on(m->delta, nullptr, 1) < 0) return -1;
+  // A row's last store is its sequence word; the host polls the words in the pinned page instead of waiting for the
+  // runtime to notice the kernel's completion signal (an interrupt or a slower poll: 10 us and more).
+  uint64_t spins = 0;
+  for (int which = 0; which < (with_delta ? 2 : 1); ++which) {
+    volatile uint32_t* words = reinterpret_cast<volatile uint32_t*>(O.h_out + which * kOneHostBytes + kOneWordsAt);
+    for (uint32_t r = 0; r < n_rows; ++r) {
+      while (words[2 * r + 1] != seq) {
+#if defined(__x86_64__)
+        __builtin_ia32_pause();
+#endif
+        if ((++spins & 0xFFFFFu) == 0) {                  // every few milliseconds: is the stream still alive?
+          const hipError_t q = hipStreamQuery(O.stream);
+          if (q == hipSuccess && words[2 * r + 1] != seq) { std::fprintf(stderr, "blurrily_hip: find_one finished without its rows\n"); errno = EIO; return -1; }
+          if (q != hipSuccess && q != hipErrorNotReady) { std::fprintf(stderr, "blurrily_hip: find_one: %s\n", hipGetErrorString(q)); errno = EIO; return -1; }
+        }
+      }
+    }
+  }
+  __atomic_thread_fence(__ATOMIC_ACQUIRE);
+  const volatile uint32_t* w0 = reinterpret_cast<const volatile uint32_t*>(O.h_out + kOneWordsAt);
+  const volatile uint32_t* w1 = reinterpret_cast<const volatile uint32_t*>(O.h_out + kOneHostBytes + kOneWordsAt);
+  for (uint32_t r = 0; r < n_rows; ++r) {
+    const uint32_t i = row_of[r];
+    const trigram_match_t* a_rows = reinterpret_cast<const trigram_match_t*>(O.h_out + r * kOneRowBytes);
+    const uint32_t got_a = w0[2 * r], na = got_a < limit ? got_a : uint32_t(limit);
+    trigram_match_t* out = results + size_t(i) * limit;
+    if (!with_delta) {
+      counts[i] = na;
+      std::memcpy(out, a_rows, size_t(na) * sizeof(trigram_match_t));
+      continue;
+    }
+    // result order: matches descending, weight ascending, reference ascending (storage.c:129-138, :566)
+    const trigram_match_t* b_rows = reinterpret_cast<const trigram_match_t*>(O.h_out + kOneHostBytes + r * kOneRowBytes);
+    const uint32_t got_b = w1[2 * r], nb_ = got_b < limit ? got_b : uint32_t(limit);
+    uint32_t ia = 0, ib = 0, k = 0;
+    while (k < limit && (ia < na || ib < nb_)) {
+      bool take_a;
+      if (ia >= na) take_a = false;
+      else if (ib >= nb_) take_a = true;
+      else {
+        const trigram_match_t x = a_rows[ia], y = b_rows[ib];
+        take_a = x.matches != y.matches ? x.matches > y.matches : x.weight != y.weight ? x.weight < y.weight : x.reference < y.reference;
+      }
+      out[k++] = take_a ? a_rows[ia++] : b_rows[ib++];
+    }
+    counts[i] = k;
+  }
+  O.taken += n_rows;
+  return 0;
+}
+
+}  // namespace detail
+}  // namespace blurrily

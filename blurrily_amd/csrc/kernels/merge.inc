@@ -35,7 +35,7 @@ __global__ __launch_bounds__(NT) void merge_parts_kernel(const FindArgs A) {
   if (tid == 0) A.counts[q] = nres;
 }
 
-// The same merge for a handful of needles tokenised on the host (c_abi.hip: find_few's latency-mode half): the rows go
+// The same merge for a handful of needles tokenised on the host (host_batch.hip: find_few's latency-mode half): the rows go
 // straight into host-coherent pinned memory -- rows[needle][kOneMaxKeep], words[needle] = {count, the launch's sequence
 // word}, the word stored last and behind a system-scope fence; the host polls it (find_one_kernel's protocol) -- so that
 // such a batch costs two launches and no copy, no stream synchronise.  Workgroup 0 hands the find launch's queue word

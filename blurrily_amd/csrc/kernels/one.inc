@@ -27,7 +27,7 @@
 // Same answer by construction: every posting of every window counted, a window's best `keep` candidates that beat the
 // workgroup's threshold taken exactly, the best `keep` of the union of per-workgroup best `keep` lists (nothing can be
 // lost).  Served: needles of at most 64 distinct trigrams, limits up to kOneMaxKeep, images without tombstones or
-// pending puts (c_abi.hip: find_one); everything else goes the batch's way as before.
+// pending puts (host_batch.hip: find_few); everything else goes the batch's way as before.
 constexpr uint32_t kOnePool = 512;
 constexpr int      kOneThreads = 1024;                   // (512 -- eight waves, 256 VGPRs each -- measured: 35.4 against 33.5 us)
 constexpr uint32_t kOneAhead = 4;                        // units a wave loads before it counts the first of them

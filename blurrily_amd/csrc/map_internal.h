@@ -1,0 +1,291 @@
+// map_internal.h -- the map object behind the C ABI (include/blurrily_storage.h) and what its sources share: the
+// error macro, the device scratch types, and the internal functions that cross translation units.  Everything
+// declared in blurrily::detail has hidden visibility: none of it is a dynamic symbol of libblurrily_hip.so.
+//   c_abi.hip        lifecycle, put / delete / save / stats, find / find_batch entries, options, debug entries
+//   map_log.hip      the mutation log: ensure_device, apply_tombstones, map_ready, map_images
+//   find_run.hip     the batch search's launch logic: run_find_on, run_find; stage_string_needles
+//   multi_device.hip replicas, run_find_multi
+//   host_batch.hip   host-buffer batches: the chunked pipeline, find_batch_host, find_few
+//   refs.hip         by reference: refs_extract, stage_reference_needles, get / find_references entries
+//   scope.hip        scoped find, a scope per needle
+//   above.hip, similar.hip   the threshold and similarity finds (their shared sort: segsort.h)
+#pragma once
+#include "../../include/blurrily_storage.h"
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cerrno>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <new>
+#include <string>
+#include <unordered_map>
+#include <vector>
+
+#include "device_index.h"
+#include "find_kernels.h"
+#include "hip_try.h"
+#include "host_index.h"
+
+struct trigram_map_t;
+
+namespace blurrily {
+namespace detail __attribute__((visibility("hidden"))) {
+
+// A map's device image lives on the HIP device that was current when it was built.  Every entry
+// point that touches the image runs inside a DeviceScope: the current device is switched to the
+// map's and restored on the way out, so a caller (torch, another map) may leave any device current.
+struct DeviceScope {
+  int  prev = -1;
+  bool changed = false;
+  explicit DeviceScope(int want) {
+    if (want >= 0 && hipGetDevice(&prev) == hipSuccess && prev != want) changed = hipSetDevice(want) == hipSuccess;
+  }
+  ~DeviceScope() { if (changed) (void)hipSetDevice(prev); }
+  DeviceScope(const DeviceScope&) = delete;
+  DeviceScope& operator=(const DeviceScope&) = delete;
+};
+
+// Device scratch that lives as long as the map and only ever grows.
+struct DeviceBuffer {
+  void*  p = nullptr;
+  size_t bytes = 0;
+  int reserve(size_t want, hipStream_t stream) {
+    if (want <= bytes) return 0;
+    if (p) { (void)hipStreamSynchronize(stream); (void)hipFree(p); p = nullptr; bytes = 0; }
+    const size_t grow = std::max(want, bytes + bytes / 2);
+    BLURRILY_HIP_TRY(hipMalloc(&p, grow));
+    bytes = grow;
+    return 0;
+  }
+  void release() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
+};
+
+inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+// where note_launch() (find_kernels.h) writes: the `last_kernels` of the map whose batch is being enqueued on this thread
+std::string*& launch_names();
+struct NameScope {                                     // the launches inside it note their kernels' names in *s
+  std::string* prev;
+  explicit NameScope(std::string* s) : prev(launch_names()) { launch_names() = s; }
+  ~NameScope() { launch_names() = prev; }
+};
+
+}  // namespace detail
+}  // namespace blurrily
+
+// Mutations since the base device image was built (DESIGN.md "Mutation and device sync").
+struct PendingPut {
+  std::string needle;
+  uint32_t    weight;
+};
+
+// "devices" > 1: one more copy of the map's device side, on another visible device (or, with more replicas than
+// devices, on one that already has one): clones of the primary's images, a map object of its own for the scratch
+// buffers, events and measured choices its finds need, a stream, and staging for its shard of a batch.
+struct Replica {
+  int            device = -1;
+  bool           same_device = false;   // it sits on the primary's own device (more replicas than devices)
+  bool           peer_access = false;   // its device and the primary's reach each other's memory directly (both ways, enabled)
+  trigram_map_t* side = nullptr;        // dev / delta / d_code_total_now are the clones; host == nullptr; mirror_of = the primary
+  uint64_t       base_builds = 0, delta_image_version = 0, log_version = 0;   // the primary's, as of the clones
+  hipStream_t    stream = nullptr;
+  hipEvent_t     ev_done = nullptr, ev_t0 = nullptr, ev_t1 = nullptr;
+  blurrily::detail::DeviceBuffer d_in, d_out;   // [offsets | needles] of the batch, [rows | counts | nb_entries] of its shard
+};
+
+struct trigram_map_t {
+  blurrily::HostIndex*  host = nullptr;
+  const trigram_map_t* mirror_of = nullptr;   // a replica's side map: the mutation log that counts is this map's
+  std::vector<Replica> replicas;        // "devices" - 1 of them
+  uint32_t    n_devices = 1;            // option "devices": shards of a large batch (the primary's included)
+  hipEvent_t  ev_ready = nullptr, ev_t0 = nullptr, ev_t1 = nullptr;   // multi-device batches
+  blurrily::DeviceIndex dev;                      // base image
+  // log of puts/deletes the base image does not contain yet
+  std::unordered_map<uint32_t, PendingPut> pending;   // by reference
+  size_t      n_tomb = 0;               // base references deleted since the build
+  std::vector<uint32_t> tomb_queue;     // their ranks, not yet on the device (applied by the next find, on its stream)
+  blurrily::detail::DeviceBuffer ws_tomb;
+  uint64_t    log_version = 0;          // bumped by every logged mutation
+  uint64_t    delta_version = 0;        // log_version the delta image / code totals were built from
+  uint64_t    delta_puts_version = 0;   // bumped when the set of pending puts changes (the delta image's content)
+  uint64_t    delta_image_version = 0;  // delta_puts_version the delta image was built from
+  bool        log_overflow = false;     // the log outgrew its budget: the next find rebuilds the base
+  uint64_t    base_builds = 0;
+  blurrily::HostIndex*  delta_host = nullptr;
+  blurrily::DeviceIndex delta;                    // image of `pending` only
+  uint32_t*   d_code_total_now = nullptr;   // [kNumCodes] bucket sizes of the whole map (base run's nb_entries)
+  blurrily::detail::DeviceBuffer ws_base_rows, ws_base_counts, ws_delta_rows, ws_delta_counts;
+  // tunables of the window-major sweep (blurrily_storage_set_option; defaults from the measured gate)
+  blurrily::IndexBuildOptions build_opt;          // ws_enabled, ws_min_windows, ws_min_slice, dense_min
+  uint32_t    ws_cmin = 3;              // a left-out slice must leave at least this many counted matches
+  uint32_t    nm_cmin = 3;              // the same for the needle-major sweep (0: it leaves nothing out)
+  uint32_t    nm_dense = 3072;          // ... which leaves out slices of at least this many postings only (4 096 through round 5;
+                                        // round 6, same rows: configs[2] 120.8 -> 119.1 ms per 300 k needles, four times the haystack 135.1 -> 129.9)
+  bool        small_sweep = true;       // images of at most kSmallMaxWindows windows: find_small_kernel serves large batches at limits up to 64
+  uint32_t    small_min_needles = 4096; // ... from this many needles on (below: two chains per CU are not the limit)
+  uint32_t    nm_min_windows = 256;     // ... and, where the choice is not measured, on images of at least this many windows
+  uint32_t    ws_min_needles = 16384;   // smaller batches: needle-major
+  bool        ws_autotune = true;       // measure the choice per class of batch on first use (run_find_on)
+  uint32_t    ws_static_slice = 2200;   // the static rule's mean_hit_slice (autotune off): break-even of the skewed family
+  int         ws_choice[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // per class: 0 not measured yet, 1 needle-major, 2 window-major,
+                                                   // 3 needle-major with slices left out
+  float       ws_tuned_ms[8][3] = {};   // what the measurement saw (needle-major, window-major, slices left out)
+  int         last_tuned = -1;          // the class measured most recently ("tuned_*_us" report its figures)
+  int         last_sweep = 0;           // which sweep the last large batch of short needles took (1 / 2 / 3; 0: none yet)
+  uint32_t latency_tasks = 0;           // option "latency_tasks": tasks latency mode aims at per resident workgroup (0: latency_ranges' rule)
+  std::string last_kernels;             // the find kernels the last batch on the base image launched, '+'-joined (blurrily_storage_last_kernels)
+  size_t      class_hint = 0;           // a chunked host batch: the WHOLE batch's size decides the class, not the chunk's
+  hipEvent_t  tune_ev[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  // a measured choice is WATCHED: the chosen sweep's later batches of the class are bracketed by two events (read at the
+  // class's next batch, never waited for); one that ran over 10 % slower per needle than what the measurement saw has
+  // the class measured again -- at most once in sixteen batches
+  hipEvent_t  watch_ev[8][2] = {};
+  bool        watch_pending[8] = {false, false, false, false, false, false, false, false};
+  size_t      watch_n[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  size_t      tuned_n[8] = {0, 0, 0, 0, 0, 0, 0, 0};      // the batch size a class was measured at (the watch compares like with like)
+  float       tuned_us_per_needle[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};   // of the sweep that was chosen
+  uint32_t    retune_holdoff[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  uint32_t    watch_strikes[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // consecutive batches of the class seen slow (one is noise: another tenant, a clock step)
+  uint64_t    retunes = 0;              // classes measured again because a batch ran slow (option "retunes", read-only)
+  int         tune_inject = 0;          // (tests) the next measurement sees this sweep at HALF its time: a bad sample to recover from
+  int         n_cus = 0;
+  bool        timing = false;
+  bool        collect_stats = false;    // request counters of the find kernels (FindArgs::stats)
+  unsigned long long* d_stats = nullptr;   // [kStatSlots], zeroed by every run_find while collecting
+  unsigned long long* d_phase = nullptr;   // [kPhaseWorkgroups][16] phase clocks of the counted build's last launch
+  blurrily::detail::DeviceBuffer ws_flags;                   // [n] path flags of the last find while collecting (FindArgs::path_flags)
+  size_t      n_flags = 0;
+  double      last_find_ms = 0.0, last_tok_ms = 0.0;
+  hipEvent_t  ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  blurrily::detail::DeviceBuffer ws_codes, ws_small, ws_parts, ws_io_in, ws_io_out;
+  blurrily::detail::DeviceBuffer ws_refs;                 // by reference: the extraction's arrays and the references' codes (refs_extract)
+  // scoped find: options "scope_strategy" (0 auto, 1 mask, 2 direct) and "scope_direct_max" (the
+  // scope's member codes up to which auto scores the members directly; 0: auto always takes the mask), and a pinned
+  // page the device maps, for small host batches the direct strategy serves without copies.  The default sits just
+  // above the largest scope measured where direct wins both batches and single finds (configs[2], 10^4 members, 140 544
+  // codes: 21x the mask's needles/s, 82 against 124 us a find; at 416 379 codes it still wins batches 4.5x but single
+  // finds take 193 against 122 us -- profiles/scope_geonames.json)
+  uint32_t    scope_strategy = 0;
+  uint64_t    scope_direct_max = 150000;
+  unsigned char* h_scope = nullptr;     // [kScopePageBytes in | kScopePageBytes out]
+  unsigned char* d_scope = nullptr;     // the same memory as the device addresses it
+  // a scope per needle: the call's plan on the device (scope table, workgroup order, the groups'
+  // needles, their rows) and on the host (what is uploaded; kept until the next such call)
+  blurrily::detail::DeviceBuffer ws_each, ws_each_rows;
+  std::vector<unsigned char> h_each;
+  unsigned char* h_stage = nullptr;     // pinned host staging: [kStageBytes in | kStageBytes out]
+  // the single find's own launch (find_one): a stream, host-coherent pinned memory the kernel writes rows, count and a
+  // sequence word into, the per-workgroup lists and the ticket on the device
+  struct One {
+    hipStream_t    stream = nullptr;
+    unsigned char* h_out = nullptr;     // per image: [kMidMaxNeedles][kOneMaxKeep] rows | [..][2] count, sequence word | codes | T (kOneHostBytes)
+    unsigned char* d_out = nullptr;     // the same memory as the device addresses it
+    blurrily::detail::DeviceBuffer   d_parts;             // per image: [kOneMaxLists][kOneMaxKeep] keys | [kOneMaxLists] flags | [kMidMaxNeedles] tickets
+    uint32_t       seq = 0;
+    bool           enabled = true;      // option "one_launch"
+    uint32_t       min_per = 0;         // option "one_windows_per_wg": at least this many windows per workgroup (0: as few as the grid allows)
+    uint32_t       mid_workgroups = 1024;   // option "mid_workgroups": workgroups a launch of more than kOneMaxNeedles needles aims at
+    uint32_t       few_max = 24;        // option "few_max": host-buffer batches of up to this many needles share find_one_kernel's launch
+                                        // (up to kMidMaxNeedles; from about thirty needles on latency mode's ranges are faster: DESIGN.md)
+    uint32_t       mid_max = blurrily::kMidMaxNeedles;   // option "mid_max": ... and up to this many take latency mode WITHOUT copies: tokenised on the
+                                        // host, read from the pinned page, the merged rows written back into it (find_few)
+    uint64_t       taken = 0;           // finds served this way (option "one_taken", read-only)
+  } one;
+  // large host-buffer batches go in chunks through a three-stream pipeline (find_batch_chunked)
+  uint32_t    host_chunk = 131072;      // needles per chunk (option "host_chunk"; 0: never chunk)
+  struct Pipe {
+    hipStream_t s_in = nullptr, s_run = nullptr, s_out = nullptr;
+    hipEvent_t  ev_in[2] = {nullptr, nullptr}, ev_run[2] = {nullptr, nullptr}, ev_out[2] = {nullptr, nullptr};
+    unsigned char* h_in[2] = {nullptr, nullptr};     // pinned
+    unsigned char* h_out[2] = {nullptr, nullptr};
+    size_t h_in_bytes = 0, h_out_bytes = 0;
+    blurrily::detail::DeviceBuffer d_in[2], d_out[2];
+  } pipe;
+};
+
+namespace blurrily {
+namespace detail __attribute__((visibility("hidden"))) {
+
+constexpr size_t kPhaseWorkgroups = 8192, kPhaseBytes = kPhaseWorkgroups * 16 * 8;
+
+// ---- map_log.hip ------------------------------------------------------------------------------------------------------
+size_t log_budget(const trigram_map m);
+const trigram_map_t* log_of(const trigram_map_t* m);
+bool log_empty(const trigram_map_t* m);
+int  ensure_device(trigram_map m);
+void log_put(trigram_map m, const char* needle, size_t len, uint32_t ref, uint32_t weight);
+int  log_delete(trigram_map m, uint32_t ref);
+int  apply_tombstones(trigram_map m, hipStream_t stream);
+// what an entry does first: the map's pending work, then the device image (ENODEV without a usable GPU), the tombstones
+int  map_ready(trigram_map m, hipStream_t stream);
+
+// ---- find_run.hip -----------------------------------------------------------------------------------------------------
+uint32_t latency_ranges(size_t n, uint32_t limit, uint32_t n_windows, size_t wgs, uint32_t tasks_per_wg);
+// (sm: a scoped find's masks, in the tombstone bitmap's place: they exclude the deleted ranks too)
+struct ScopeMasks { const uint32_t* base; const uint32_t* delta; };
+int run_find(trigram_map m, const char* d_packed, size_t packed_bytes, const uint64_t* d_offsets, size_t n,
+             uint16_t limit, trigram_match d_results, uint32_t* d_counts, uint32_t* d_nb, bool maybe_long,
+             bool maybe_mid, hipStream_t stream, const RefNeedles* rn = nullptr, const ScopeMasks* sm = nullptr);
+
+// ---- multi_device.hip -------------------------------------------------------------------------------------------------
+void free_replica(Replica& r);
+int  run_find_multi(trigram_map m, const char* d_packed, size_t packed_bytes, const uint64_t* d_offsets, size_t n,
+                    uint16_t limit, trigram_match d_results, uint32_t* d_counts, uint32_t* d_nb, hipStream_t stream);
+bool wants_multi(const trigram_map_t* m, size_t n);
+
+// ---- host_batch.hip ---------------------------------------------------------------------------------------------------
+constexpr int kOneNotTaken = -2;   // find_few: the finds have to go the batch's way
+int find_few(trigram_map m, const char* const* s, const size_t* len, size_t n, uint16_t limit, trigram_match results,
+             uint32_t* counts);
+int find_batch_host(trigram_map m, const char* packed, const uint64_t* offsets, size_t n, uint16_t limit,
+                    trigram_match results, uint32_t* counts, bool raw, uint32_t* non_ascii);
+
+// The needles of a call as the threshold and similarity sweeps read them (the front ends' layout: tokenise_kernel,
+// refs_extract): needle q's ntri[q] distinct codes at codes + qoff[q] + q.
+struct NeedleView {
+  const uint16_t* codes;
+  const uint64_t* qoff;
+  const uint32_t* ntri;
+};
+
+// The images a call searches and the deleted ranks of each: the base image, and the delta image of pending puts.
+struct MapImages {
+  uint32_t        n;
+  DeviceIndex*    img[2];
+  const uint32_t* tomb[2];
+};
+MapImages map_images(trigram_map m);                                                             // map_log.hip
+// Windows per workgroup of a sweep over nc needles: a small batch spreads each needle's windows over the GPU, a large
+// one gives a needle one workgroup (at_least: a floor of the caller's).
+inline uint32_t windows_per_workgroup(const trigram_map_t* m, const DeviceIndex& ix, size_t nc, uint64_t at_least = 1) {
+  const uint64_t want = uint64_t(std::max(m->n_cus, 1)) * 8u;
+  const uint64_t per = std::max<uint64_t>(std::max<uint64_t>(uint64_t(ix.n_windows) * nc / want, 1), at_least);
+  return uint32_t(std::min<uint64_t>(per, std::max<uint32_t>(ix.n_windows, 1)));
+}
+// n host strings up and tokenised by the string path's own front end (find_run.hip); buf: the call's scratch for them
+int stage_string_needles(trigram_map m, const char* packed, const uint64_t* offsets, size_t n, DeviceBuffer& buf,
+                         hipStream_t stream, NeedleView* out);
+// n host references up and extracted by the by-reference front end (refs.hip); nb_trigrams (may be null): copied back
+int stage_reference_needles(trigram_map m, const uint32_t* references, size_t n, DeviceBuffer& buf, hipStream_t stream,
+                            uint32_t* nb_trigrams, NeedleView* out);
+
+// ---- refs.hip ---------------------------------------------------------------------------------------------------------
+// The trigrams of n device-resident references, extracted on `stream` from the map as it is now: the base image minus its
+// deleted ranks, the delta image of pending puts (kernels/refs.inc).  Each image uploads its reference table at its first
+// such call.  *out describes the needles for run_find, and where the count of distinct references found and of the codes
+// extracted for them sit on the device.
+struct RefExtract {
+  RefNeedles needles;
+  const uint64_t* win_base_total;   // [1] distinct references found
+  const uint64_t* slot_start;       // [n + 1]: slot_start[*win_base_total] codes in all
+  const uint2*    loc;              // [n] where each reference was found (RefArgs::loc)
+  uint32_t        win0_delta;       // the delta image's first window in loc's numbering (with_delta)
+  bool            with_delta;
+};
+int refs_extract(trigram_map m, const uint32_t* d_refs, size_t n, hipStream_t stream, RefExtract* out);
+
+}  // namespace detail
+}  // namespace blurrily

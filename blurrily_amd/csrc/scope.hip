@@ -1,0 +1,710 @@
+// scope.hip -- scoped find and a scope per needle (blurrily_scope_*, blurrily_storage_find_in / _find_batch_in[_device],
+// _find_batch_each_in[_device], _find_references_each_in; DESIGN.md sections 12 and 13).
+#include "map_internal.h"
+
+using namespace blurrily;
+using namespace blurrily::detail;
+
+// ---- scoped find (blurrily_scope_* / blurrily_storage_find_in / _find_batch_in[_device]) ---------
+// A scope keeps its references sorted and distinct.  Its device state is made at the first scoped find and whenever
+// the map has changed since (base_builds, log_version): the members are looked up and extracted as by reference
+// (refs_extract), a mask per image excludes every rank but the members held now, and -- for scopes the direct strategy
+// may serve -- the held members' codes, weights and references in (weight, reference) order are copied into the
+// scope's own buffers (ws_refs is every later by-reference call's).
+struct blurrily_scope_t {
+  trigram_map           map = nullptr;
+  std::vector<uint32_t> refs;           // sorted, distinct
+  bool         ready = false;
+  bool         mask_ready = false;       // (a scope prepared with others, by a scope-per-needle call, has no masks yet)
+  uint64_t     built_base = 0, built_log = 0;
+  uint32_t     n_held = 0;               // members held at the last preparation
+  DeviceBuffer d_refs, d_mask[2];        // masks: base image, delta image (pending puts)
+  bool         has_delta = false;
+  // direct form (n_direct members: m_off [n_direct + 1] | m_ref | m_weight | m_codes)
+  bool         direct = false;
+  uint32_t     n_direct = 0;
+  uint64_t     direct_codes = 0;
+  DeviceBuffer d_direct;
+  const uint32_t *m_off = nullptr, *m_ref = nullptr, *m_weight = nullptr;
+  const uint16_t* m_codes = nullptr;
+};
+
+namespace {
+
+constexpr size_t kScopePageBytes = size_t(1) << 16;   // small direct batches: needles in, rows out, through mapped memory
+
+// The direct form from an extraction's readback: the held members (indices into sc->refs) in (weight, reference)
+// order -- the rows' order among equal matches -- with member i's ntri[i] codes at codes_of(i), copied to the device.
+template <class CodesOf>
+int scope_set_direct(blurrily_scope sc, std::vector<uint32_t>& held, const uint32_t* ntri, const uint32_t* wgt,
+                     uint64_t codes, CodesOf codes_of, hipStream_t stream) {
+  std::sort(held.begin(), held.end(), [&](uint32_t a, uint32_t b) {
+    return wgt[a] != wgt[b] ? wgt[a] < wgt[b] : sc->refs[a] < sc->refs[b];
+  });
+  const size_t nd = held.size();
+  const size_t o_ref = align_up((nd + 1) * 4, 256), o_wgt = o_ref + align_up(nd * 4, 256);
+  const size_t o_codes = o_wgt + align_up(nd * 4, 256), bytes = o_codes + std::max<size_t>(codes * 2, 16);
+  std::vector<unsigned char> h(bytes, 0);
+  uint32_t* off = reinterpret_cast<uint32_t*>(h.data());
+  uint32_t* ref = reinterpret_cast<uint32_t*>(h.data() + o_ref);
+  uint32_t* weight = reinterpret_cast<uint32_t*>(h.data() + o_wgt);
+  uint16_t* cd = reinterpret_cast<uint16_t*>(h.data() + o_codes);
+  off[0] = 0;
+  for (size_t j = 0; j < nd; ++j) {
+    const uint32_t i = held[j];
+    std::memcpy(cd + off[j], codes_of(i), size_t(ntri[i]) * sizeof(uint16_t));
+    off[j + 1] = off[j] + ntri[i];
+    ref[j] = sc->refs[i];
+    weight[j] = wgt[i];
+  }
+  if (sc->d_direct.reserve(bytes, stream) < 0) return -1;
+  BLURRILY_HIP_TRY(hipMemcpy(sc->d_direct.p, h.data(), bytes, hipMemcpyHostToDevice));
+  unsigned char* d = static_cast<unsigned char*>(sc->d_direct.p);
+  sc->m_off = reinterpret_cast<const uint32_t*>(d);
+  sc->m_ref = reinterpret_cast<const uint32_t*>(d + o_ref);
+  sc->m_weight = reinterpret_cast<const uint32_t*>(d + o_wgt);
+  sc->m_codes = reinterpret_cast<const uint16_t*>(d + o_codes);
+  sc->n_direct = uint32_t(nd);
+  sc->direct_codes = codes;
+  sc->direct = true;
+  return 0;
+}
+
+// The scope's device state for the map as it is now (the image brought up to date and tombstones applied first).
+int scope_prepare(trigram_map m, blurrily_scope sc, hipStream_t stream) {
+  if (m->host->dirty_buckets()) m->host->sort_dirty_buckets();
+  if (ensure_device(m) < 0) return -1;
+  if (apply_tombstones(m, stream) < 0) return -1;
+  if (sc->ready && sc->mask_ready && sc->built_base == m->base_builds && sc->built_log == log_of(m)->log_version)
+    return 0;
+  sc->ready = false;
+  sc->mask_ready = false;
+  sc->direct = false;
+  sc->n_held = 0;
+  const size_t n = sc->refs.size();
+  const bool with_delta = !log_of(m)->pending.empty() && m->delta.device >= 0;
+  const uint32_t words[2] = {(m->dev.n_refs + 31u) / 32u + 1u, with_delta ? (m->delta.n_refs + 31u) / 32u + 1u : 1u};
+  for (int k = 0; k < 2; ++k)
+    if (sc->d_mask[k].reserve(size_t(words[k]) * 4, stream) < 0) return -1;
+  sc->has_delta = with_delta;
+  ScopeMaskArgs ma{};
+  ma.n_img = with_delta ? 2u : 1u;
+  ma.win0[0] = 0; ma.win0[1] = m->dev.n_windows;
+  ma.mask[0] = static_cast<uint32_t*>(sc->d_mask[0].p); ma.mask[1] = static_cast<uint32_t*>(sc->d_mask[1].p);
+  ma.mask_words[0] = words[0]; ma.mask_words[1] = words[1];
+  if (n == 0) {
+    if (launch_scope_mask(ma, stream) < 0) return -1;
+  } else {
+    if (sc->d_refs.reserve(n * sizeof(uint32_t), stream) < 0) return -1;
+    BLURRILY_HIP_TRY(hipMemcpyAsync(sc->d_refs.p, sc->refs.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    RefExtract x;
+    if (refs_extract(m, static_cast<const uint32_t*>(sc->d_refs.p), n, stream, &x) < 0) return -1;
+    ma.loc = x.loc; ma.n = uint32_t(n);
+    if (launch_scope_mask(ma, stream) < 0) return -1;
+    std::vector<uint32_t> ntri(n), wgt(n);
+    BLURRILY_HIP_TRY(hipMemcpyAsync(ntri.data(), x.needles.ntri, n * 4, hipMemcpyDeviceToHost, stream));
+    BLURRILY_HIP_TRY(hipMemcpyAsync(wgt.data(), x.needles.weight, n * 4, hipMemcpyDeviceToHost, stream));
+    BLURRILY_HIP_TRY(hipStreamSynchronize(stream));
+    std::vector<uint32_t> held;
+    uint64_t codes = 0;
+    uint32_t widest = 0;
+    for (size_t i = 0; i < n; ++i)
+      if (ntri[i]) { held.push_back(uint32_t(i)); codes += ntri[i]; widest = std::max(widest, ntri[i]); }
+    sc->n_held = uint32_t(held.size());
+    // the direct form, when the direct strategy can serve the scope at all
+    if (!held.empty() && held.size() <= kScopeMaxMembers && widest <= kScopeMaxMemberCodes) {
+      std::vector<uint64_t> qoff(n);
+      uint64_t slots = 0, total = 0;
+      BLURRILY_HIP_TRY(hipMemcpyAsync(qoff.data(), x.needles.qoff, n * 8, hipMemcpyDeviceToHost, stream));
+      BLURRILY_HIP_TRY(hipMemcpyAsync(&slots, x.win_base_total, 8, hipMemcpyDeviceToHost, stream));
+      BLURRILY_HIP_TRY(hipStreamSynchronize(stream));
+      BLURRILY_HIP_TRY(hipMemcpy(&total, x.slot_start + slots, 8, hipMemcpyDeviceToHost));
+      std::vector<uint16_t> all(total);
+      if (total) BLURRILY_HIP_TRY(hipMemcpy(all.data(), x.needles.codes + n, total * sizeof(uint16_t), hipMemcpyDeviceToHost));
+      if (scope_set_direct(sc, held, ntri.data(), wgt.data(), codes,
+                           [&](uint32_t i) { return all.data() + (qoff[i] + i - n); }, stream) < 0)
+        return -1;
+    }
+  }
+  sc->built_base = m->base_builds;
+  sc->built_log = log_of(m)->log_version;
+  sc->ready = true;
+  sc->mask_ready = true;
+  return 0;
+}
+
+// Which strategy serves a scoped find of `limit` (the scope prepared): the direct one declines limits above its pool and
+// scopes without a direct form (above kScopeMaxMembers held members, or a member of more than 255 distinct trigrams);
+// auto takes it for scopes of at most "scope_direct_max" member codes.
+bool scope_takes_direct(const trigram_map_t* m, const blurrily_scope_t* sc, uint16_t limit) {
+  if (m->scope_strategy == 1 || !sc->direct || limit == 0 || limit > kScopeMaxKeep) return false;
+  return m->scope_strategy == 2 || sc->direct_codes <= m->scope_direct_max;
+}
+
+// Enqueue a scoped find of n device-resident needles on the prepared scope: rows of only its members.
+int scope_run(trigram_map m, blurrily_scope sc, const char* d_packed, size_t packed_bytes, const uint64_t* d_offsets,
+              size_t n, uint16_t limit, trigram_match d_results, uint32_t* d_counts, bool maybe_long, bool maybe_mid,
+              hipStream_t stream) {
+  if (n == 0) return 0;
+  if (n > 0xFFFFFFF0ull) { errno = EINVAL; return -1; }
+  if (sc->n_held == 0 || limit == 0) {                 // nothing in the scope is held: no rows
+    NameScope name_scope(&m->last_kernels);
+    m->last_kernels.clear();
+    m->last_sweep = 0;
+    BLURRILY_HIP_TRY(hipMemsetAsync(d_counts, 0, n * sizeof(uint32_t), stream));
+    return 0;
+  }
+  if (scope_takes_direct(m, sc, limit)) {
+    NameScope name_scope(&m->last_kernels);
+    m->last_kernels.clear();
+    m->last_sweep = 0;
+    ScopeFindArgs a{};
+    a.packed = d_packed; a.offsets = d_offsets; a.n = uint32_t(n);
+    a.m_off = sc->m_off; a.m_codes = sc->m_codes; a.m_ref = sc->m_ref; a.m_weight = sc->m_weight;
+    a.n_members = sc->n_direct; a.limit = limit; a.results = d_results; a.counts = d_counts;
+    return launch_scope_find(a, stream);
+  }
+  const ScopeMasks sm{static_cast<const uint32_t*>(sc->d_mask[0].p),
+                      sc->has_delta ? static_cast<const uint32_t*>(sc->d_mask[1].p) : nullptr};
+  if (m->timing && !m->ev[0])
+    for (auto& e : m->ev) BLURRILY_HIP_TRY(hipEventCreate(&e));
+  return run_find(m, d_packed, packed_bytes, d_offsets, n, limit, d_results, d_counts, nullptr, maybe_long, maybe_mid,
+                  stream, nullptr, &sm);
+}
+
+// The pinned page small direct batches go through (m->h_scope, mapped at m->d_scope), made at first use.
+int scope_page(trigram_map m) {
+  if (m->h_scope) return 0;
+  unsigned char *h = nullptr, *d = nullptr;
+  hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&h), 2 * kScopePageBytes, hipHostMallocMapped | hipHostMallocCoherent);
+  if (e == hipSuccess) e = hipHostGetDevicePointer(reinterpret_cast<void**>(&d), h, 0);
+  if (e != hipSuccess) {
+    std::fprintf(stderr, "blurrily_hip: the scoped find's pinned page: %s\n", hipGetErrorString(e));
+    if (h) (void)hipHostFree(h);
+    errno = (e == hipErrorOutOfMemory) ? ENOMEM : EIO;
+    return -1;
+  }
+  m->h_scope = h; m->d_scope = d;
+  return 0;
+}
+
+int scope_check(trigram_map m, blurrily_scope sc) {
+  if (!m || !sc || sc->map != m) { errno = EINVAL; return -1; }
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int blurrily_scope_new(trigram_map m, const uint32_t* references, size_t n, blurrily_scope* scope) {
+  if (!m || !scope || (n && !references)) { errno = EINVAL; return -1; }
+  blurrily_scope sc = new (std::nothrow) blurrily_scope_t();
+  if (!sc) { errno = ENOMEM; return -1; }
+  try {
+    sc->refs.assign(references, references + n);
+  } catch (const std::bad_alloc&) {
+    delete sc;
+    errno = ENOMEM;
+    return -1;
+  }
+  std::sort(sc->refs.begin(), sc->refs.end());
+  sc->refs.erase(std::unique(sc->refs.begin(), sc->refs.end()), sc->refs.end());
+  sc->map = m;
+  *scope = sc;
+  return 0;
+}
+
+int blurrily_scope_close(blurrily_scope* scope) {
+  if (!scope) { errno = EINVAL; return -1; }
+  blurrily_scope sc = *scope;
+  if (sc) {
+    if (sc->d_refs.p || sc->d_mask[0].p || sc->d_mask[1].p || sc->d_direct.p) (void)hipDeviceSynchronize();
+    sc->d_refs.release(); sc->d_mask[0].release(); sc->d_mask[1].release(); sc->d_direct.release();
+    delete sc;
+  }
+  *scope = nullptr;
+  return 0;
+}
+
+int blurrily_scope_members(blurrily_scope scope, uint32_t* held) {
+  if (!scope || !held || !scope->map) { errno = EINVAL; return -1; }
+  uint32_t k = 0;
+  for (uint32_t r : scope->refs) k += scope->map->host->holds(r) ? 1u : 0u;
+  *held = k;
+  return 0;
+}
+
+int blurrily_storage_find_batch_in_device(trigram_map m, blurrily_scope sc, const char* d_packed, size_t packed_bytes,
+                                          const uint64_t* d_offsets, size_t n, uint16_t limit,
+                                          trigram_match d_results, uint32_t* d_counts, void* stream) {
+  if (scope_check(m, sc) < 0) return -1;
+  DeviceScope scope(m->dev.device);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (scope_prepare(m, sc, st) < 0) return -1;
+  return scope_run(m, sc, d_packed, packed_bytes, d_offsets, n, limit, d_results, d_counts, true, true, st);
+}
+
+int blurrily_storage_find_batch_in(trigram_map m, blurrily_scope sc, const char* packed, const uint64_t* offsets,
+                                   size_t n, uint16_t limit, trigram_match results, uint32_t* counts) {
+  if (scope_check(m, sc) < 0) return -1;
+  if (n && (!packed || !offsets || !counts || (limit && !results))) { errno = EINVAL; return -1; }
+  DeviceScope scope(m->dev.device);
+  hipStream_t stream = nullptr;
+  if (scope_prepare(m, sc, stream) < 0) return -1;     // (without a GPU this is what fails, with ENODEV)
+  if (n == 0) return 0;
+  size_t max_len = 0;
+  for (size_t i = 0; i < n && max_len <= 126; ++i) {   // (what the sweeps need to know: > 63, > 126)
+    const size_t cap = size_t(offsets[i + 1] - offsets[i]);
+    if (cap <= max_len) continue;
+    const char* s = packed + offsets[i];
+    const void* nul = std::memchr(s, 0, cap);
+    max_len = std::max(max_len, nul ? size_t(static_cast<const char*>(nul) - s) : cap);
+  }
+  const size_t packed_bytes = size_t(offsets[n]);
+  const size_t off_bytes = (n + 1) * sizeof(uint64_t);
+  const size_t row_bytes = n * size_t(limit) * sizeof(trigram_match_t);
+  const size_t cnt_bytes = n * sizeof(uint32_t);
+  const size_t in_bytes = align_up(off_bytes, 256) + std::max<size_t>(packed_bytes, 16);
+  const size_t out_bytes = align_up(cnt_bytes, 256) + std::max<size_t>(row_bytes, 16);
+  // a small batch the direct strategy serves: needles read and rows written by the kernel in mapped pinned memory --
+  // one launch, no copies
+  if (in_bytes <= kScopePageBytes && out_bytes <= kScopePageBytes && sc->n_held && scope_takes_direct(m, sc, limit)) {
+    if (scope_page(m) < 0) return -1;
+    unsigned char* h_in = m->h_scope;
+    unsigned char* h_out = m->h_scope + kScopePageBytes;
+    std::memcpy(h_in, offsets, off_bytes);
+    if (packed_bytes) std::memcpy(h_in + align_up(off_bytes, 256), packed, packed_bytes);
+    unsigned char* d_in = m->d_scope;
+    unsigned char* d_out = m->d_scope + kScopePageBytes;
+    if (scope_run(m, sc, reinterpret_cast<const char*>(d_in + align_up(off_bytes, 256)), packed_bytes,
+                  reinterpret_cast<const uint64_t*>(d_in), n, limit,
+                  reinterpret_cast<trigram_match>(d_out + align_up(cnt_bytes, 256)), reinterpret_cast<uint32_t*>(d_out),
+                  false, false, stream) < 0)
+      return -1;
+    BLURRILY_HIP_TRY(hipStreamSynchronize(stream));
+    std::memcpy(counts, h_out, cnt_bytes);
+    if (limit) std::memcpy(results, h_out + align_up(cnt_bytes, 256), row_bytes);
+    return 0;
+  }
+  if (m->ws_io_in.reserve(in_bytes, stream) < 0 || m->ws_io_out.reserve(out_bytes, stream) < 0) return -1;
+  unsigned char* d_in = static_cast<unsigned char*>(m->ws_io_in.p);
+  unsigned char* d_out = static_cast<unsigned char*>(m->ws_io_out.p);
+  BLURRILY_HIP_TRY(hipMemcpyAsync(d_in, offsets, off_bytes, hipMemcpyHostToDevice, stream));
+  if (packed_bytes)
+    BLURRILY_HIP_TRY(hipMemcpyAsync(d_in + align_up(off_bytes, 256), packed, packed_bytes, hipMemcpyHostToDevice, stream));
+  uint32_t* d_counts = reinterpret_cast<uint32_t*>(d_out);
+  trigram_match d_rows = reinterpret_cast<trigram_match>(d_out + align_up(cnt_bytes, 256));
+  if (scope_run(m, sc, reinterpret_cast<const char*>(d_in + align_up(off_bytes, 256)), packed_bytes,
+                reinterpret_cast<const uint64_t*>(d_in), n, limit, d_rows, d_counts, max_len > 126, max_len > 63,
+                stream) < 0)
+    return -1;
+  BLURRILY_HIP_TRY(hipMemcpyAsync(counts, d_counts, cnt_bytes, hipMemcpyDeviceToHost, stream));
+  if (limit) BLURRILY_HIP_TRY(hipMemcpyAsync(results, d_rows, row_bytes, hipMemcpyDeviceToHost, stream));
+  BLURRILY_HIP_TRY(hipStreamSynchronize(stream));
+  return 0;
+}
+
+int blurrily_storage_find_in(trigram_map m, blurrily_scope sc, const char* needle, uint16_t limit, trigram_match results) {
+  if (!needle) { errno = EINVAL; return -1; }
+  const uint64_t offsets[2] = {0, std::strlen(needle)};
+  uint32_t count = 0;
+  if (blurrily_storage_find_batch_in(m, sc, needle, offsets, 1, limit, results, &count) < 0) return -1;
+  return int(count);
+}
+
+}  // extern "C"
+
+// ---- a scope per needle (blurrily_storage_find_batch_each_in[_device] / _find_references_each_in) -
+// Needle i is a scoped find in scopes[which[i]], or a plain find for BLURRILY_NO_SCOPE.  The call groups the needles by
+// what serves their scope: every needle the direct strategy serves, whatever its scope, goes into ONE launch of
+// scope_each_kernel; each scope the mask serves gets one run_find over its needles, compacted, and so does the NO_SCOPE
+// group (unscoped); a scatter puts their rows back in the caller's order.  The stale scopes of a call are prepared
+// together (scopes_prepare_direct: one extraction of all their members, one readback); a scope's masks are built only
+// when a call serves it through them (scope_prepare).
+namespace {
+
+int each_check(trigram_map m, const blurrily_scope* scopes, size_t n_scopes) {
+  if (!m || (n_scopes && !scopes)) { errno = EINVAL; return -1; }
+  for (size_t j = 0; j < n_scopes; ++j)
+    if (!scopes[j] || scopes[j]->map != m) { errno = EINVAL; return -1; }
+  return 0;
+}
+
+int each_check_which(const uint32_t* which, size_t n, size_t n_scopes) {
+  for (size_t i = 0; i < n; ++i)
+    if (which[i] != BLURRILY_NO_SCOPE && which[i] >= n_scopes) { errno = EINVAL; return -1; }
+  return 0;
+}
+
+// The direct form and the held count of every scope in `stale` for the map as it is now: their members uploaded and
+// extracted as one list, read back once.  No masks: mask_ready stays false until scope_prepare builds them.
+int scopes_prepare_direct(trigram_map m, const std::vector<blurrily_scope>& stale, hipStream_t stream) {
+  if (stale.empty()) return 0;
+  size_t n = 0;
+  for (blurrily_scope sc : stale) {
+    n += sc->refs.size();
+    sc->ready = false; sc->mask_ready = false; sc->direct = false; sc->n_held = 0;
+  }
+  if (n > 0xFFFFFFF0ull) { errno = EINVAL; return -1; }
+  std::vector<uint32_t> ntri(n), wgt(n);
+  std::vector<uint64_t> qoff(n);
+  std::vector<uint16_t> all;
+  if (n) {
+    std::vector<uint32_t> refs;
+    refs.reserve(n);
+    for (blurrily_scope sc : stale) refs.insert(refs.end(), sc->refs.begin(), sc->refs.end());
+    if (m->ws_each.reserve(n * sizeof(uint32_t), stream) < 0) return -1;
+    BLURRILY_HIP_TRY(hipMemcpyAsync(m->ws_each.p, refs.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    RefExtract x;
+    if (refs_extract(m, static_cast<const uint32_t*>(m->ws_each.p), n, stream, &x) < 0) return -1;
+    uint64_t slots = 0, total = 0;
+    BLURRILY_HIP_TRY(hipMemcpyAsync(ntri.data(), x.needles.ntri, n * 4, hipMemcpyDeviceToHost, stream));
+    BLURRILY_HIP_TRY(hipMemcpyAsync(wgt.data(), x.needles.weight, n * 4, hipMemcpyDeviceToHost, stream));
+    BLURRILY_HIP_TRY(hipMemcpyAsync(qoff.data(), x.needles.qoff, n * 8, hipMemcpyDeviceToHost, stream));
+    BLURRILY_HIP_TRY(hipMemcpyAsync(&slots, x.win_base_total, 8, hipMemcpyDeviceToHost, stream));
+    BLURRILY_HIP_TRY(hipStreamSynchronize(stream));
+    BLURRILY_HIP_TRY(hipMemcpy(&total, x.slot_start + slots, 8, hipMemcpyDeviceToHost));
+    all.resize(total);
+    if (total) BLURRILY_HIP_TRY(hipMemcpy(all.data(), x.needles.codes + n, total * sizeof(uint16_t), hipMemcpyDeviceToHost));
+  }
+  size_t at = 0;
+  for (blurrily_scope sc : stale) {
+    const size_t k = sc->refs.size();
+    std::vector<uint32_t> held;
+    uint64_t codes = 0;
+    uint32_t widest = 0;
+    for (size_t i = 0; i < k; ++i)
+      if (ntri[at + i]) { held.push_back(uint32_t(i)); codes += ntri[at + i]; widest = std::max(widest, ntri[at + i]); }
+    sc->n_held = uint32_t(held.size());
+    if (!held.empty() && held.size() <= kScopeMaxMembers && widest <= kScopeMaxMemberCodes &&
+        scope_set_direct(sc, held, ntri.data() + at, wgt.data() + at, codes,
+                         [&](uint32_t i) { return all.data() + (qoff[at + i] + at + i - n); }, stream) < 0)
+      return -1;
+    sc->built_base = m->base_builds;
+    sc->built_log = log_of(m)->log_version;
+    sc->ready = true;
+    at += k;
+  }
+  return 0;
+}
+
+// Which launch serves each needle of a call.
+struct EachPlan {
+  std::vector<ScopeDirect>    table;         // the direct scopes' forms
+  std::vector<uint2>          order;         // the direct needles {needle, table slot}: largest scopes first
+  uint32_t                    max_members = 0;
+  std::vector<uint32_t>       idx;           // the swept groups' needles, group after group
+  std::vector<size_t>         group_start;   // [groups + 1]
+  std::vector<blurrily_scope> group_scope;   // nullptr: the NO_SCOPE group
+  bool                        any_empty = false;   // needles of a scope without rows (no held member, limit 0)
+};
+
+// Group the needles and prepare what serves them: the stale scopes together, then the masks of the scopes the mask
+// serves.  (Every extraction of the call happens here, before the by-reference needles take ws_refs.)
+int each_plan(trigram_map m, const blurrily_scope* scopes, size_t n_scopes, const uint32_t* which, size_t n,
+              uint16_t limit, hipStream_t stream, EachPlan* P) {
+  std::unordered_map<blurrily_scope, uint32_t> slot_of;    // the distinct scopes (a handle given twice is one)
+  std::vector<blurrily_scope> uniq;
+  std::vector<uint32_t> slot(n_scopes);
+  for (size_t j = 0; j < n_scopes; ++j) {
+    auto it = slot_of.emplace(scopes[j], uint32_t(uniq.size()));
+    if (it.second) uniq.push_back(scopes[j]);
+    slot[j] = it.first->second;
+  }
+  const uint32_t U = uint32_t(uniq.size());                // slot U: NO_SCOPE
+  auto slot_at = [&](size_t i) { return which[i] == BLURRILY_NO_SCOPE ? U : slot[which[i]]; };
+  std::vector<uint32_t> per(U + 1, 0);
+  for (size_t i = 0; i < n; ++i) ++per[slot_at(i)];
+  std::vector<blurrily_scope> stale;
+  for (uint32_t u = 0; u < U; ++u) {
+    const blurrily_scope sc = uniq[u];
+    if (per[u] && !(sc->ready && sc->built_base == m->base_builds && sc->built_log == log_of(m)->log_version))
+      stale.push_back(sc);
+  }
+  if (scopes_prepare_direct(m, stale, stream) < 0) return -1;
+  // 0: no rows, 1: direct, 2: through its masks, 3: NO_SCOPE (unscoped)
+  std::vector<uint8_t> kind(U + 1, 0);
+  kind[U] = 3;
+  for (uint32_t u = 0; u < U; ++u) {
+    const blurrily_scope sc = uniq[u];
+    if (!per[u]) continue;
+    if (sc->n_held == 0 || limit == 0) { P->any_empty = true; continue; }
+    if (scope_takes_direct(m, sc, limit)) { kind[u] = 1; continue; }
+    if (scope_prepare(m, sc, stream) < 0) return -1;      // (builds the masks if this scope has none yet)
+    kind[u] = 2;
+  }
+  std::vector<uint32_t> direct_u, dslot(U + 1, 0);
+  for (uint32_t u = 0; u < U; ++u)
+    if (kind[u] == 1) direct_u.push_back(u);
+  std::stable_sort(direct_u.begin(), direct_u.end(),
+                   [&](uint32_t a, uint32_t b) { return uniq[a]->n_direct > uniq[b]->n_direct; });
+  std::vector<size_t> cursor(U + 1, 0);
+  size_t nd = 0, ng = 0;
+  for (uint32_t u : direct_u) {
+    const blurrily_scope sc = uniq[u];
+    dslot[u] = uint32_t(P->table.size());
+    P->table.push_back(ScopeDirect{sc->m_off, sc->m_codes, sc->m_ref, sc->m_weight, sc->n_direct, 0u});
+    P->max_members = std::max(P->max_members, sc->n_direct);
+    cursor[u] = nd;
+    nd += per[u];
+  }
+  for (uint32_t u = 0; u <= U; ++u) {
+    if (kind[u] < 2 || !per[u]) continue;
+    P->group_start.push_back(ng);
+    P->group_scope.push_back(u < U ? uniq[u] : nullptr);
+    cursor[u] = ng;
+    ng += per[u];
+  }
+  P->group_start.push_back(ng);
+  P->order.resize(nd);
+  P->idx.resize(ng);
+  for (size_t i = 0; i < n; ++i) {
+    const uint32_t u = slot_at(i);
+    if (kind[u] == 1) P->order[cursor[u]++] = make_uint2(uint32_t(i), dslot[u]);
+    else if (kind[u] >= 2) P->idx[cursor[u]++] = uint32_t(i);
+  }
+  return 0;
+}
+
+// The needles of a call: strings on the device (h_offsets: the caller's offsets on the host, or nullptr: read back if
+// a swept group needs them) or references extracted by refs_extract (rn).
+struct EachNeedles {
+  const char*       d_packed = nullptr;
+  const uint64_t*   d_offsets = nullptr;
+  const uint64_t*   h_offsets = nullptr;
+  const RefNeedles* rn = nullptr;
+};
+
+int each_launch_direct(const EachPlan& P, const EachNeedles& N, const ScopeDirect* d_table, const uint2* d_order,
+                       uint16_t limit, trigram_match d_results, uint32_t* d_counts, hipStream_t stream) {
+  ScopeEachArgs a{};
+  if (N.rn) { a.codes = N.rn->codes; a.qoff = N.rn->qoff; a.ntri = N.rn->ntri; }
+  else { a.packed = N.d_packed; a.offsets = N.d_offsets; }
+  a.order = d_order; a.n = uint32_t(P.order.size()); a.scopes = d_table; a.max_members = P.max_members;
+  a.limit = limit; a.results = d_results; a.counts = d_counts;
+  return launch_scope_each(a, stream);
+}
+
+// Enqueue the planned call on `stream`: rows and counts of needle i at d_results + i * limit, d_counts[i].
+// last_kernels: every find kernel the call launched.
+int each_run(trigram_map m, const EachPlan& P, const EachNeedles& N, size_t n, uint16_t limit, trigram_match d_results,
+             uint32_t* d_counts, bool maybe_long, bool maybe_mid, hipStream_t stream) {
+  std::string names;
+  const size_t nd = P.order.size(), ng = P.idx.size();
+  if (P.any_empty) BLURRILY_HIP_TRY(hipMemsetAsync(d_counts, 0, n * sizeof(uint32_t), stream));
+  // the swept groups' strings: where each lands when compacted
+  std::vector<uint64_t> goff, off_back;
+  if (ng && !N.rn) {
+    const uint64_t* off = N.h_offsets;
+    if (!off) {
+      off_back.resize(n + 1);
+      BLURRILY_HIP_TRY(hipMemcpyAsync(off_back.data(), N.d_offsets, (n + 1) * 8, hipMemcpyDeviceToHost, stream));
+      BLURRILY_HIP_TRY(hipStreamSynchronize(stream));
+      off = off_back.data();
+    }
+    goff.resize(ng + 1);
+    goff[0] = 0;
+    for (size_t k = 0; k < ng; ++k) goff[k + 1] = goff[k] + (off[P.idx[k] + 1] - off[P.idx[k]]);
+  }
+  // one upload (table | order | idx | compacted offsets), then the device's own: compacted strings or descriptors
+  size_t at = 0;
+  auto take = [&](size_t bytes) { const size_t here = at; at += align_up(std::max<size_t>(bytes, 8), 256); return here; };
+  const size_t o_tab = take(P.table.size() * sizeof(ScopeDirect)), o_ord = take(nd * sizeof(uint2));
+  const size_t o_idx = take(ng * 4), o_goff = take(goff.size() * 8), up = at;
+  const size_t o_gpk = take(goff.empty() ? 0 : goff[ng]), o_gq = take(N.rn ? ng * 8 : 0);
+  const size_t o_gn = take(N.rn ? ng * 4 : 0), o_gw = take(N.rn ? ng * 4 : 0);
+  m->h_each.assign(up, 0);
+  unsigned char* h = m->h_each.data();
+  if (!P.table.empty()) std::memcpy(h + o_tab, P.table.data(), P.table.size() * sizeof(ScopeDirect));
+  if (nd) std::memcpy(h + o_ord, P.order.data(), nd * sizeof(uint2));
+  if (ng) std::memcpy(h + o_idx, P.idx.data(), ng * 4);
+  if (!goff.empty()) std::memcpy(h + o_goff, goff.data(), goff.size() * 8);
+  if (m->ws_each.reserve(at, stream) < 0) return -1;
+  unsigned char* d = static_cast<unsigned char*>(m->ws_each.p);
+  BLURRILY_HIP_TRY(hipMemcpyAsync(d, h, up, hipMemcpyHostToDevice, stream));
+  // every needle served directly: one launch
+  if (nd) {
+    NameScope name_scope(&names);
+    if (each_launch_direct(P, N, reinterpret_cast<const ScopeDirect*>(d + o_tab), reinterpret_cast<const uint2*>(d + o_ord),
+                           limit, d_results, d_counts, stream) < 0)
+      return -1;
+  }
+  if (ng) {
+    const uint32_t* d_idx = reinterpret_cast<const uint32_t*>(d + o_idx);
+    const size_t row_bytes = align_up(std::max<size_t>(ng * size_t(limit) * sizeof(trigram_match_t), 16), 256);
+    if (m->ws_each_rows.reserve(row_bytes + ng * 4, stream) < 0) return -1;
+    trigram_match g_rows = static_cast<trigram_match>(m->ws_each_rows.p);
+    uint32_t* g_counts = reinterpret_cast<uint32_t*>(static_cast<unsigned char*>(m->ws_each_rows.p) + row_bytes);
+    const uint64_t* d_goff = reinterpret_cast<const uint64_t*>(d + o_goff);
+    char* d_gpk = reinterpret_cast<char*>(d + o_gpk);
+    if (!N.rn && launch_scope_gather_strings(N.d_packed, N.d_offsets, d_idx, d_goff, uint32_t(ng), d_gpk, stream) < 0)
+      return -1;
+    if (m->timing && !m->ev[0])
+      for (auto& e : m->ev) BLURRILY_HIP_TRY(hipEventCreate(&e));
+    for (size_t g = 0; g + 1 < P.group_start.size(); ++g) {
+      const size_t k0 = P.group_start[g], cnt = P.group_start[g + 1] - k0;
+      const blurrily_scope sc = P.group_scope[g];
+      const ScopeMasks sm{sc ? static_cast<const uint32_t*>(sc->d_mask[0].p) : nullptr,
+                          sc && sc->has_delta ? static_cast<const uint32_t*>(sc->d_mask[1].p) : nullptr};
+      RefNeedles rg{};
+      if (N.rn) {
+        uint64_t* gq = reinterpret_cast<uint64_t*>(d + o_gq) + k0;
+        uint32_t* gn = reinterpret_cast<uint32_t*>(d + o_gn) + k0;
+        uint32_t* gw = reinterpret_cast<uint32_t*>(d + o_gw) + k0;
+        if (launch_scope_gather_refs(*N.rn, d_idx + k0, uint32_t(cnt), gq, gn, gw, stream) < 0) return -1;
+        rg = RefNeedles{N.rn->codes, gq, gn, gw, uint32_t(cnt), N.rn->code_slots};
+      }
+      if (run_find(m, N.rn ? nullptr : d_gpk, N.rn ? 0 : size_t(goff[ng]), N.rn ? nullptr : d_goff + k0, cnt, limit,
+                   g_rows + k0 * limit, g_counts + k0, nullptr, maybe_long, maybe_mid, stream, N.rn ? &rg : nullptr,
+                   sc ? &sm : nullptr) < 0)
+        return -1;
+      NameScope name_scope(&names);                      // (what that run noted in last_kernels, in launch order)
+      for (size_t b = 0, e; b < m->last_kernels.size(); b = e + 1) {
+        e = m->last_kernels.find('+', b);
+        if (e == std::string::npos) e = m->last_kernels.size();
+        note_launch(m->last_kernels.substr(b, e - b).c_str());
+      }
+    }
+    if (launch_scope_scatter(g_rows, g_counts, d_idx, uint32_t(ng), limit, d_results, d_counts, stream) < 0) return -1;
+  }
+  m->last_kernels = names;
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int blurrily_storage_find_batch_each_in_device(trigram_map m, const blurrily_scope* scopes, size_t n_scopes,
+                                               const uint32_t* d_which, const char* d_packed, size_t packed_bytes,
+                                               const uint64_t* d_offsets, size_t n, uint16_t limit,
+                                               trigram_match d_results, uint32_t* d_counts, void* stream) {
+  (void)packed_bytes;
+  if (each_check(m, scopes, n_scopes) < 0) return -1;
+  if (n && (!d_which || !d_offsets || !d_counts || (limit && !d_results))) { errno = EINVAL; return -1; }
+  if (n > 0xFFFFFFF0ull) { errno = EINVAL; return -1; }
+  DeviceScope scope(m->dev.device);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (map_ready(m, st) < 0) return -1;
+  if (n == 0) return 0;
+  std::vector<uint32_t> which(n);                        // (read back to group the needles: the call waits for it)
+  BLURRILY_HIP_TRY(hipMemcpyAsync(which.data(), d_which, n * 4, hipMemcpyDeviceToHost, st));
+  BLURRILY_HIP_TRY(hipStreamSynchronize(st));
+  if (each_check_which(which.data(), n, n_scopes) < 0) return -1;
+  EachPlan P;
+  if (each_plan(m, scopes, n_scopes, which.data(), n, limit, st, &P) < 0) return -1;
+  EachNeedles N;
+  N.d_packed = d_packed; N.d_offsets = d_offsets;
+  return each_run(m, P, N, n, limit, d_results, d_counts, true, true, st);
+}
+
+int blurrily_storage_find_batch_each_in(trigram_map m, const blurrily_scope* scopes, size_t n_scopes,
+                                        const uint32_t* which, const char* packed, const uint64_t* offsets, size_t n,
+                                        uint16_t limit, trigram_match results, uint32_t* counts) {
+  if (each_check(m, scopes, n_scopes) < 0) return -1;
+  if (n && (!which || !packed || !offsets || !counts || (limit && !results))) { errno = EINVAL; return -1; }
+  if (n > 0xFFFFFFF0ull) { errno = EINVAL; return -1; }
+  if (each_check_which(which, n, n_scopes) < 0) return -1;
+  DeviceScope scope(m->dev.device);
+  hipStream_t stream = nullptr;
+  if (map_ready(m, stream) < 0) return -1;
+  if (n == 0) return 0;
+  EachPlan P;
+  if (each_plan(m, scopes, n_scopes, which, n, limit, stream, &P) < 0) return -1;
+  size_t max_len = 0;
+  for (size_t i = 0; i < n && max_len <= 126; ++i) {   // (what the sweeps need to know: > 63, > 126)
+    const size_t cap = size_t(offsets[i + 1] - offsets[i]);
+    if (cap <= max_len) continue;
+    const char* s = packed + offsets[i];
+    const void* nul = std::memchr(s, 0, cap);
+    max_len = std::max(max_len, nul ? size_t(static_cast<const char*>(nul) - s) : cap);
+  }
+  const size_t packed_bytes = size_t(offsets[n]);
+  const size_t off_bytes = (n + 1) * sizeof(uint64_t);
+  const size_t row_bytes = n * size_t(limit) * sizeof(trigram_match_t);
+  const size_t cnt_bytes = n * sizeof(uint32_t);
+  const size_t o_packed = align_up(off_bytes, 256), o_tab = o_packed + align_up(std::max<size_t>(packed_bytes, 16), 256);
+  const size_t o_ord = o_tab + align_up(P.table.size() * sizeof(ScopeDirect) + 8, 256);
+  const size_t page_in = o_ord + P.order.size() * sizeof(uint2);
+  const size_t out_bytes = align_up(cnt_bytes, 256) + std::max<size_t>(row_bytes, 16);
+  // a small batch served directly alone: needles, scope table and order read, rows written, in mapped pinned memory --
+  // one launch, no copies
+  if (P.idx.empty() && !P.order.empty() && page_in <= kScopePageBytes && out_bytes <= kScopePageBytes) {
+    if (scope_page(m) < 0) return -1;
+    unsigned char* h_in = m->h_scope;
+    unsigned char* h_out = m->h_scope + kScopePageBytes;
+    std::memcpy(h_in, offsets, off_bytes);
+    if (packed_bytes) std::memcpy(h_in + o_packed, packed, packed_bytes);
+    std::memcpy(h_in + o_tab, P.table.data(), P.table.size() * sizeof(ScopeDirect));
+    std::memcpy(h_in + o_ord, P.order.data(), P.order.size() * sizeof(uint2));
+    unsigned char* d_in = m->d_scope;
+    unsigned char* d_out = m->d_scope + kScopePageBytes;
+    uint32_t* d_counts = reinterpret_cast<uint32_t*>(d_out);
+    if (P.any_empty) std::memset(h_out, 0, cnt_bytes);
+    EachNeedles N;
+    N.d_packed = reinterpret_cast<const char*>(d_in + o_packed); N.d_offsets = reinterpret_cast<const uint64_t*>(d_in);
+    NameScope name_scope(&m->last_kernels);
+    m->last_kernels.clear();
+    if (each_launch_direct(P, N, reinterpret_cast<const ScopeDirect*>(d_in + o_tab),
+                           reinterpret_cast<const uint2*>(d_in + o_ord), limit,
+                           reinterpret_cast<trigram_match>(d_out + align_up(cnt_bytes, 256)), d_counts, stream) < 0)
+      return -1;
+    BLURRILY_HIP_TRY(hipStreamSynchronize(stream));
+    std::memcpy(counts, h_out, cnt_bytes);
+    if (limit) std::memcpy(results, h_out + align_up(cnt_bytes, 256), row_bytes);
+    return 0;
+  }
+  const size_t in_bytes = o_packed + std::max<size_t>(packed_bytes, 16);
+  if (m->ws_io_in.reserve(in_bytes, stream) < 0 || m->ws_io_out.reserve(out_bytes, stream) < 0) return -1;
+  unsigned char* d_in = static_cast<unsigned char*>(m->ws_io_in.p);
+  unsigned char* d_out = static_cast<unsigned char*>(m->ws_io_out.p);
+  BLURRILY_HIP_TRY(hipMemcpyAsync(d_in, offsets, off_bytes, hipMemcpyHostToDevice, stream));
+  if (packed_bytes) BLURRILY_HIP_TRY(hipMemcpyAsync(d_in + o_packed, packed, packed_bytes, hipMemcpyHostToDevice, stream));
+  uint32_t* d_counts = reinterpret_cast<uint32_t*>(d_out);
+  trigram_match d_rows = reinterpret_cast<trigram_match>(d_out + align_up(cnt_bytes, 256));
+  EachNeedles N;
+  N.d_packed = reinterpret_cast<const char*>(d_in + o_packed); N.d_offsets = reinterpret_cast<const uint64_t*>(d_in);
+  N.h_offsets = offsets;
+  if (each_run(m, P, N, n, limit, d_rows, d_counts, max_len > 126, max_len > 63, stream) < 0) return -1;
+  BLURRILY_HIP_TRY(hipMemcpyAsync(counts, d_counts, cnt_bytes, hipMemcpyDeviceToHost, stream));
+  if (limit) BLURRILY_HIP_TRY(hipMemcpyAsync(results, d_rows, row_bytes, hipMemcpyDeviceToHost, stream));
+  BLURRILY_HIP_TRY(hipStreamSynchronize(stream));
+  return 0;
+}
+
+int blurrily_storage_find_references_each_in(trigram_map m, const blurrily_scope* scopes, size_t n_scopes,
+                                             const uint32_t* which, const uint32_t* references, size_t n,
+                                             uint16_t limit, trigram_match results, uint32_t* counts,
+                                             uint32_t* nb_trigrams) {
+  if (each_check(m, scopes, n_scopes) < 0) return -1;
+  if (n && (!which || !references || !counts || (limit && !results))) { errno = EINVAL; return -1; }
+  if (n > 0xFFFFFFF0ull) { errno = EINVAL; return -1; }
+  if (each_check_which(which, n, n_scopes) < 0) return -1;
+  DeviceScope scope(m->dev.device);
+  hipStream_t stream = nullptr;
+  if (map_ready(m, stream) < 0) return -1;
+  if (n == 0) return 0;
+  EachPlan P;
+  if (each_plan(m, scopes, n_scopes, which, n, limit, stream, &P) < 0) return -1;
+  const size_t row_bytes = n * size_t(limit) * sizeof(trigram_match_t), cnt_bytes = align_up(n * sizeof(uint32_t), 256);
+  if (m->ws_io_in.reserve(n * sizeof(uint32_t), stream) < 0 ||
+      m->ws_io_out.reserve(cnt_bytes + std::max<size_t>(row_bytes, 16), stream) < 0)
+    return -1;
+  unsigned char* d_out = static_cast<unsigned char*>(m->ws_io_out.p);
+  uint32_t* d_counts = reinterpret_cast<uint32_t*>(d_out);
+  trigram_match d_rows = reinterpret_cast<trigram_match>(d_out + cnt_bytes);
+  BLURRILY_HIP_TRY(hipMemcpyAsync(m->ws_io_in.p, references, n * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+  RefExtract x;                                          // (after every scope's preparation: both use ws_refs)
+  if (refs_extract(m, static_cast<const uint32_t*>(m->ws_io_in.p), n, stream, &x) < 0) return -1;
+  EachNeedles N;
+  N.rn = &x.needles;
+  if (each_run(m, P, N, n, limit, d_rows, d_counts, true, true, stream) < 0) return -1;
+  BLURRILY_HIP_TRY(hipMemcpyAsync(counts, d_counts, n * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+  if (nb_trigrams) BLURRILY_HIP_TRY(hipMemcpyAsync(nb_trigrams, x.needles.ntri, n * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+  if (limit) BLURRILY_HIP_TRY(hipMemcpyAsync(results, d_rows, row_bytes, hipMemcpyDeviceToHost, stream));
+  BLURRILY_HIP_TRY(hipStreamSynchronize(stream));
+  return 0;
+}
+
+}  // extern "C"

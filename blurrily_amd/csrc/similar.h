@@ -10,6 +10,7 @@
 
 #include "../../include/blurrily_storage.h"
 #include "device_index.h"
+#include "segsort.h"
 
 namespace blurrily {
 
@@ -78,27 +79,21 @@ constexpr uint32_t kSimListSmall = 256;    // limits served by the 8 KiB list (t
 constexpr uint32_t kSimListMax   = 1024;   // ... by the 32 KiB list (one a CU); above: all mode
 int launch_similar_sweep(const SimilarArgs& a, hipStream_t stream);
 
-// Sorting key segments ascending (keys are distinct within a segment: the reference is in lo).  tiles: every tile of
-// at most kSimTile keys sorted in LDS, in[start, start + len) -> out[start, ...]; merge: one pass over the segments
-// longer than a tile, every pair of sorted runs of `width` keys merged from in to out (elem_off: exclusive scan of
-// seg_len over the n_segs long segments).
+// Sorting key segments ascending (segsort.h; keys are distinct within a segment: the reference is in lo).
 constexpr uint32_t kSimTile = 2048;
-struct SimilarTile {
-  uint32_t start, len;
+int launch_similar_tiles(const SegTile* tiles, uint32_t n_tiles, const SimilarKey* in, SimilarKey* out, hipStream_t stream);
+int launch_similar_merge(const SegMergeArgs<SimilarKey>& a, hipStream_t stream);
+template <>
+struct SegKey<SimilarKey> {
+  static constexpr uint32_t kTile = kSimTile;
+  static int tiles(const SegTile* t, uint32_t n, const SimilarKey* in, SimilarKey* out, hipStream_t s) {
+    return launch_similar_tiles(t, n, in, out, s);
+  }
+  static int merge(const SegMergeArgs<SimilarKey>& a, hipStream_t s) { return launch_similar_merge(a, s); }
+#ifdef __HIPCC__
+  __device__ static bool less(const SimilarKey& a, const SimilarKey& b) { return a.hi != b.hi ? a.hi < b.hi : a.lo < b.lo; }
+#endif
 };
-int launch_similar_tiles(const SimilarTile* tiles, uint32_t n_tiles, const SimilarKey* in, SimilarKey* out,
-                         hipStream_t stream);
-struct SimilarMergeArgs {
-  const uint32_t*   seg_start;
-  const uint32_t*   seg_len;
-  const uint32_t*   elem_off;
-  uint32_t          n_segs;
-  uint32_t          n_elems;
-  uint32_t          width;
-  const SimilarKey* in;
-  SimilarKey*       out;
-};
-int launch_similar_merge(const SimilarMergeArgs& a, hipStream_t stream);
 
 // Rows from the sorted segments of up to two images, merged per needle and cut at `limit`: needle q's segment in
 // image i is keys[i][off[i][q] .. off[i][q + 1]) (kSimNone keys are no rows).  Row k of needle q goes to

@@ -1,11 +1,13 @@
-// similar.hip -- the similarity find's entry points (include/blurrily_storage.h).  Compiled as
-// one translation unit with above.hip and c_abi.hip, whose map internals (the mutation log, the device images, the
-// string and by-reference front ends) they drive; the kernels are similar_kernels.hip's.
-#include "above.hip"
-
+// similar.hip -- the similarity find's entry points (include/blurrily_storage.h).  They drive the
+// map's internals (map_internal.h: the mutation log, the device images, the string and by-reference front ends);
+// the kernels are similar_kernels.hip's.
 #include <mutex>
 
+#include "map_internal.h"
 #include "similar.h"
+
+using namespace blurrily;
+using namespace blurrily::detail;
 
 namespace {
 
@@ -100,53 +102,12 @@ int similar_table(DeviceIndex* ix, hipStream_t stream, SimilarTables& call, Simi
 int similar_finish(uint32_t n_img, SimilarKey* const keys[2], SimilarKey* const sorted[2], const uint32_t* const d_off[2],
                    const std::vector<uint32_t>* const h_off, const bool need_sort[2], size_t nc, uint32_t limit,
                    SimilarScratch& S, trigram_match d_rows, uint32_t* d_rntri, uint32_t* d_counts, hipStream_t stream) {
-  std::vector<SimilarTile> tiles[2];
-  std::vector<uint32_t> longs[2];                             // seg_start | seg_len | elem_off, each of n_long (+1)
-  uint32_t max_len[2] = {0, 0};
-  for (uint32_t i = 0; i < n_img; ++i) {
-    if (!need_sort[i]) continue;
-    const std::vector<uint32_t>& o = h_off[i];
-    std::vector<uint32_t> st, ln, eo{0};
-    for (size_t q = 0; q < nc; ++q) {
-      const uint32_t len = o[q + 1] - o[q];
-      if (len < 2) continue;
-      for (uint32_t t0 = 0; t0 < len; t0 += kSimTile) tiles[i].push_back(SimilarTile{o[q] + t0, std::min(kSimTile, len - t0)});
-      if (len > kSimTile) { st.push_back(o[q]); ln.push_back(len); eo.push_back(eo.back() + len); }
-      max_len[i] = std::max(max_len[i], len);
-    }
-    longs[i] = st;
-    longs[i].insert(longs[i].end(), ln.begin(), ln.end());
-    longs[i].insert(longs[i].end(), eo.begin(), eo.end());
-  }
-  const size_t tile_bytes = align_up((tiles[0].size() + tiles[1].size()) * sizeof(SimilarTile), 256);
-  if (S.b[4].reserve(tile_bytes + align_up((longs[0].size() + longs[1].size()) * 4, 256) + 256, stream) < 0) return -1;
-  SimilarTile* d_tiles = static_cast<SimilarTile*>(S.b[4].p);
-  uint32_t* d_longs = reinterpret_cast<uint32_t*>(static_cast<unsigned char*>(S.b[4].p) + tile_bytes);
   SimilarRowsArgs r{};
   for (uint32_t i = 0; i < n_img; ++i) {
     r.keys[i] = keys[i]; r.off[i] = d_off[i]; r.n_keys[i] = h_off[i][nc];
     if (!need_sort[i] || h_off[i][nc] == 0) continue;
-    // (the segments shorter than two keys are copied as they are)
-    BLURRILY_HIP_TRY(hipMemcpyAsync(sorted[i], keys[i], size_t(h_off[i][nc]) * sizeof(SimilarKey), hipMemcpyDeviceToDevice, stream));
-    SimilarTile* t_i = d_tiles + (i ? tiles[0].size() : 0);
-    uint32_t* l_i = d_longs + (i ? longs[0].size() : 0);
-    if (!tiles[i].empty())
-      BLURRILY_HIP_TRY(hipMemcpyAsync(t_i, tiles[i].data(), tiles[i].size() * sizeof(SimilarTile), hipMemcpyHostToDevice, stream));
-    if (!longs[i].empty())
-      BLURRILY_HIP_TRY(hipMemcpyAsync(l_i, longs[i].data(), longs[i].size() * 4, hipMemcpyHostToDevice, stream));
-    if (launch_similar_tiles(t_i, uint32_t(tiles[i].size()), keys[i], sorted[i], stream) < 0) return -1;
-    const uint32_t n_long = uint32_t((longs[i].size() - 1) / 3);
-    if (n_long) {
-      SimilarMergeArgs g{l_i, l_i + n_long, l_i + 2 * n_long, n_long, longs[i][3 * n_long], kSimTile, sorted[i], keys[i]};
-      for (; g.width < max_len[i]; g.width *= 2) {
-        if (launch_similar_merge(g, stream) < 0) return -1;
-        std::swap(const_cast<SimilarKey*&>(g.in), g.out);
-      }
-      if (g.in != sorted[i]) {                                // (an odd number of passes: copied back)
-        g.width = 1u << 31;
-        if (launch_similar_merge(g, stream) < 0) return -1;
-      }
-    }
+    // (the segments shorter than two keys are copied as they are; the two images' tables: b[4], b[7])
+    if (segmented_sort(keys[i], sorted[i], h_off[i].data(), nc, 2, true, S.b[i ? 7 : 4], stream) < 0) return -1;
     r.keys[i] = sorted[i];
   }
   r.n_img = n_img; r.n = uint32_t(nc); r.limit = limit;
@@ -155,24 +116,21 @@ int similar_finish(uint32_t n_img, SimilarKey* const keys[2], SimilarKey* const 
 }
 
 // The top-`limit` rows of n needles over the map as it is now: results / row_ntri [n * limit], counts [n].
-int similar_run(trigram_map m, size_t n, const AboveNeedles& N, uint32_t limit, uint32_t min_permille,
+int similar_run(trigram_map m, size_t n, const NeedleView& N, uint32_t limit, uint32_t min_permille,
                 trigram_match results, uint32_t* counts, uint32_t* row_ntri, hipStream_t stream, SimilarScratch& S) {
-  const bool with_delta = !log_of(m)->pending.empty() && m->delta.device >= 0;
-  const uint32_t n_img = with_delta ? 2u : 1u;
-  DeviceIndex* img[2] = {&m->dev, &m->delta};
-  const uint32_t* tomb[2] = {log_of(m)->n_tomb ? m->dev.d_tomb : nullptr, nullptr};
+  const MapImages I = map_images(m);
+  const uint32_t n_img = I.n;
+  const bool with_delta = n_img > 1;
+  DeviceIndex* const* img = I.img;
+  const uint32_t* const* tomb = I.tomb;
   SimilarTables call;
   SimilarTable tab[2];
   for (uint32_t i = 0; i < n_img; ++i)
     if (similar_table(img[i], stream, call, &tab[i]) < 0) return -1;
   const bool all = limit > kSimListMax;
-  // windows per workgroup: a small batch spreads each needle's windows over the GPU, a large one gives a needle one
-  // workgroup; in list mode a needle's lists (tasks * limit keys) fit one tile
+  // windows per workgroup: in list mode a needle's lists (tasks * limit keys) fit one tile
   auto per_of = [&](const DeviceIndex& ix, size_t nc) {
-    const uint64_t want = uint64_t(std::max(m->n_cus, 1)) * 8u;
-    uint64_t per = std::max<uint64_t>(uint64_t(ix.n_windows) * nc / want, 1);
-    if (!all) per = std::max<uint64_t>(per, (ix.n_windows + kSimTile / limit - 1) / (kSimTile / limit));
-    return uint32_t(std::min<uint64_t>(per, std::max<uint32_t>(ix.n_windows, 1)));
+    return windows_per_workgroup(m, ix, nc, all ? 1 : (ix.n_windows + kSimTile / limit - 1) / (kSimTile / limit));
   };
   auto args_of = [&](uint32_t i, size_t s, size_t nc) {
     const DeviceIndex& ix = *img[i];
@@ -342,34 +300,15 @@ int blurrily_storage_find_batch_similar(trigram_map m, const char* packed, const
   }
   DeviceScope scope(m->dev.device);
   hipStream_t stream = nullptr;
-  if (above_ready(m, stream) < 0) return -1;
+  if (map_ready(m, stream) < 0) return -1;
   if (n == 0) return 0;
   if (limit == 0) { std::memset(counts, 0, n * 4); return 0; }
   NameScope names(&m->last_kernels);
   m->last_kernels.clear();
   SimilarScratch S;
-  // the needles up, tokenised by the string path's own front end
-  const size_t packed_bytes = size_t(offsets[n]);
-  const size_t per_n = align_up(n * 4, 256), o_pk = align_up((n + 1) * 8, 256);
-  const size_t o_codes = o_pk + align_up(std::max<size_t>(packed_bytes, 16), 256);
-  const size_t o_ntri = o_codes + align_up((packed_bytes + n) * 2, 256);
-  const size_t bytes = o_ntri + 6 * per_n + 256;
-  if (S.b[6].reserve(bytes, stream) < 0) return -1;
-  unsigned char* b = static_cast<unsigned char*>(S.b[6].p);
-  uint64_t* d_offsets = reinterpret_cast<uint64_t*>(b);
-  char* d_packed = reinterpret_cast<char*>(b + o_pk);
-  uint16_t* d_codes = reinterpret_cast<uint16_t*>(b + o_codes);
-  uint32_t* q = reinterpret_cast<uint32_t*>(b + o_ntri);      // ntri | nb | big | mid | start | (spare) | scalars
-  uint32_t* scalars = reinterpret_cast<uint32_t*>(b + o_ntri + 6 * per_n);
-  BLURRILY_HIP_TRY(hipMemcpyAsync(d_offsets, offsets, (n + 1) * 8, hipMemcpyHostToDevice, stream));
-  if (packed_bytes) BLURRILY_HIP_TRY(hipMemcpyAsync(d_packed, packed, packed_bytes, hipMemcpyHostToDevice, stream));
-  BLURRILY_HIP_TRY(hipMemsetAsync(scalars, 0, 256, stream));
-  const size_t w = per_n / 4;
-  TokeniseArgs t{d_packed, d_offsets, uint32_t(n), m->dev.d_code_total, d_codes, q, q + w, q + 2 * w, scalars,
-                 q + 3 * w, scalars + 1, m->dev.d_start_win, q + 4 * w, 0u};
-  note_launch("tokenise_kernel");
-  if (launch_tokenise(t, stream) < 0) return -1;
-  return similar_run(m, n, AboveNeedles{d_codes, d_offsets, q}, limit, min_permille, results, counts, row_ntri, stream, S);
+  NeedleView N;
+  if (stage_string_needles(m, packed, offsets, n, S.b[6], stream, &N) < 0) return -1;
+  return similar_run(m, n, N, limit, min_permille, results, counts, row_ntri, stream, S);
 }
 
 int blurrily_storage_find_similar(trigram_map m, const char* needle, uint16_t limit, uint32_t min_permille,
@@ -391,22 +330,15 @@ int blurrily_storage_find_references_similar(trigram_map m, const uint32_t* refe
   }
   DeviceScope scope(m->dev.device);
   hipStream_t stream = nullptr;
-  if (above_ready(m, stream) < 0) return -1;
+  if (map_ready(m, stream) < 0) return -1;
   if (n == 0) return 0;
   NameScope names(&m->last_kernels);
   m->last_kernels.clear();
   SimilarScratch S;
-  if (S.b[6].reserve(n * 4, stream) < 0) return -1;
-  BLURRILY_HIP_TRY(hipMemcpyAsync(S.b[6].p, references, n * 4, hipMemcpyHostToDevice, stream));
-  RefExtract x;                                                // the by-reference front end (section 11)
-  if (refs_extract(m, static_cast<const uint32_t*>(S.b[6].p), n, stream, &x) < 0) return -1;
-  if (nb_trigrams) {
-    BLURRILY_HIP_TRY(hipMemcpyAsync(nb_trigrams, x.needles.ntri, n * 4, hipMemcpyDeviceToHost, stream));
-    BLURRILY_HIP_TRY(hipStreamSynchronize(stream));
-  }
+  NeedleView N;
+  if (stage_reference_needles(m, references, n, S.b[6], stream, nb_trigrams, &N) < 0) return -1;
   if (limit == 0) { std::memset(counts, 0, n * 4); return 0; }
-  return similar_run(m, n, AboveNeedles{x.needles.codes, x.needles.qoff, x.needles.ntri}, limit, min_permille, results,
-                     counts, row_ntri, stream, S);
+  return similar_run(m, n, N, limit, min_permille, results, counts, row_ntri, stream, S);
 }
 
 }  // extern "C"

@@ -10,26 +10,13 @@
 // exact key (similar.h); once the list is full its worst row m_k / u_k raises the bar (t = ceil(m_k T / u_k),
 // ceil(m_k T / u_k) <= R <= floor(T u_k / m_k)), and the windows whose range of R holds T are visited first so that
 // it rises early.  All mode (large limits) counts, then writes, every row at or above the floor.
-// similar_tiles_kernel / similar_merge_kernel sort key segments, and similar_rows_kernel merges the base and delta
+// similar_tiles_kernel / seg_merge_kernel (segsort.h) sort key segments, and similar_rows_kernel merges the base and delta
 // images per needle and writes the first `limit` rows.
 #include "similar.h"
-
-#include <cerrno>
-#include <cstdio>
-
-#define BLURRILY_HIP_TRY(expr)                                                        \
-  do {                                                                                \
-    hipError_t e_ = (expr);                                                           \
-    if (e_ != hipSuccess) {                                                           \
-      std::fprintf(stderr, "blurrily_hip: %s failed: %s\n", #expr, hipGetErrorString(e_)); \
-      errno = (e_ == hipErrorOutOfMemory) ? ENOMEM : EIO;                             \
-      return -1;                                                                      \
-    }                                                                                 \
-  } while (0)
+#include "find_kernels.h"
+#include "hip_try.h"
 
 namespace blurrily {
-
-void note_launch(const char* kernel_name);   // (c_abi.hip: the map's last_kernels)
 
 namespace {
 
@@ -39,7 +26,7 @@ constexpr uint32_t kSimWords    = kWindowSize / 4;            // 64 KiB of count
 constexpr uint32_t kSimMaxDense = 64;                         // dense slices of a (needle, window) that may be left out
 
 __device__ inline bool key_less(const SimilarKey& a, const SimilarKey& b) {
-  return a.hi != b.hi ? a.hi < b.hi : a.lo < b.lo;
+  return SegKey<SimilarKey>::less(a, b);
 }
 
 __global__ __launch_bounds__(kSimThreads) void similar_ntri_kernel(const uint2* slice_se, const uint16_t* ent,
@@ -331,10 +318,10 @@ __global__ __launch_bounds__(kSimThreads) void similar_sweep_kernel(SimilarArgs 
 }
 
 // one tile per workgroup: bitonic sort over the next power of two at or above its length, padded with kSimNone
-__global__ __launch_bounds__(256) void similar_tiles_kernel(const SimilarTile* tiles, const SimilarKey* in,
+__global__ __launch_bounds__(256) void similar_tiles_kernel(const SegTile* tiles, const SimilarKey* in,
                                                             SimilarKey* out) {
   __shared__ unsigned long long s_hi[kSimTile], s_lo[kSimTile];
-  const SimilarTile tl = tiles[blockIdx.x];
+  const SegTile tl = tiles[blockIdx.x];
   uint32_t P = 1;
   while (P < tl.len) P <<= 1;
   for (uint32_t i = threadIdx.x; i < P; i += 256u) {
@@ -354,31 +341,6 @@ __global__ __launch_bounds__(256) void similar_tiles_kernel(const SimilarTile* t
       __syncthreads();
     }
   for (uint32_t i = threadIdx.x; i < tl.len; i += 256u) out[size_t(tl.start) + i] = SimilarKey{s_hi[i], s_lo[i]};
-}
-
-// one thread per key of the long segments: its place in the merge of its run with the partner run
-__global__ __launch_bounds__(256) void similar_merge_kernel(SimilarMergeArgs a) {
-  const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= a.n_elems) return;
-  uint32_t lo = 0, hi = a.n_segs;                             // the segment: the last k with elem_off[k] <= e
-  while (hi - lo > 1u) {
-    const uint32_t mid = (lo + hi) / 2u;
-    if (a.elem_off[mid] <= e) lo = mid; else hi = mid;
-  }
-  const uint32_t base = a.seg_start[lo], len = a.seg_len[lo], i = e - a.elem_off[lo];
-  const uint32_t b = i / a.width, p = b ^ 1u;
-  const SimilarKey x = a.in[size_t(base) + i];
-  uint32_t rank = 0;
-  if (size_t(p) * a.width < len) {
-    uint32_t f = p * a.width, l = min(len, f + a.width);
-    const uint32_t first = f;
-    while (f < l) {                                           // partner keys below x (keys are distinct)
-      const uint32_t mid = (f + l) / 2u;
-      if (key_less(a.in[size_t(base) + mid], x)) f = mid + 1u; else l = mid;
-    }
-    rank = f - first;
-  }
-  a.out[size_t(base) + min(b, p) * a.width + (i - b * a.width) + rank] = x;
 }
 
 __global__ __launch_bounds__(256) void similar_rows_kernel(SimilarRowsArgs a) {
@@ -443,8 +405,7 @@ int launch_similar_sweep(const SimilarArgs& a, hipStream_t stream) {
   return 0;
 }
 
-int launch_similar_tiles(const SimilarTile* tiles, uint32_t n_tiles, const SimilarKey* in, SimilarKey* out,
-                         hipStream_t stream) {
+int launch_similar_tiles(const SegTile* tiles, uint32_t n_tiles, const SimilarKey* in, SimilarKey* out, hipStream_t stream) {
   if (n_tiles == 0) return 0;
   note_launch("similar_tiles_kernel");
   hipLaunchKernelGGL(similar_tiles_kernel, dim3(n_tiles), dim3(256), 0, stream, tiles, in, out);
@@ -452,10 +413,10 @@ int launch_similar_tiles(const SimilarTile* tiles, uint32_t n_tiles, const Simil
   return 0;
 }
 
-int launch_similar_merge(const SimilarMergeArgs& a, hipStream_t stream) {
+int launch_similar_merge(const SegMergeArgs<SimilarKey>& a, hipStream_t stream) {
   if (a.n_elems == 0) return 0;
   note_launch("similar_merge_kernel");
-  hipLaunchKernelGGL(similar_merge_kernel, dim3((a.n_elems + 255u) / 256u), dim3(256), 0, stream, a);
+  hipLaunchKernelGGL(seg_merge_kernel<SimilarKey>, dim3((a.n_elems + 255u) / 256u), dim3(256), 0, stream, a);
   BLURRILY_HIP_TRY(hipGetLastError());
   return 0;
 }

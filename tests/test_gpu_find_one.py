@@ -1,4 +1,4 @@
-"""blurrily_storage_find as ONE launch (c_abi.hip: find_one, find_kernels.hip: find_one_kernel) -- the reference's
+"""blurrily_storage_find as ONE launch (host_batch.hip: find_few, find_kernels.hip: find_one_kernel) -- the reference's
 only call shape (ext/blurrily/map_ext.c:131-162 -> storage.c:477-580) -- row for row against the live compiled
 reference (oracle/_ref, where it travelled) or the oracle, and against the batch's way on the same map:
   * hypothesis-generated needles at limits 1 .. 120 on a haystack of five windows full of duplicate words (ties);
@@ -215,7 +215,7 @@ def test_mutations_the_image_has_not_absorbed(geo):
 
 def test_a_handful_of_needles_share_one_launch(geo):
     """blurrily_storage_find_batch with up to "few_max" needles (24; the kernel takes up to 128): one launch, a row of the
-    grid per needle (c_abi.hip: find_few) -- each element still exactly one blurrily_storage_find; needles without a
+    grid per needle (host_batch.hip: find_few) -- each element still exactly one blurrily_storage_find; needles without a
     posting take no row.  Up to sixteen needles travel as kernel arguments and the row's last workgroup merges; more are
     read from the pinned page and the workgroup that finishes last merges (tickets).  Beyond few_max and up to "mid_max"
     (128) needles: latency mode's ranges with the needles read from the pinned page and the merged rows written back

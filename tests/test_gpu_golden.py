@@ -35,7 +35,7 @@ def test_hip_matches_reference_fixture(name):
         rows = (np.zeros((g["limit"], 3), dtype=np.uint32))
         n = m._lib.blurrily_storage_find(m.handle, nd, g["limit"], rows.ctypes.data)
         assert rows[:n].tolist() == want
-    if g["limit"] <= 120:                                            # ... which went as ONE launch (c_abi.hip: find_one)
+    if g["limit"] <= 120:                                            # ... which went as ONE launch (host_batch.hip: find_few)
         assert m.get_option("one_taken") - taken >= sum(1 for w in g["expected"] if w)
 
 

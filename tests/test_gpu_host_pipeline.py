@@ -1,5 +1,5 @@
 """Large host-buffer batches go through blurrily_storage_find_batch in chunks -- needles to the device, search,
-rows back, on three streams, two slots by turns (c_abi.hip: find_batch_chunked).  Every element is still one
+rows back, on three streams, two slots by turns (host_batch.hip: find_batch_chunked).  Every element is still one
 blurrily_storage_find: rows must equal those of the batch taken in one piece, and the oracle's."""
 import numpy as np
 import pytest

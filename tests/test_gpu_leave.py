@@ -1,5 +1,5 @@
 """The needle-major sweep that LEAVES dense slices out of a step's count (find_kernels.hip: sweep_role -- a manager
-wave and fifteen workers; c_abi.hip: sweep 3) against the oracle, row for row.  Once a needle has a threshold, the
+wave and fifteen workers; find_run.hip: sweep 3) against the oracle, row for row.  Once a needle has a threshold, the
 largest slices of at least "nm_dense" postings of a window (at most need - "nm_cmin" of them, four at most) are not
 counted; a reference that could still reach the threshold on its best case waits in the step's pending list and is
 settled through the left-out slices' bitmaps by the manager during the next step (storage.c:545-573 is what it must
@@ -107,7 +107,7 @@ def test_single_words_small_windows_and_latency_mode_is_left_alone():
     # settled candidates' tail (from 150 on) neither; limit 100 does (the 1 024-entry pool, a tail of 256)
     q2, qo2 = W.queries(hay, off, 40, 57)
     rows, counts = m.find_batch_packed(q2, qo2, 10)
-    assert m.last_kernels() == ["find_kernel<uint8_t,1024,true,true>", "merge_parts_pinned_kernel"]   # (over the pinned page: c_abi.hip, find_few)
+    assert m.last_kernels() == ["find_kernel<uint8_t,1024,true,true>", "merge_parts_pinned_kernel"]   # (over the pinned page: host_batch.hip, find_few)
     want = o.batch(q2, qo2, limit=10)
     assert np.array_equal(counts, want["counts"])
     m.set_option("mid_max", 0)                                  # ... and the batch's way, copies and all
@@ -182,7 +182,7 @@ def test_device_info_for_a_caller_of_another_header_version():
 
 
 def test_a_bad_first_sample_of_the_measured_choice_is_corrected(geonames_full):
-    """The sweep that serves a class of batches is MEASURED on the class's first batch (c_abi.hip: run_find_on) -- every
+    """The sweep that serves a class of batches is MEASURED on the class's first batch (find_run.hip: run_find_on) -- every
     sweep twice, the better run counting -- and WATCHED afterwards: two batches of the class in a row that run over 10 %
     slower per needle than the measurement saw have the class measured again.  Here the first measurement is given a bad sample on
     purpose (option "tune_inject": the plain sweep at half its time, which makes it win); the second batch then runs
@@ -216,7 +216,7 @@ def test_a_bad_first_sample_of_the_measured_choice_is_corrected(geonames_full):
 
 def test_mid_size_batches_have_their_sweep_measured_too():
     """Batches of 129 .. 16 383 needles -- a server's coalesced FINDs -- are a class of their own (6; 7 above limit 32)
-    whose first batch measures the sweeps like a large one's (c_abi.hip: run_find_on); smaller batches keep the static
+    whose first batch measures the sweeps like a large one's (find_run.hip: run_find_on); smaller batches keep the static
     rule.  Same rows whatever is chosen."""
     hay, off = W.geonames(700000, 90000, 51)                   # 11 windows: the static rule alone would never leave a slice out
     n = len(off) - 1

@@ -1,4 +1,4 @@
-"""In-process multi-GPU behind the C ABI (option "devices", c_abi.hip: run_find_multi): the device image replicated
+"""In-process multi-GPU behind the C ABI (option "devices", multi_device.hip: run_find_multi): the device image replicated
 on the first n visible devices, a large batch sharded contiguously over them, every replica's block of rows sent
 into the caller's buffers by peer copies.  The drop-in host is ONE process (lib/blurrily/server.rb:19-30), so this is
 how it reaches more than one GPU.  With a single GPU on the box the replicas share it (replica k lives on device

@@ -136,7 +136,7 @@ def test_map_find_batch_mixes_device_and_host_normalisation():
 
 def test_a_handful_of_raw_needles_is_normalised_on_the_host_and_shares_one_launch():
     """blurrily_storage_find_batch_raw with up to "few_max" needles: normalised by the library on the host -- the C++ twin of
-    normalise_kernel -- and served by find_one_kernel's launch (c_abi.hip: normalise_one, find_few): same rows and flags as
+    normalise_kernel -- and served by find_one_kernel's launch (host_batch.hip: normalise_one, find_few): same rows and flags as
     the device's normalisation gives the same needles in a larger batch, and as finds over host-normalised needles."""
     rng = np.random.default_rng(77)
     hay, off = W.geonames(60000, 8000, seed=5)

@@ -1,4 +1,4 @@
-"""By reference on the GPU (c_abi.hip: refs_extract, kernels/refs.inc): blurrily_storage_get gives a stored reference's
+"""By reference on the GPU (refs.hip: refs_extract, kernels/refs.inc): blurrily_storage_get gives a stored reference's
 weight and exactly the tokeniser's codes of the string it was put with, and blurrily_storage_find_references gives, for
 every reference, exactly the oracle's find of that string -- across batch sizes that cross every find path, limits of
 one pass and of several, needles of 1 to more than 127 trigrams, duplicates and absent references, weights that bear no

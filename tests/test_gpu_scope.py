@@ -1,4 +1,4 @@
-"""Scoped find on the GPU (c_abi.hip: scope_prepare / scope_run, kernels/scope.inc): blurrily_storage_find_in and
+"""Scoped find on the GPU (scope.hip: scope_prepare / scope_run, kernels/scope.inc): blurrily_storage_find_in and
 _find_batch_in[_device] return exactly the unbounded find's rows restricted to the scope's members, truncated to the
 limit -- checked against a numpy restatement that is itself anchored on the oracle -- with each strategy forced (mask,
 direct) and auto, across scope sizes, limits, needles at the find path's trigram-class boundaries, batch sizes and

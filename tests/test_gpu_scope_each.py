@@ -1,4 +1,4 @@
-"""A scope per needle on the GPU (c_abi.hip: each_plan / each_run, kernels/scope.inc: scope_each_kernel):
+"""A scope per needle on the GPU (scope.hip: each_plan / each_run, kernels/scope.inc: scope_each_kernel):
 blurrily_storage_find_batch_each_in[_device] and _find_references_each_in return, for needle i, exactly what find_in
 in scopes[which[i]] -- or find, for BLURRILY_NO_SCOPE -- returns for that needle alone.  Checked against a numpy
 restatement anchored on the oracle, against find_in and find_batch, with each strategy forced and auto, across a family

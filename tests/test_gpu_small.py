@@ -1,4 +1,4 @@
-"""The small-haystack sweep (find_kernels.hip: find_small_kernel; c_abi.hip: sweep 4) against the oracle, row for row.
+"""The small-haystack sweep (find_kernels.hip: find_small_kernel; find_run.hip: sweep 4) against the oracle, row for row.
 An image of at most eight windows serves large batches at limits up to 64 with four waves and one window's 4-bit
 counters per needle; needles of 16..64 distinct trigrams are listed by it and follow through the byte-counter kernel.
 What it must compute is what every sweep must (storage.c:477-580): every reference's match count, the best `limit`
