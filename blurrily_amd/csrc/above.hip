@@ -118,7 +118,7 @@ extern "C" {
 int blurrily_storage_find_batch_above(trigram_map m, const char* packed, const uint64_t* offsets, size_t n,
                                       uint32_t min_matches, uint32_t min_permille, trigram_match results,
                                       uint64_t capacity, uint64_t* row_off) {
-  if (!m || !row_off || min_permille > 1000 || (n && (!packed || !offsets)) || n > 0xFFFFFFF0ull) {
+  if (!m || !row_off || min_permille > 1000 || (n && (!packed || !offsets)) || n > kMaxBatchNeedles) {
     errno = EINVAL;
     return -1;
   }
@@ -149,7 +149,7 @@ int blurrily_storage_find_above(trigram_map m, const char* needle, uint32_t min_
 int blurrily_storage_find_references_above(trigram_map m, const uint32_t* references, size_t n, uint32_t min_matches,
                                            uint32_t min_permille, trigram_match results, uint64_t capacity,
                                            uint64_t* row_off, uint32_t* nb_trigrams) {
-  if (!m || !row_off || min_permille > 1000 || (n && !references) || n > 0xFFFFFFF0ull) {
+  if (!m || !row_off || min_permille > 1000 || (n && !references) || n > kMaxBatchNeedles) {
     errno = EINVAL;
     return -1;
   }

@@ -120,9 +120,7 @@ long blurrily_storage_put_many(trigram_map haystack, const char* packed, const u
   long total = 0;
   for (size_t i = 0; i < n; ++i) {
     const char* s = packed + offsets[i];
-    const size_t cap = size_t(offsets[i + 1] - offsets[i]);
-    const void* nul = std::memchr(s, 0, cap);
-    const size_t len = nul ? size_t(static_cast<const char*>(nul) - s) : cap;
+    const size_t len = needle_len(s, size_t(offsets[i + 1] - offsets[i]));
     const int added = haystack->host->put(s, len, references[i], weights ? weights[i] : 0u);
     if (added > 0) log_put(haystack, s, len, references[i], weights ? weights[i] : 0u);
     total += added;
@@ -158,8 +156,6 @@ int blurrily_storage_find_batch_device(trigram_map m, const char* d_packed, size
   DeviceScope scope(m->dev.device);
   if (m->host->dirty_buckets()) m->host->sort_dirty_buckets();
   if (ensure_device(m) < 0) return -1;
-  if (m->timing && !m->ev[0])
-    for (auto& e : m->ev) BLURRILY_HIP_TRY(hipEventCreate(&e));
   if (wants_multi(m, n))
     return run_find_multi(m, d_packed, packed_bytes, d_offsets, n, limit, d_results, d_counts, d_nb_entries,
                           static_cast<hipStream_t>(stream));

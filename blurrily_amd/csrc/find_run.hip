@@ -40,7 +40,7 @@ static int run_find_on(trigram_map m, const DeviceIndex& ix, const uint32_t* d_c
                 trigram_match d_results, uint32_t* d_counts, uint32_t* d_nb, bool maybe_long, bool maybe_mid,
                 hipStream_t stream, const RefNeedles* rn = nullptr, bool scoped = false) {
   if (n == 0) return 0;
-  if (n > 0xFFFFFFF0ull) { errno = EINVAL; return -1; }
+  if (n > kMaxBatchNeedles) { errno = EINVAL; return -1; }
   const bool is_base = &ix == &m->dev;                 // (the delta image of pending puts is searched the same way)
   if (is_base) m->last_sweep = 0;
   NameScope name_scope(is_base ? &m->last_kernels : nullptr);    // the launches below note their kernels' names in the map
@@ -386,6 +386,8 @@ static int run_find_on(trigram_map m, const DeviceIndex& ix, const uint32_t* d_c
 int run_find(trigram_map m, const char* d_packed, size_t packed_bytes, const uint64_t* d_offsets, size_t n,
              uint16_t limit, trigram_match d_results, uint32_t* d_counts, uint32_t* d_nb, bool maybe_long,
              bool maybe_mid, hipStream_t stream, const RefNeedles* rn, const ScopeMasks* sm) {
+  if (m->timing && !m->ev[0])                          // (every timed run_find_on goes through here: its events, at first use)
+    for (auto& e : m->ev) BLURRILY_HIP_TRY(hipEventCreate(&e));
   if (m->collect_stats) {
     if (!m->d_stats) BLURRILY_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&m->d_stats), kStatAllSlots * 8));
     BLURRILY_HIP_TRY(hipMemsetAsync(m->d_stats, 0, kStatAllSlots * 8, stream));
@@ -427,19 +429,18 @@ int run_find(trigram_map m, const char* d_packed, size_t packed_bytes, const uin
 int stage_string_needles(trigram_map m, const char* packed, const uint64_t* offsets, size_t n, DeviceBuffer& buf,
                          hipStream_t stream, NeedleView* out) {
   const size_t packed_bytes = size_t(offsets[n]);
-  const size_t per_n = align_up(n * 4, 256), o_pk = align_up((n + 1) * 8, 256);
-  const size_t o_codes = o_pk + align_up(std::max<size_t>(packed_bytes, 16), 256);
+  const BatchBlocks B(n, packed_bytes, 0, false);             // the needles as a host batch's in block, then the tokeniser's arrays
+  const size_t per_n = align_up(n * 4, 256), o_codes = align_up(B.in_bytes, 256);
   const size_t o_ntri = o_codes + align_up((packed_bytes + n) * 2, 256);
   const size_t bytes = o_ntri + 6 * per_n + 256;
   if (buf.reserve(bytes, stream) < 0) return -1;
   unsigned char* b = static_cast<unsigned char*>(buf.p);
-  uint64_t* d_offsets = reinterpret_cast<uint64_t*>(b);
-  char* d_packed = reinterpret_cast<char*>(b + o_pk);
+  const uint64_t* d_offsets = B.in(b).offsets;
+  char* d_packed = B.in(b).packed;
   uint16_t* d_codes = reinterpret_cast<uint16_t*>(b + o_codes);
   uint32_t* q = reinterpret_cast<uint32_t*>(b + o_ntri);      // ntri | nb | big | mid | start | (spare) | scalars
   uint32_t* scalars = reinterpret_cast<uint32_t*>(b + o_ntri + 6 * per_n);
-  BLURRILY_HIP_TRY(hipMemcpyAsync(d_offsets, offsets, (n + 1) * 8, hipMemcpyHostToDevice, stream));
-  if (packed_bytes) BLURRILY_HIP_TRY(hipMemcpyAsync(d_packed, packed, packed_bytes, hipMemcpyHostToDevice, stream));
+  if (B.copy_in(b, packed, offsets, stream) < 0) return -1;
   BLURRILY_HIP_TRY(hipMemsetAsync(scalars, 0, 256, stream));
   const size_t w = per_n / 4;
   TokeniseArgs t{d_packed, d_offsets, uint32_t(n), m->dev.d_code_total, d_codes, q, q + w, q + 2 * w, scalars,

@@ -26,11 +26,8 @@ static int find_batch_chunked_run(trigram_map m, const char* packed, const uint6
     const size_t b = std::min(n, a + chunk);
     max_packed = std::max<size_t>(max_packed, size_t(offsets[b] - offsets[a]));
   }
-  const size_t off_cap = align_up((chunk + 1) * sizeof(uint64_t), 256);
-  const size_t cnt_cap = align_up(chunk * sizeof(uint32_t), 256);
-  const size_t flag_cap = raw ? cnt_cap : 0;
-  const size_t in_cap = off_cap + std::max<size_t>(max_packed, 16);
-  const size_t out_cap = cnt_cap + flag_cap + std::max<size_t>(chunk * size_t(limit) * sizeof(trigram_match_t), 16);
+  const BatchBlocks C(chunk, max_packed, limit, raw);           // (a short last chunk keeps the full chunk's layout)
+  const size_t in_cap = C.in_bytes, out_cap = C.out_bytes;
   if (P.h_in_bytes < in_cap || P.h_out_bytes < out_cap) {
     BLURRILY_HIP_TRY(hipDeviceSynchronize());
     for (int i = 0; i < 2; ++i) {
@@ -56,10 +53,10 @@ static int find_batch_chunked_run(trigram_map m, const char* packed, const uint6
     if (sp.b == sp.a) return 0;
     BLURRILY_HIP_TRY(hipEventSynchronize(P.ev_out[i]));
     const size_t c = sp.b - sp.a;
-    std::memcpy(counts + sp.a, P.h_out[i], c * sizeof(uint32_t));
-    if (raw && non_ascii) std::memcpy(non_ascii + sp.a, P.h_out[i] + cnt_cap, c * sizeof(uint32_t));
-    if (limit)
-      std::memcpy(results + sp.a * size_t(limit), P.h_out[i] + cnt_cap + flag_cap, c * size_t(limit) * sizeof(trigram_match_t));
+    const BatchBlocks::Out h = C.out(P.h_out[i]);
+    std::memcpy(counts + sp.a, h.counts, c * sizeof(uint32_t));
+    if (raw && non_ascii) std::memcpy(non_ascii + sp.a, h.flags, c * sizeof(uint32_t));
+    if (limit) std::memcpy(results + sp.a * size_t(limit), h.rows, c * size_t(limit) * sizeof(trigram_match_t));
     in_slot[i] = {0, 0};
     return 0;
   };
@@ -71,36 +68,26 @@ static int find_batch_chunked_run(trigram_map m, const char* packed, const uint6
     // ---- stage chunk k: offsets rebased to the chunk, its needles; how long they can be --------------
     uint64_t* h_off = reinterpret_cast<uint64_t*>(P.h_in[i]);
     const uint64_t base = offsets[a];
-    size_t max_len = 0;
     for (size_t j = 0; j <= c; ++j) h_off[j] = offsets[a + j] - base;
     const size_t bytes = size_t(offsets[b] - base);
-    if (bytes) std::memcpy(P.h_in[i] + off_cap, packed + base, bytes);
-    for (size_t j = 0; j < c && max_len <= 126; ++j) {            // (what the launches need to know: > 63, > 126)
-      const size_t cap = size_t(h_off[j + 1] - h_off[j]);
-      if (cap <= max_len) continue;
-      const char* s = packed + base + h_off[j];
-      const void* nul = std::memchr(s, 0, cap);
-      max_len = std::max(max_len, nul ? size_t(static_cast<const char*>(nul) - s) : cap);
-    }
+    if (bytes) std::memcpy(P.h_in[i] + C.o_packed, packed + base, bytes);
+    const size_t max_len = longest_needle(packed + base, h_off, c);
     unsigned char* d_in = static_cast<unsigned char*>(P.d_in[i].p);
     unsigned char* d_out = static_cast<unsigned char*>(P.d_out[i].p);
-    BLURRILY_HIP_TRY(hipMemcpyAsync(d_in, P.h_in[i], off_cap + std::max<size_t>(bytes, 16), hipMemcpyHostToDevice, P.s_in));
+    BLURRILY_HIP_TRY(hipMemcpyAsync(d_in, P.h_in[i], C.o_packed + std::max<size_t>(bytes, 16), hipMemcpyHostToDevice, P.s_in));
     BLURRILY_HIP_TRY(hipEventRecord(P.ev_in[i], P.s_in));
     // ---- search it ---------------------------------------------------------------------------------
     BLURRILY_HIP_TRY(hipStreamWaitEvent(P.s_run, P.ev_in[i], 0));
-    const uint64_t* d_offsets = reinterpret_cast<const uint64_t*>(d_in);
-    char* d_packed = reinterpret_cast<char*>(d_in + off_cap);
-    uint32_t* d_counts = reinterpret_cast<uint32_t*>(d_out);
-    uint32_t* d_flags = reinterpret_cast<uint32_t*>(d_out + cnt_cap);
-    trigram_match d_rows = reinterpret_cast<trigram_match>(d_out + cnt_cap + flag_cap);
-    if (raw && launch_normalise(d_packed, d_offsets, uint32_t(c), d_packed, d_flags, P.s_run) < 0) return -1;
-    if (run_find(m, d_packed, bytes, d_offsets, c, limit, d_rows, d_counts, nullptr, max_len > 126, max_len > 63,
+    const BatchBlocks::In in = C.in(d_in);
+    const BatchBlocks::Out out = C.out(d_out);
+    if (raw && launch_normalise(in.packed, in.offsets, uint32_t(c), in.packed, out.flags, P.s_run) < 0) return -1;
+    if (run_find(m, in.packed, bytes, in.offsets, c, limit, out.rows, out.counts, nullptr, max_len > 126, max_len > 63,
                  P.s_run) < 0)
       return -1;
     BLURRILY_HIP_TRY(hipEventRecord(P.ev_run[i], P.s_run));
     // ---- and send its rows home ----------------------------------------------------------------------
     BLURRILY_HIP_TRY(hipStreamWaitEvent(P.s_out, P.ev_run[i], 0));
-    BLURRILY_HIP_TRY(hipMemcpyAsync(P.h_out[i], d_out, cnt_cap + flag_cap + c * size_t(limit) * sizeof(trigram_match_t),
+    BLURRILY_HIP_TRY(hipMemcpyAsync(P.h_out[i], d_out, C.o_rows + c * size_t(limit) * sizeof(trigram_match_t),
                                     hipMemcpyDeviceToHost, P.s_out));
     BLURRILY_HIP_TRY(hipEventRecord(P.ev_out[i], P.s_out));
     in_slot[i] = {a, b};
@@ -155,12 +142,63 @@ size_t normalise_one(const char* in, size_t cap, char* out, uint32_t* high_out) 
     if (c != 0) keep = w;
   }
   if (high_out) *high_out = high;
-  const void* nul = std::memchr(out, 0, keep);
-  return nul ? size_t(static_cast<const char*>(nul) - out) : keep;
+  return needle_len(out, keep);
 }
 
 namespace blurrily {
 namespace detail {
+
+size_t needle_len(const char* s, size_t cap) {
+  const void* nul = std::memchr(s, 0, cap);
+  return nul ? size_t(static_cast<const char*>(nul) - s) : cap;
+}
+
+size_t longest_needle(const char* packed, const uint64_t* offsets, size_t n) {
+  size_t max_len = 0;
+  for (size_t i = 0; i < n && max_len <= 126; ++i) {
+    const size_t cap = size_t(offsets[i + 1] - offsets[i]);
+    if (cap > max_len) max_len = std::max(max_len, needle_len(packed + offsets[i], cap));
+  }
+  return max_len;
+}
+
+BatchBlocks::BatchBlocks(size_t n, size_t packed_bytes_, uint16_t limit, bool flags)
+    : off_bytes((n + 1) * sizeof(uint64_t)), packed_bytes(packed_bytes_), cnt_bytes(n * sizeof(uint32_t)),
+      row_bytes(n * size_t(limit) * sizeof(trigram_match_t)),
+      o_packed(align_up(off_bytes, 256)), in_bytes(o_packed + std::max<size_t>(packed_bytes, 16)),
+      o_flags(align_up(cnt_bytes, 256)), o_rows(o_flags + (flags ? o_flags : 0)),
+      out_bytes(o_rows + std::max<size_t>(row_bytes, 16)) {}
+
+BatchBlocks::In BatchBlocks::in(unsigned char* base) const {
+  return In{reinterpret_cast<const uint64_t*>(base), reinterpret_cast<char*>(base + o_packed)};
+}
+BatchBlocks::Out BatchBlocks::out(unsigned char* base) const {
+  return Out{reinterpret_cast<uint32_t*>(base), reinterpret_cast<uint32_t*>(base + o_flags),
+             reinterpret_cast<trigram_match>(base + o_rows)};
+}
+void BatchBlocks::fill_in(unsigned char* h_in, const char* packed, const uint64_t* offsets) const {
+  std::memcpy(h_in, offsets, off_bytes);
+  if (packed_bytes) std::memcpy(h_in + o_packed, packed, packed_bytes);
+}
+int BatchBlocks::copy_in(unsigned char* d_in, const char* packed, const uint64_t* offsets, hipStream_t stream) const {
+  BLURRILY_HIP_TRY(hipMemcpyAsync(d_in, offsets, off_bytes, hipMemcpyHostToDevice, stream));
+  if (packed_bytes)
+    BLURRILY_HIP_TRY(hipMemcpyAsync(d_in + o_packed, packed, packed_bytes, hipMemcpyHostToDevice, stream));
+  return 0;
+}
+void BatchBlocks::take_out(const Out& h, uint32_t* counts, uint32_t* flags, trigram_match results) const {
+  std::memcpy(counts, h.counts, cnt_bytes);
+  if (flags) std::memcpy(flags, h.flags, cnt_bytes);
+  if (row_bytes) std::memcpy(results, h.rows, row_bytes);
+}
+int BatchBlocks::copy_out(const uint32_t* d_counts, const uint32_t* d_flags, const trigram_match_t* d_rows,
+                          uint32_t* counts, uint32_t* flags, trigram_match results, hipStream_t stream) const {
+  BLURRILY_HIP_TRY(hipMemcpyAsync(counts, d_counts, cnt_bytes, hipMemcpyDeviceToHost, stream));
+  if (flags) BLURRILY_HIP_TRY(hipMemcpyAsync(flags, d_flags, cnt_bytes, hipMemcpyDeviceToHost, stream));
+  if (row_bytes) BLURRILY_HIP_TRY(hipMemcpyAsync(results, d_rows, row_bytes, hipMemcpyDeviceToHost, stream));
+  BLURRILY_HIP_TRY(hipStreamSynchronize(stream));
+  return 0;
+}
 
 // Host-buffer batch: needles in, rows out.  raw = the needles are un-normalised ASCII (see
 // blurrily_storage_find_batch_raw); non_ascii (raw only, may be null) receives the per-needle flags.
@@ -186,8 +224,7 @@ int find_batch_host(trigram_map m, const char* packed, const uint64_t* offsets, 
         if (non_ascii) non_ascii[i] = high;
       } else {
         s[i] = packed + offsets[i];
-        const void* nul = std::memchr(s[i], 0, cap);
-        len[i] = nul ? size_t(static_cast<const char*>(nul) - s[i]) : cap;
+        len[i] = needle_len(s[i], cap);
       }
     }
     if (fits) {
@@ -202,9 +239,7 @@ int find_batch_host(trigram_map m, const char* packed, const uint64_t* offsets, 
   std::vector<uint16_t> codes;
   for (size_t i = 0; i < n; ++i) {
     const char* s = packed + offsets[i];
-    const size_t cap = size_t(offsets[i + 1] - offsets[i]);
-    const void* nul = std::memchr(s, 0, cap);
-    const size_t len = nul ? size_t(static_cast<const char*>(nul) - s) : cap;
+    const size_t len = needle_len(s, size_t(offsets[i + 1] - offsets[i]));
     max_len = std::max(max_len, len);
     if (any_dirty && !raw) {
       codes.resize(len + 1);
@@ -215,8 +250,6 @@ int find_batch_host(trigram_map m, const char* packed, const uint64_t* offsets, 
   // (raw needles are only normalised on the device: sort every dirty bucket, as the device entry does)
   if (any_dirty && raw) m->host->sort_dirty_buckets();
   if (ensure_device(m) < 0) return -1;
-  if (m->timing && !m->ev[0])
-    for (auto& e : m->ev) BLURRILY_HIP_TRY(hipEventCreate(&e));
   // (timing and request counters describe ONE launch sequence: those runs stay in one piece)
   const bool multi = wants_multi(m, n);   // (the batch then goes in one piece through the primary: its rows come home over ONE PCIe link)
   if (!multi && m->host_chunk && n >= 2 * size_t(m->host_chunk) && !m->timing && !m->collect_stats) {
@@ -227,56 +260,33 @@ int find_batch_host(trigram_map m, const char* packed, const uint64_t* offsets, 
   }
 
   hipStream_t stream = nullptr;
-  const size_t packed_bytes = size_t(offsets[n]);
-  const size_t off_bytes = (n + 1) * sizeof(uint64_t);
-  const size_t row_bytes = n * size_t(limit) * sizeof(trigram_match_t);
-  const size_t cnt_bytes = n * sizeof(uint32_t);
-  // one device block in ([offsets | needles]) and one out ([counts | rows])
-  const size_t in_bytes = align_up(off_bytes, 256) + std::max<size_t>(packed_bytes, 16);
-  const size_t flag_bytes = raw ? align_up(cnt_bytes, 256) : 0;          // [counts | flags | rows]
-  const size_t out_bytes = align_up(cnt_bytes, 256) + flag_bytes + std::max<size_t>(row_bytes, 16);
-  if (m->ws_io_in.reserve(in_bytes, stream) < 0 || m->ws_io_out.reserve(out_bytes, stream) < 0) return -1;
+  const BatchBlocks B(n, size_t(offsets[n]), limit, raw);
+  if (m->ws_io_in.reserve(B.in_bytes, stream) < 0 || m->ws_io_out.reserve(B.out_bytes, stream) < 0) return -1;
   unsigned char* d_in = static_cast<unsigned char*>(m->ws_io_in.p);
   unsigned char* d_out = static_cast<unsigned char*>(m->ws_io_out.p);
-  const uint64_t* d_offsets = reinterpret_cast<const uint64_t*>(d_in);
-  char* d_packed = reinterpret_cast<char*>(d_in + align_up(off_bytes, 256));
-  uint32_t* d_counts = reinterpret_cast<uint32_t*>(d_out);
-  uint32_t* d_flags = reinterpret_cast<uint32_t*>(d_out + align_up(cnt_bytes, 256));
-  trigram_match d_rows = reinterpret_cast<trigram_match>(d_out + align_up(cnt_bytes, 256) + flag_bytes);
+  const BatchBlocks::In in = B.in(d_in);
+  const BatchBlocks::Out out = B.out(d_out);
 
   // Small batches (the single blurrily_storage_find above all) go through pinned staging: one
   // copy in, one copy out, instead of four pageable ones.
-  const bool staged = in_bytes <= kStageBytes && out_bytes <= kStageBytes;
+  const bool staged = B.in_bytes <= kStageBytes && B.out_bytes <= kStageBytes;
   if (staged && !m->h_stage) BLURRILY_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&m->h_stage), 2 * kStageBytes));
   if (staged) {
-    unsigned char* h_in = m->h_stage;
-    std::memcpy(h_in, offsets, off_bytes);
-    if (packed_bytes) std::memcpy(h_in + align_up(off_bytes, 256), packed, packed_bytes);
-    BLURRILY_HIP_TRY(hipMemcpyAsync(d_in, h_in, in_bytes, hipMemcpyHostToDevice, stream));
-  } else {
-    BLURRILY_HIP_TRY(hipMemcpyAsync(d_in, offsets, off_bytes, hipMemcpyHostToDevice, stream));
-    if (packed_bytes)
-      BLURRILY_HIP_TRY(hipMemcpyAsync(d_in + align_up(off_bytes, 256), packed, packed_bytes, hipMemcpyHostToDevice,
-                                      stream));
+    B.fill_in(m->h_stage, packed, offsets);
+    BLURRILY_HIP_TRY(hipMemcpyAsync(d_in, m->h_stage, B.in_bytes, hipMemcpyHostToDevice, stream));
+  } else if (B.copy_in(d_in, packed, offsets, stream) < 0) {
+    return -1;
   }
-  if (raw && launch_normalise(d_packed, d_offsets, uint32_t(n), d_packed, d_flags, stream) < 0) return -1;
-  if ((multi ? run_find_multi(m, d_packed, packed_bytes, d_offsets, n, limit, d_rows, d_counts, nullptr, stream)
-             : run_find(m, d_packed, packed_bytes, d_offsets, n, limit, d_rows, d_counts, nullptr, max_len > 126,
+  if (raw && launch_normalise(in.packed, in.offsets, uint32_t(n), in.packed, out.flags, stream) < 0) return -1;
+  if ((multi ? run_find_multi(m, in.packed, B.packed_bytes, in.offsets, n, limit, out.rows, out.counts, nullptr, stream)
+             : run_find(m, in.packed, B.packed_bytes, in.offsets, n, limit, out.rows, out.counts, nullptr, max_len > 126,
                         max_len > 63, stream)) < 0)
     return -1;
-  if (staged) {
-    unsigned char* h_out = m->h_stage + kStageBytes;
-    BLURRILY_HIP_TRY(hipMemcpyAsync(h_out, d_out, out_bytes, hipMemcpyDeviceToHost, stream));
-    BLURRILY_HIP_TRY(hipStreamSynchronize(stream));
-    std::memcpy(counts, h_out, cnt_bytes);
-    if (raw && non_ascii) std::memcpy(non_ascii, h_out + align_up(cnt_bytes, 256), cnt_bytes);
-    if (limit) std::memcpy(results, h_out + align_up(cnt_bytes, 256) + flag_bytes, row_bytes);
-  } else {
-    BLURRILY_HIP_TRY(hipMemcpyAsync(counts, d_counts, cnt_bytes, hipMemcpyDeviceToHost, stream));
-    if (raw && non_ascii) BLURRILY_HIP_TRY(hipMemcpyAsync(non_ascii, d_flags, cnt_bytes, hipMemcpyDeviceToHost, stream));
-    if (limit) BLURRILY_HIP_TRY(hipMemcpyAsync(results, d_rows, row_bytes, hipMemcpyDeviceToHost, stream));
-    BLURRILY_HIP_TRY(hipStreamSynchronize(stream));
-  }
+  if (!staged) return B.copy_out(out.counts, out.flags, out.rows, counts, raw ? non_ascii : nullptr, results, stream);
+  unsigned char* h_out = m->h_stage + kStageBytes;
+  BLURRILY_HIP_TRY(hipMemcpyAsync(h_out, d_out, B.out_bytes, hipMemcpyDeviceToHost, stream));
+  BLURRILY_HIP_TRY(hipStreamSynchronize(stream));
+  B.take_out(B.out(h_out), counts, raw ? non_ascii : nullptr, results);
   return 0;
 }
 

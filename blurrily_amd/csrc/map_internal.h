@@ -3,10 +3,11 @@
 // declared in blurrily::detail has hidden visibility: none of it is a dynamic symbol of libblurrily_hip.so.
 //   c_abi.hip        lifecycle, put / delete / save / stats, find / find_batch entries, options, debug entries
 //   map_log.hip      the mutation log: ensure_device, apply_tombstones, map_ready, map_images
-//   find_run.hip     the batch search's launch logic: run_find_on, run_find; stage_string_needles
+//   find_run.hip     the batch search's launch logic: run_find_on, run_find (the timing events); stage_string_needles
 //   multi_device.hip replicas, run_find_multi
-//   host_batch.hip   host-buffer batches: the chunked pipeline, find_batch_host, find_few
-//   refs.hip         by reference: refs_extract, stage_reference_needles, get / find_references entries
+//   host_batch.hip   host-buffer batches: needle_len, longest_needle, BatchBlocks; the chunked pipeline,
+//                    find_batch_host, find_few
+//   refs.hip         by reference: refs_extract, ExtractionOnHost, stage_reference_needles, get / find_references entries
 //   scope.hip        scoped find, a scope per needle
 //   above.hip, similar.hip   the threshold and similarity finds (their shared sort: segsort.h)
 #pragma once
@@ -210,6 +211,7 @@ namespace blurrily {
 namespace detail __attribute__((visibility("hidden"))) {
 
 constexpr size_t kPhaseWorkgroups = 8192, kPhaseBytes = kPhaseWorkgroups * 16 * 8;
+constexpr uint64_t kMaxBatchNeedles = 0xFFFFFFF0ull;   // needles (or references) a call takes: the kernels count them in 32 bits
 
 // ---- map_log.hip ------------------------------------------------------------------------------------------------------
 size_t log_budget(const trigram_map m);
@@ -242,6 +244,32 @@ int find_few(trigram_map m, const char* const* s, const size_t* len, size_t n, u
              uint32_t* counts);
 int find_batch_host(trigram_map m, const char* packed, const uint64_t* offsets, size_t n, uint16_t limit,
                     trigram_match results, uint32_t* counts, bool raw, uint32_t* non_ascii);
+// A needle's length: up to its first NUL among its `cap` bytes (where the tokeniser stops).
+size_t needle_len(const char* s, size_t cap);
+// The longest of n packed needles, as far as the launches need to know it (> 63, > 126): the scan stops beyond 126.
+size_t longest_needle(const char* packed, const uint64_t* offsets, size_t n);
+
+// The two blocks a host-buffer batch of n needles travels in: [offsets | needles] in, [counts | (flags) | rows] out
+// (flags: a raw batch's non-ASCII flags, a by-reference batch's trigram counts).  The layout is the same whatever backs
+// the blocks: device scratch with pageable copies (copy_in / copy_out), or pinned or mapped host memory the caller
+// copies in one piece or not at all (fill_in / take_out).  A by-reference batch, whose references go in alone, uses the
+// out block only.
+struct BatchBlocks {
+  struct In  { const uint64_t* offsets; char* packed; };
+  struct Out { uint32_t* counts; uint32_t* flags; trigram_match rows; };
+  size_t off_bytes, packed_bytes, cnt_bytes, row_bytes;
+  size_t o_packed, in_bytes, o_flags, o_rows, out_bytes;
+  BatchBlocks(size_t n, size_t packed_bytes, uint16_t limit, bool flags);
+  In  in(unsigned char* base) const;
+  Out out(unsigned char* base) const;
+  void fill_in(unsigned char* h_in, const char* packed, const uint64_t* offsets) const;
+  int  copy_in(unsigned char* d_in, const char* packed, const uint64_t* offsets, hipStream_t stream) const;
+  // counts, the flags (where the caller wants them) and the rows to the caller; copy_out synchronises the stream
+  // (d_flags: the block's, or a by-reference call's trigram counts where the extraction left them)
+  void take_out(const Out& h, uint32_t* counts, uint32_t* flags, trigram_match results) const;
+  int  copy_out(const uint32_t* d_counts, const uint32_t* d_flags, const trigram_match_t* d_rows, uint32_t* counts,
+                uint32_t* flags, trigram_match results, hipStream_t stream) const;
+};
 
 // The needles of a call as the threshold and similarity sweeps read them (the front ends' layout: tokenise_kernel,
 // refs_extract): needle q's ntri[q] distinct codes at codes + qoff[q] + q.
@@ -286,6 +314,25 @@ struct RefExtract {
   bool            with_delta;
 };
 int refs_extract(trigram_map m, const uint32_t* d_refs, size_t n, hipStream_t stream, RefExtract* out);
+
+// An extraction read back to the host, in the steps its readers need: the counts and weights (enqueued: the caller
+// may have more to enqueue before it waits), where each reference's codes sit and how many there are in all (waits
+// for the stream), the codes themselves.
+struct ExtractionOnHost {
+  RefExtract x;
+  size_t n;
+  std::vector<uint32_t> ntri, weight;
+  std::vector<uint64_t> qoff;                            // (sized by read_offsets: a scope of every reference never reads them)
+  std::vector<uint16_t> all;                             // every distinct reference's codes once, behind the pad of n
+  uint64_t total = 0;
+  bool have_offsets = false, have_codes = false;
+  explicit ExtractionOnHost(size_t n_refs) : n(n_refs), ntri(n), weight(n) {}
+  int enqueue_counts(const RefExtract& from, hipStream_t stream);
+  int read_offsets(hipStream_t stream);
+  int read_codes(hipStream_t stream);                    // (the offsets first, unless they are here already)
+  // (on the device reference i's codes sit at codes + qoff[i] + i, as a needle's do; `all` starts behind the pad)
+  const uint16_t* codes_of(size_t i) const { return all.data() + (qoff[i] + i - n); }
+};
 
 }  // namespace detail
 }  // namespace blurrily

@@ -14,10 +14,8 @@ namespace blurrily {
 namespace detail {
 
 int refs_extract(trigram_map m, const uint32_t* d_refs, size_t n, hipStream_t stream, RefExtract* out) {
-  if (n > 0xFFFFFFF0ull) { errno = EINVAL; return -1; }
-  if (m->host->dirty_buckets()) m->host->sort_dirty_buckets();   // (a find's needles would: as the device entry does)
-  if (ensure_device(m) < 0) return -1;
-  if (apply_tombstones(m, stream) < 0) return -1;
+  if (n > kMaxBatchNeedles) { errno = EINVAL; return -1; }
+  if (map_ready(m, stream) < 0) return -1;             // (every dirty bucket sorted: a find's needles would, as the device entry does)
   const bool with_delta = !log_of(m)->pending.empty() && m->delta.device >= 0;
   if (device_index_ensure_ref_table(&m->dev) < 0 || (with_delta && device_index_ensure_ref_table(&m->delta) < 0)) return -1;
   const uint32_t W = m->dev.n_windows + (with_delta ? m->delta.n_windows : 0u);
@@ -61,6 +59,33 @@ int refs_extract(trigram_map m, const uint32_t* d_refs, size_t n, hipStream_t st
   return 0;
 }
 
+int ExtractionOnHost::enqueue_counts(const RefExtract& from, hipStream_t stream) {
+  x = from;
+  BLURRILY_HIP_TRY(hipMemcpyAsync(ntri.data(), x.needles.ntri, n * 4, hipMemcpyDeviceToHost, stream));
+  BLURRILY_HIP_TRY(hipMemcpyAsync(weight.data(), x.needles.weight, n * 4, hipMemcpyDeviceToHost, stream));
+  return 0;
+}
+
+int ExtractionOnHost::read_offsets(hipStream_t stream) {
+  uint64_t slots = 0;
+  qoff = std::vector<uint64_t>(n);
+  BLURRILY_HIP_TRY(hipMemcpyAsync(qoff.data(), x.needles.qoff, n * 8, hipMemcpyDeviceToHost, stream));
+  BLURRILY_HIP_TRY(hipMemcpyAsync(&slots, x.win_base_total, 8, hipMemcpyDeviceToHost, stream));
+  BLURRILY_HIP_TRY(hipStreamSynchronize(stream));
+  BLURRILY_HIP_TRY(hipMemcpy(&total, x.slot_start + slots, 8, hipMemcpyDeviceToHost));
+  have_offsets = true;
+  return 0;
+}
+
+int ExtractionOnHost::read_codes(hipStream_t stream) {
+  if (have_codes) return 0;
+  if (!have_offsets && read_offsets(stream) < 0) return -1;
+  all = std::vector<uint16_t>(total);
+  if (total) BLURRILY_HIP_TRY(hipMemcpy(all.data(), x.needles.codes + n, total * sizeof(uint16_t), hipMemcpyDeviceToHost));
+  have_codes = true;
+  return 0;
+}
+
 // The by-reference front end of the threshold and similarity finds: host references up and extracted.
 int stage_reference_needles(trigram_map m, const uint32_t* references, size_t n, DeviceBuffer& buf, hipStream_t stream,
                             uint32_t* nb_trigrams, NeedleView* out) {
@@ -98,25 +123,17 @@ int blurrily_storage_get_batch(trigram_map m, const uint32_t* references, size_t
   BLURRILY_HIP_TRY(hipMemcpyAsync(m->ws_io_in.p, references, n * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
   RefExtract x;
   if (refs_extract(m, static_cast<const uint32_t*>(m->ws_io_in.p), n, stream, &x) < 0) return -1;
-  std::vector<uint32_t> ntri(n), wgt(n);
-  std::vector<uint64_t> qoff(n);
-  uint64_t slots = 0, total = 0;
-  BLURRILY_HIP_TRY(hipMemcpyAsync(ntri.data(), x.needles.ntri, n * 4, hipMemcpyDeviceToHost, stream));
-  BLURRILY_HIP_TRY(hipMemcpyAsync(wgt.data(), x.needles.weight, n * 4, hipMemcpyDeviceToHost, stream));
-  BLURRILY_HIP_TRY(hipMemcpyAsync(qoff.data(), x.needles.qoff, n * 8, hipMemcpyDeviceToHost, stream));
-  BLURRILY_HIP_TRY(hipMemcpyAsync(&slots, x.win_base_total, 8, hipMemcpyDeviceToHost, stream));
-  BLURRILY_HIP_TRY(hipStreamSynchronize(stream));
-  BLURRILY_HIP_TRY(hipMemcpy(&total, x.slot_start + slots, 8, hipMemcpyDeviceToHost));
+  ExtractionOnHost R(n);
+  if (R.enqueue_counts(x, stream) < 0 || R.read_offsets(stream) < 0) return -1;
   code_offsets[0] = 0;
-  for (size_t i = 0; i < n; ++i) code_offsets[i + 1] = code_offsets[i] + ntri[i];
+  for (size_t i = 0; i < n; ++i) code_offsets[i + 1] = code_offsets[i] + R.ntri[i];
   if (weights)
-    for (size_t i = 0; i < n; ++i) weights[i] = ntri[i] ? wgt[i] : 0u;
+    for (size_t i = 0; i < n; ++i) weights[i] = R.ntri[i] ? R.weight[i] : 0u;
   if (code_offsets[n] > codes_cap) { errno = ERANGE; return -1; }
   if (code_offsets[n] == 0) return 0;
-  std::vector<uint16_t> all(total);                      // every distinct reference's codes once, behind the pad of n
-  BLURRILY_HIP_TRY(hipMemcpy(all.data(), x.needles.codes + n, total * sizeof(uint16_t), hipMemcpyDeviceToHost));
+  if (R.read_codes(stream) < 0) return -1;
   for (size_t i = 0; i < n; ++i)
-    if (ntri[i]) std::memcpy(codes + code_offsets[i], all.data() + (qoff[i] + i - n), size_t(ntri[i]) * sizeof(uint16_t));
+    if (R.ntri[i]) std::memcpy(codes + code_offsets[i], R.codes_of(i), size_t(R.ntri[i]) * sizeof(uint16_t));
   return 0;
 }
 
@@ -141,8 +158,6 @@ int blurrily_storage_find_references_device(trigram_map m, const uint32_t* d_ref
   if (n == 0) return ensure_device(m);
   RefExtract x;
   if (refs_extract(m, d_references, n, st, &x) < 0) return -1;
-  if (m->timing && !m->ev[0])
-    for (auto& e : m->ev) BLURRILY_HIP_TRY(hipEventCreate(&e));
   // (the primary alone, whatever "devices" says; the rows do not depend on it)
   if (run_find(m, nullptr, 0, nullptr, n, limit, d_results, d_counts, nullptr, true, true, st, &x.needles) < 0) return -1;
   if (d_nb_trigrams)
@@ -155,26 +170,18 @@ int blurrily_storage_find_references(trigram_map m, const uint32_t* references, 
   if (!m || (n && (!references || !counts || (limit && !results)))) { errno = EINVAL; return -1; }
   DeviceScope scope(m->dev.device);
   if (n == 0) return ensure_device(m);
+  // (the image before the blocks, as in get_batch: without a GPU that is what fails, with ENODEV)
   if (m->host->dirty_buckets()) m->host->sort_dirty_buckets();
   if (ensure_device(m) < 0) return -1;
   hipStream_t stream = nullptr;
-  const size_t row_bytes = n * size_t(limit) * sizeof(trigram_match_t), cnt_bytes = align_up(n * sizeof(uint32_t), 256);
-  if (m->ws_io_in.reserve(n * sizeof(uint32_t), stream) < 0 ||
-      m->ws_io_out.reserve(2 * cnt_bytes + std::max<size_t>(row_bytes, 16), stream) < 0)
-    return -1;
-  unsigned char* d_out = static_cast<unsigned char*>(m->ws_io_out.p);
-  uint32_t* d_counts = reinterpret_cast<uint32_t*>(d_out);
-  uint32_t* d_ntri = reinterpret_cast<uint32_t*>(d_out + cnt_bytes);
-  trigram_match d_rows = reinterpret_cast<trigram_match>(d_out + 2 * cnt_bytes);
+  const BatchBlocks B(n, 0, limit, true);               // (the references go in alone; out: [counts | nb_trigrams | rows])
+  if (m->ws_io_in.reserve(n * sizeof(uint32_t), stream) < 0 || m->ws_io_out.reserve(B.out_bytes, stream) < 0) return -1;
+  const BatchBlocks::Out out = B.out(static_cast<unsigned char*>(m->ws_io_out.p));
   BLURRILY_HIP_TRY(hipMemcpyAsync(m->ws_io_in.p, references, n * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-  if (blurrily_storage_find_references_device(m, static_cast<const uint32_t*>(m->ws_io_in.p), n, limit, d_rows, d_counts,
-                                              d_ntri, stream) < 0)
+  if (blurrily_storage_find_references_device(m, static_cast<const uint32_t*>(m->ws_io_in.p), n, limit, out.rows,
+                                              out.counts, out.flags, stream) < 0)
     return -1;
-  BLURRILY_HIP_TRY(hipMemcpyAsync(counts, d_counts, n * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-  if (nb_trigrams) BLURRILY_HIP_TRY(hipMemcpyAsync(nb_trigrams, d_ntri, n * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-  if (limit) BLURRILY_HIP_TRY(hipMemcpyAsync(results, d_rows, row_bytes, hipMemcpyDeviceToHost, stream));
-  BLURRILY_HIP_TRY(hipStreamSynchronize(stream));
-  return 0;
+  return B.copy_out(out.counts, out.flags, out.rows, counts, nb_trigrams, results, stream);
 }
 
 }  // extern "C"

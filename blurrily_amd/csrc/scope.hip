@@ -33,11 +33,13 @@ namespace {
 
 constexpr size_t kScopePageBytes = size_t(1) << 16;   // small direct batches: needles in, rows out, through mapped memory
 
-// The direct form from an extraction's readback: the held members (indices into sc->refs) in (weight, reference)
-// order -- the rows' order among equal matches -- with member i's ntri[i] codes at codes_of(i), copied to the device.
-template <class CodesOf>
-int scope_set_direct(blurrily_scope sc, std::vector<uint32_t>& held, const uint32_t* ntri, const uint32_t* wgt,
-                     uint64_t codes, CodesOf codes_of, hipStream_t stream) {
+// The direct form from an extraction's readback, whose members [at, at + sc->refs.size()) are the scope's: the held
+// ones (indices into sc->refs) in (weight, reference) order -- the rows' order among equal matches -- with their
+// codes, copied to the device.
+int scope_set_direct(blurrily_scope sc, std::vector<uint32_t>& held, const ExtractionOnHost& R, size_t at, uint64_t codes,
+                     hipStream_t stream) {
+  const uint32_t* ntri = R.ntri.data() + at;
+  const uint32_t* wgt = R.weight.data() + at;
   std::sort(held.begin(), held.end(), [&](uint32_t a, uint32_t b) {
     return wgt[a] != wgt[b] ? wgt[a] < wgt[b] : sc->refs[a] < sc->refs[b];
   });
@@ -52,7 +54,7 @@ int scope_set_direct(blurrily_scope sc, std::vector<uint32_t>& held, const uint3
   off[0] = 0;
   for (size_t j = 0; j < nd; ++j) {
     const uint32_t i = held[j];
-    std::memcpy(cd + off[j], codes_of(i), size_t(ntri[i]) * sizeof(uint16_t));
+    std::memcpy(cd + off[j], R.codes_of(at + i), size_t(ntri[i]) * sizeof(uint16_t));
     off[j + 1] = off[j] + ntri[i];
     ref[j] = sc->refs[i];
     weight[j] = wgt[i];
@@ -70,11 +72,29 @@ int scope_set_direct(blurrily_scope sc, std::vector<uint32_t>& held, const uint3
   return 0;
 }
 
-// The scope's device state for the map as it is now (the image brought up to date and tombstones applied first).
+// A scope's held count and -- when the direct strategy can serve the scope at all -- its direct form, from members
+// [at, at + sc->refs.size()) of an extraction whose counts are on the host; the scope is then ready for the map as it
+// is now (its masks apart).  The codes are read back here unless the caller has them already.
+int scope_from_extraction(trigram_map m, blurrily_scope sc, ExtractionOnHost& R, size_t at, hipStream_t stream) {
+  std::vector<uint32_t> held;
+  uint64_t codes = 0;
+  uint32_t widest = 0;
+  for (size_t i = 0; i < sc->refs.size(); ++i)
+    if (const uint32_t t = R.ntri[at + i]) { held.push_back(uint32_t(i)); codes += t; widest = std::max(widest, t); }
+  sc->n_held = uint32_t(held.size());
+  if (!held.empty() && held.size() <= kScopeMaxMembers && widest <= kScopeMaxMemberCodes &&
+      (R.read_codes(stream) < 0 || scope_set_direct(sc, held, R, at, codes, stream) < 0))
+    return -1;
+  sc->built_base = m->base_builds;
+  sc->built_log = log_of(m)->log_version;
+  sc->ready = true;
+  return 0;
+}
+
+// The scope's device state for the map as it is now (the image brought up to date and tombstones applied first): the
+// direct form of this one scope, if it is stale, and its masks.
 int scope_prepare(trigram_map m, blurrily_scope sc, hipStream_t stream) {
-  if (m->host->dirty_buckets()) m->host->sort_dirty_buckets();
-  if (ensure_device(m) < 0) return -1;
-  if (apply_tombstones(m, stream) < 0) return -1;
+  if (map_ready(m, stream) < 0) return -1;
   if (sc->ready && sc->mask_ready && sc->built_base == m->base_builds && sc->built_log == log_of(m)->log_version)
     return 0;
   sc->ready = false;
@@ -92,6 +112,7 @@ int scope_prepare(trigram_map m, blurrily_scope sc, hipStream_t stream) {
   ma.win0[0] = 0; ma.win0[1] = m->dev.n_windows;
   ma.mask[0] = static_cast<uint32_t*>(sc->d_mask[0].p); ma.mask[1] = static_cast<uint32_t*>(sc->d_mask[1].p);
   ma.mask_words[0] = words[0]; ma.mask_words[1] = words[1];
+  ExtractionOnHost R(n);
   if (n == 0) {
     if (launch_scope_mask(ma, stream) < 0) return -1;
   } else {
@@ -101,34 +122,11 @@ int scope_prepare(trigram_map m, blurrily_scope sc, hipStream_t stream) {
     if (refs_extract(m, static_cast<const uint32_t*>(sc->d_refs.p), n, stream, &x) < 0) return -1;
     ma.loc = x.loc; ma.n = uint32_t(n);
     if (launch_scope_mask(ma, stream) < 0) return -1;
-    std::vector<uint32_t> ntri(n), wgt(n);
-    BLURRILY_HIP_TRY(hipMemcpyAsync(ntri.data(), x.needles.ntri, n * 4, hipMemcpyDeviceToHost, stream));
-    BLURRILY_HIP_TRY(hipMemcpyAsync(wgt.data(), x.needles.weight, n * 4, hipMemcpyDeviceToHost, stream));
+    // (the counts alone first: the offsets and the codes travel only if a direct form is possible)
+    if (R.enqueue_counts(x, stream) < 0) return -1;
     BLURRILY_HIP_TRY(hipStreamSynchronize(stream));
-    std::vector<uint32_t> held;
-    uint64_t codes = 0;
-    uint32_t widest = 0;
-    for (size_t i = 0; i < n; ++i)
-      if (ntri[i]) { held.push_back(uint32_t(i)); codes += ntri[i]; widest = std::max(widest, ntri[i]); }
-    sc->n_held = uint32_t(held.size());
-    // the direct form, when the direct strategy can serve the scope at all
-    if (!held.empty() && held.size() <= kScopeMaxMembers && widest <= kScopeMaxMemberCodes) {
-      std::vector<uint64_t> qoff(n);
-      uint64_t slots = 0, total = 0;
-      BLURRILY_HIP_TRY(hipMemcpyAsync(qoff.data(), x.needles.qoff, n * 8, hipMemcpyDeviceToHost, stream));
-      BLURRILY_HIP_TRY(hipMemcpyAsync(&slots, x.win_base_total, 8, hipMemcpyDeviceToHost, stream));
-      BLURRILY_HIP_TRY(hipStreamSynchronize(stream));
-      BLURRILY_HIP_TRY(hipMemcpy(&total, x.slot_start + slots, 8, hipMemcpyDeviceToHost));
-      std::vector<uint16_t> all(total);
-      if (total) BLURRILY_HIP_TRY(hipMemcpy(all.data(), x.needles.codes + n, total * sizeof(uint16_t), hipMemcpyDeviceToHost));
-      if (scope_set_direct(sc, held, ntri.data(), wgt.data(), codes,
-                           [&](uint32_t i) { return all.data() + (qoff[i] + i - n); }, stream) < 0)
-        return -1;
-    }
   }
-  sc->built_base = m->base_builds;
-  sc->built_log = log_of(m)->log_version;
-  sc->ready = true;
+  if (scope_from_extraction(m, sc, R, 0, stream) < 0) return -1;
   sc->mask_ready = true;
   return 0;
 }
@@ -146,18 +144,16 @@ int scope_run(trigram_map m, blurrily_scope sc, const char* d_packed, size_t pac
               size_t n, uint16_t limit, trigram_match d_results, uint32_t* d_counts, bool maybe_long, bool maybe_mid,
               hipStream_t stream) {
   if (n == 0) return 0;
-  if (n > 0xFFFFFFF0ull) { errno = EINVAL; return -1; }
-  if (sc->n_held == 0 || limit == 0) {                 // nothing in the scope is held: no rows
+  if (n > kMaxBatchNeedles) { errno = EINVAL; return -1; }
+  const bool no_rows = sc->n_held == 0 || limit == 0;  // nothing in the scope is held
+  if (no_rows || scope_takes_direct(m, sc, limit)) {
     NameScope name_scope(&m->last_kernels);
     m->last_kernels.clear();
     m->last_sweep = 0;
-    BLURRILY_HIP_TRY(hipMemsetAsync(d_counts, 0, n * sizeof(uint32_t), stream));
-    return 0;
-  }
-  if (scope_takes_direct(m, sc, limit)) {
-    NameScope name_scope(&m->last_kernels);
-    m->last_kernels.clear();
-    m->last_sweep = 0;
+    if (no_rows) {
+      BLURRILY_HIP_TRY(hipMemsetAsync(d_counts, 0, n * sizeof(uint32_t), stream));
+      return 0;
+    }
     ScopeFindArgs a{};
     a.packed = d_packed; a.offsets = d_offsets; a.n = uint32_t(n);
     a.m_off = sc->m_off; a.m_codes = sc->m_codes; a.m_ref = sc->m_ref; a.m_weight = sc->m_weight;
@@ -166,8 +162,6 @@ int scope_run(trigram_map m, blurrily_scope sc, const char* d_packed, size_t pac
   }
   const ScopeMasks sm{static_cast<const uint32_t*>(sc->d_mask[0].p),
                       sc->has_delta ? static_cast<const uint32_t*>(sc->d_mask[1].p) : nullptr};
-  if (m->timing && !m->ev[0])
-    for (auto& e : m->ev) BLURRILY_HIP_TRY(hipEventCreate(&e));
   return run_find(m, d_packed, packed_bytes, d_offsets, n, limit, d_results, d_counts, nullptr, maybe_long, maybe_mid,
                   stream, nullptr, &sm);
 }
@@ -253,56 +247,30 @@ int blurrily_storage_find_batch_in(trigram_map m, blurrily_scope sc, const char*
   hipStream_t stream = nullptr;
   if (scope_prepare(m, sc, stream) < 0) return -1;     // (without a GPU this is what fails, with ENODEV)
   if (n == 0) return 0;
-  size_t max_len = 0;
-  for (size_t i = 0; i < n && max_len <= 126; ++i) {   // (what the sweeps need to know: > 63, > 126)
-    const size_t cap = size_t(offsets[i + 1] - offsets[i]);
-    if (cap <= max_len) continue;
-    const char* s = packed + offsets[i];
-    const void* nul = std::memchr(s, 0, cap);
-    max_len = std::max(max_len, nul ? size_t(static_cast<const char*>(nul) - s) : cap);
-  }
-  const size_t packed_bytes = size_t(offsets[n]);
-  const size_t off_bytes = (n + 1) * sizeof(uint64_t);
-  const size_t row_bytes = n * size_t(limit) * sizeof(trigram_match_t);
-  const size_t cnt_bytes = n * sizeof(uint32_t);
-  const size_t in_bytes = align_up(off_bytes, 256) + std::max<size_t>(packed_bytes, 16);
-  const size_t out_bytes = align_up(cnt_bytes, 256) + std::max<size_t>(row_bytes, 16);
+  const size_t max_len = longest_needle(packed, offsets, n);
+  const BatchBlocks B(n, size_t(offsets[n]), limit, false);
   // a small batch the direct strategy serves: needles read and rows written by the kernel in mapped pinned memory --
   // one launch, no copies
-  if (in_bytes <= kScopePageBytes && out_bytes <= kScopePageBytes && sc->n_held && scope_takes_direct(m, sc, limit)) {
+  if (B.in_bytes <= kScopePageBytes && B.out_bytes <= kScopePageBytes && sc->n_held && scope_takes_direct(m, sc, limit)) {
     if (scope_page(m) < 0) return -1;
-    unsigned char* h_in = m->h_scope;
-    unsigned char* h_out = m->h_scope + kScopePageBytes;
-    std::memcpy(h_in, offsets, off_bytes);
-    if (packed_bytes) std::memcpy(h_in + align_up(off_bytes, 256), packed, packed_bytes);
-    unsigned char* d_in = m->d_scope;
-    unsigned char* d_out = m->d_scope + kScopePageBytes;
-    if (scope_run(m, sc, reinterpret_cast<const char*>(d_in + align_up(off_bytes, 256)), packed_bytes,
-                  reinterpret_cast<const uint64_t*>(d_in), n, limit,
-                  reinterpret_cast<trigram_match>(d_out + align_up(cnt_bytes, 256)), reinterpret_cast<uint32_t*>(d_out),
-                  false, false, stream) < 0)
+    B.fill_in(m->h_scope, packed, offsets);
+    const BatchBlocks::In in = B.in(m->d_scope);
+    const BatchBlocks::Out out = B.out(m->d_scope + kScopePageBytes);
+    if (scope_run(m, sc, in.packed, B.packed_bytes, in.offsets, n, limit, out.rows, out.counts, false, false, stream) < 0)
       return -1;
     BLURRILY_HIP_TRY(hipStreamSynchronize(stream));
-    std::memcpy(counts, h_out, cnt_bytes);
-    if (limit) std::memcpy(results, h_out + align_up(cnt_bytes, 256), row_bytes);
+    B.take_out(B.out(m->h_scope + kScopePageBytes), counts, nullptr, results);
     return 0;
   }
-  if (m->ws_io_in.reserve(in_bytes, stream) < 0 || m->ws_io_out.reserve(out_bytes, stream) < 0) return -1;
+  if (m->ws_io_in.reserve(B.in_bytes, stream) < 0 || m->ws_io_out.reserve(B.out_bytes, stream) < 0) return -1;
   unsigned char* d_in = static_cast<unsigned char*>(m->ws_io_in.p);
-  unsigned char* d_out = static_cast<unsigned char*>(m->ws_io_out.p);
-  BLURRILY_HIP_TRY(hipMemcpyAsync(d_in, offsets, off_bytes, hipMemcpyHostToDevice, stream));
-  if (packed_bytes)
-    BLURRILY_HIP_TRY(hipMemcpyAsync(d_in + align_up(off_bytes, 256), packed, packed_bytes, hipMemcpyHostToDevice, stream));
-  uint32_t* d_counts = reinterpret_cast<uint32_t*>(d_out);
-  trigram_match d_rows = reinterpret_cast<trigram_match>(d_out + align_up(cnt_bytes, 256));
-  if (scope_run(m, sc, reinterpret_cast<const char*>(d_in + align_up(off_bytes, 256)), packed_bytes,
-                reinterpret_cast<const uint64_t*>(d_in), n, limit, d_rows, d_counts, max_len > 126, max_len > 63,
+  const BatchBlocks::In in = B.in(d_in);
+  const BatchBlocks::Out out = B.out(static_cast<unsigned char*>(m->ws_io_out.p));
+  if (B.copy_in(d_in, packed, offsets, stream) < 0) return -1;
+  if (scope_run(m, sc, in.packed, B.packed_bytes, in.offsets, n, limit, out.rows, out.counts, max_len > 126, max_len > 63,
                 stream) < 0)
     return -1;
-  BLURRILY_HIP_TRY(hipMemcpyAsync(counts, d_counts, cnt_bytes, hipMemcpyDeviceToHost, stream));
-  if (limit) BLURRILY_HIP_TRY(hipMemcpyAsync(results, d_rows, row_bytes, hipMemcpyDeviceToHost, stream));
-  BLURRILY_HIP_TRY(hipStreamSynchronize(stream));
-  return 0;
+  return B.copy_out(out.counts, nullptr, out.rows, counts, nullptr, results, stream);
 }
 
 int blurrily_storage_find_in(trigram_map m, blurrily_scope sc, const char* needle, uint16_t limit, trigram_match results) {
@@ -346,10 +314,8 @@ int scopes_prepare_direct(trigram_map m, const std::vector<blurrily_scope>& stal
     n += sc->refs.size();
     sc->ready = false; sc->mask_ready = false; sc->direct = false; sc->n_held = 0;
   }
-  if (n > 0xFFFFFFF0ull) { errno = EINVAL; return -1; }
-  std::vector<uint32_t> ntri(n), wgt(n);
-  std::vector<uint64_t> qoff(n);
-  std::vector<uint16_t> all;
+  if (n > kMaxBatchNeedles) { errno = EINVAL; return -1; }
+  ExtractionOnHost R(n);
   if (n) {
     std::vector<uint32_t> refs;
     refs.reserve(n);
@@ -358,33 +324,12 @@ int scopes_prepare_direct(trigram_map m, const std::vector<blurrily_scope>& stal
     BLURRILY_HIP_TRY(hipMemcpyAsync(m->ws_each.p, refs.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
     RefExtract x;
     if (refs_extract(m, static_cast<const uint32_t*>(m->ws_each.p), n, stream, &x) < 0) return -1;
-    uint64_t slots = 0, total = 0;
-    BLURRILY_HIP_TRY(hipMemcpyAsync(ntri.data(), x.needles.ntri, n * 4, hipMemcpyDeviceToHost, stream));
-    BLURRILY_HIP_TRY(hipMemcpyAsync(wgt.data(), x.needles.weight, n * 4, hipMemcpyDeviceToHost, stream));
-    BLURRILY_HIP_TRY(hipMemcpyAsync(qoff.data(), x.needles.qoff, n * 8, hipMemcpyDeviceToHost, stream));
-    BLURRILY_HIP_TRY(hipMemcpyAsync(&slots, x.win_base_total, 8, hipMemcpyDeviceToHost, stream));
-    BLURRILY_HIP_TRY(hipStreamSynchronize(stream));
-    BLURRILY_HIP_TRY(hipMemcpy(&total, x.slot_start + slots, 8, hipMemcpyDeviceToHost));
-    all.resize(total);
-    if (total) BLURRILY_HIP_TRY(hipMemcpy(all.data(), x.needles.codes + n, total * sizeof(uint16_t), hipMemcpyDeviceToHost));
+    if (R.enqueue_counts(x, stream) < 0 || R.read_codes(stream) < 0) return -1;   // (one readback, whatever the scopes hold)
   }
   size_t at = 0;
   for (blurrily_scope sc : stale) {
-    const size_t k = sc->refs.size();
-    std::vector<uint32_t> held;
-    uint64_t codes = 0;
-    uint32_t widest = 0;
-    for (size_t i = 0; i < k; ++i)
-      if (ntri[at + i]) { held.push_back(uint32_t(i)); codes += ntri[at + i]; widest = std::max(widest, ntri[at + i]); }
-    sc->n_held = uint32_t(held.size());
-    if (!held.empty() && held.size() <= kScopeMaxMembers && widest <= kScopeMaxMemberCodes &&
-        scope_set_direct(sc, held, ntri.data() + at, wgt.data() + at, codes,
-                         [&](uint32_t i) { return all.data() + (qoff[at + i] + at + i - n); }, stream) < 0)
-      return -1;
-    sc->built_base = m->base_builds;
-    sc->built_log = log_of(m)->log_version;
-    sc->ready = true;
-    at += k;
+    if (scope_from_extraction(m, sc, R, at, stream) < 0) return -1;
+    at += sc->refs.size();
   }
   return 0;
 }
@@ -540,8 +485,6 @@ int each_run(trigram_map m, const EachPlan& P, const EachNeedles& N, size_t n, u
     char* d_gpk = reinterpret_cast<char*>(d + o_gpk);
     if (!N.rn && launch_scope_gather_strings(N.d_packed, N.d_offsets, d_idx, d_goff, uint32_t(ng), d_gpk, stream) < 0)
       return -1;
-    if (m->timing && !m->ev[0])
-      for (auto& e : m->ev) BLURRILY_HIP_TRY(hipEventCreate(&e));
     for (size_t g = 0; g + 1 < P.group_start.size(); ++g) {
       const size_t k0 = P.group_start[g], cnt = P.group_start[g + 1] - k0;
       const blurrily_scope sc = P.group_scope[g];
@@ -583,7 +526,7 @@ int blurrily_storage_find_batch_each_in_device(trigram_map m, const blurrily_sco
   (void)packed_bytes;
   if (each_check(m, scopes, n_scopes) < 0) return -1;
   if (n && (!d_which || !d_offsets || !d_counts || (limit && !d_results))) { errno = EINVAL; return -1; }
-  if (n > 0xFFFFFFF0ull) { errno = EINVAL; return -1; }
+  if (n > kMaxBatchNeedles) { errno = EINVAL; return -1; }
   DeviceScope scope(m->dev.device);
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (map_ready(m, st) < 0) return -1;
@@ -604,7 +547,7 @@ int blurrily_storage_find_batch_each_in(trigram_map m, const blurrily_scope* sco
                                         uint16_t limit, trigram_match results, uint32_t* counts) {
   if (each_check(m, scopes, n_scopes) < 0) return -1;
   if (n && (!which || !packed || !offsets || !counts || (limit && !results))) { errno = EINVAL; return -1; }
-  if (n > 0xFFFFFFF0ull) { errno = EINVAL; return -1; }
+  if (n > kMaxBatchNeedles) { errno = EINVAL; return -1; }
   if (each_check_which(which, n, n_scopes) < 0) return -1;
   DeviceScope scope(m->dev.device);
   hipStream_t stream = nullptr;
@@ -612,65 +555,43 @@ int blurrily_storage_find_batch_each_in(trigram_map m, const blurrily_scope* sco
   if (n == 0) return 0;
   EachPlan P;
   if (each_plan(m, scopes, n_scopes, which, n, limit, stream, &P) < 0) return -1;
-  size_t max_len = 0;
-  for (size_t i = 0; i < n && max_len <= 126; ++i) {   // (what the sweeps need to know: > 63, > 126)
-    const size_t cap = size_t(offsets[i + 1] - offsets[i]);
-    if (cap <= max_len) continue;
-    const char* s = packed + offsets[i];
-    const void* nul = std::memchr(s, 0, cap);
-    max_len = std::max(max_len, nul ? size_t(static_cast<const char*>(nul) - s) : cap);
-  }
-  const size_t packed_bytes = size_t(offsets[n]);
-  const size_t off_bytes = (n + 1) * sizeof(uint64_t);
-  const size_t row_bytes = n * size_t(limit) * sizeof(trigram_match_t);
-  const size_t cnt_bytes = n * sizeof(uint32_t);
-  const size_t o_packed = align_up(off_bytes, 256), o_tab = o_packed + align_up(std::max<size_t>(packed_bytes, 16), 256);
-  const size_t o_ord = o_tab + align_up(P.table.size() * sizeof(ScopeDirect) + 8, 256);
+  const size_t max_len = longest_needle(packed, offsets, n);
+  const BatchBlocks B(n, size_t(offsets[n]), limit, false);
+  // (the page carries the scope table and the order behind the needles)
+  const size_t o_tab = align_up(B.in_bytes, 256), o_ord = o_tab + align_up(P.table.size() * sizeof(ScopeDirect) + 8, 256);
   const size_t page_in = o_ord + P.order.size() * sizeof(uint2);
-  const size_t out_bytes = align_up(cnt_bytes, 256) + std::max<size_t>(row_bytes, 16);
   // a small batch served directly alone: needles, scope table and order read, rows written, in mapped pinned memory --
   // one launch, no copies
-  if (P.idx.empty() && !P.order.empty() && page_in <= kScopePageBytes && out_bytes <= kScopePageBytes) {
+  if (P.idx.empty() && !P.order.empty() && page_in <= kScopePageBytes && B.out_bytes <= kScopePageBytes) {
     if (scope_page(m) < 0) return -1;
     unsigned char* h_in = m->h_scope;
-    unsigned char* h_out = m->h_scope + kScopePageBytes;
-    std::memcpy(h_in, offsets, off_bytes);
-    if (packed_bytes) std::memcpy(h_in + o_packed, packed, packed_bytes);
+    const BatchBlocks::Out h_out = B.out(m->h_scope + kScopePageBytes);
+    B.fill_in(h_in, packed, offsets);
     std::memcpy(h_in + o_tab, P.table.data(), P.table.size() * sizeof(ScopeDirect));
     std::memcpy(h_in + o_ord, P.order.data(), P.order.size() * sizeof(uint2));
     unsigned char* d_in = m->d_scope;
-    unsigned char* d_out = m->d_scope + kScopePageBytes;
-    uint32_t* d_counts = reinterpret_cast<uint32_t*>(d_out);
-    if (P.any_empty) std::memset(h_out, 0, cnt_bytes);
+    const BatchBlocks::Out out = B.out(m->d_scope + kScopePageBytes);
+    if (P.any_empty) std::memset(h_out.counts, 0, B.cnt_bytes);
     EachNeedles N;
-    N.d_packed = reinterpret_cast<const char*>(d_in + o_packed); N.d_offsets = reinterpret_cast<const uint64_t*>(d_in);
+    N.d_packed = B.in(d_in).packed; N.d_offsets = B.in(d_in).offsets;
     NameScope name_scope(&m->last_kernels);
     m->last_kernels.clear();
     if (each_launch_direct(P, N, reinterpret_cast<const ScopeDirect*>(d_in + o_tab),
-                           reinterpret_cast<const uint2*>(d_in + o_ord), limit,
-                           reinterpret_cast<trigram_match>(d_out + align_up(cnt_bytes, 256)), d_counts, stream) < 0)
+                           reinterpret_cast<const uint2*>(d_in + o_ord), limit, out.rows, out.counts, stream) < 0)
       return -1;
     BLURRILY_HIP_TRY(hipStreamSynchronize(stream));
-    std::memcpy(counts, h_out, cnt_bytes);
-    if (limit) std::memcpy(results, h_out + align_up(cnt_bytes, 256), row_bytes);
+    B.take_out(h_out, counts, nullptr, results);
     return 0;
   }
-  const size_t in_bytes = o_packed + std::max<size_t>(packed_bytes, 16);
-  if (m->ws_io_in.reserve(in_bytes, stream) < 0 || m->ws_io_out.reserve(out_bytes, stream) < 0) return -1;
+  if (m->ws_io_in.reserve(B.in_bytes, stream) < 0 || m->ws_io_out.reserve(B.out_bytes, stream) < 0) return -1;
   unsigned char* d_in = static_cast<unsigned char*>(m->ws_io_in.p);
-  unsigned char* d_out = static_cast<unsigned char*>(m->ws_io_out.p);
-  BLURRILY_HIP_TRY(hipMemcpyAsync(d_in, offsets, off_bytes, hipMemcpyHostToDevice, stream));
-  if (packed_bytes) BLURRILY_HIP_TRY(hipMemcpyAsync(d_in + o_packed, packed, packed_bytes, hipMemcpyHostToDevice, stream));
-  uint32_t* d_counts = reinterpret_cast<uint32_t*>(d_out);
-  trigram_match d_rows = reinterpret_cast<trigram_match>(d_out + align_up(cnt_bytes, 256));
+  const BatchBlocks::Out out = B.out(static_cast<unsigned char*>(m->ws_io_out.p));
+  if (B.copy_in(d_in, packed, offsets, stream) < 0) return -1;
   EachNeedles N;
-  N.d_packed = reinterpret_cast<const char*>(d_in + o_packed); N.d_offsets = reinterpret_cast<const uint64_t*>(d_in);
+  N.d_packed = B.in(d_in).packed; N.d_offsets = B.in(d_in).offsets;
   N.h_offsets = offsets;
-  if (each_run(m, P, N, n, limit, d_rows, d_counts, max_len > 126, max_len > 63, stream) < 0) return -1;
-  BLURRILY_HIP_TRY(hipMemcpyAsync(counts, d_counts, cnt_bytes, hipMemcpyDeviceToHost, stream));
-  if (limit) BLURRILY_HIP_TRY(hipMemcpyAsync(results, d_rows, row_bytes, hipMemcpyDeviceToHost, stream));
-  BLURRILY_HIP_TRY(hipStreamSynchronize(stream));
-  return 0;
+  if (each_run(m, P, N, n, limit, out.rows, out.counts, max_len > 126, max_len > 63, stream) < 0) return -1;
+  return B.copy_out(out.counts, nullptr, out.rows, counts, nullptr, results, stream);
 }
 
 int blurrily_storage_find_references_each_in(trigram_map m, const blurrily_scope* scopes, size_t n_scopes,
@@ -679,7 +600,7 @@ int blurrily_storage_find_references_each_in(trigram_map m, const blurrily_scope
                                              uint32_t* nb_trigrams) {
   if (each_check(m, scopes, n_scopes) < 0) return -1;
   if (n && (!which || !references || !counts || (limit && !results))) { errno = EINVAL; return -1; }
-  if (n > 0xFFFFFFF0ull) { errno = EINVAL; return -1; }
+  if (n > kMaxBatchNeedles) { errno = EINVAL; return -1; }
   if (each_check_which(which, n, n_scopes) < 0) return -1;
   DeviceScope scope(m->dev.device);
   hipStream_t stream = nullptr;
@@ -687,24 +608,16 @@ int blurrily_storage_find_references_each_in(trigram_map m, const blurrily_scope
   if (n == 0) return 0;
   EachPlan P;
   if (each_plan(m, scopes, n_scopes, which, n, limit, stream, &P) < 0) return -1;
-  const size_t row_bytes = n * size_t(limit) * sizeof(trigram_match_t), cnt_bytes = align_up(n * sizeof(uint32_t), 256);
-  if (m->ws_io_in.reserve(n * sizeof(uint32_t), stream) < 0 ||
-      m->ws_io_out.reserve(cnt_bytes + std::max<size_t>(row_bytes, 16), stream) < 0)
-    return -1;
-  unsigned char* d_out = static_cast<unsigned char*>(m->ws_io_out.p);
-  uint32_t* d_counts = reinterpret_cast<uint32_t*>(d_out);
-  trigram_match d_rows = reinterpret_cast<trigram_match>(d_out + cnt_bytes);
+  const BatchBlocks B(n, 0, limit, false);               // (the references go in alone; out: [counts | rows])
+  if (m->ws_io_in.reserve(n * sizeof(uint32_t), stream) < 0 || m->ws_io_out.reserve(B.out_bytes, stream) < 0) return -1;
+  const BatchBlocks::Out out = B.out(static_cast<unsigned char*>(m->ws_io_out.p));
   BLURRILY_HIP_TRY(hipMemcpyAsync(m->ws_io_in.p, references, n * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
   RefExtract x;                                          // (after every scope's preparation: both use ws_refs)
   if (refs_extract(m, static_cast<const uint32_t*>(m->ws_io_in.p), n, stream, &x) < 0) return -1;
   EachNeedles N;
   N.rn = &x.needles;
-  if (each_run(m, P, N, n, limit, d_rows, d_counts, true, true, stream) < 0) return -1;
-  BLURRILY_HIP_TRY(hipMemcpyAsync(counts, d_counts, n * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-  if (nb_trigrams) BLURRILY_HIP_TRY(hipMemcpyAsync(nb_trigrams, x.needles.ntri, n * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-  if (limit) BLURRILY_HIP_TRY(hipMemcpyAsync(results, d_rows, row_bytes, hipMemcpyDeviceToHost, stream));
-  BLURRILY_HIP_TRY(hipStreamSynchronize(stream));
-  return 0;
+  if (each_run(m, P, N, n, limit, out.rows, out.counts, true, true, stream) < 0) return -1;
+  return B.copy_out(out.counts, x.needles.ntri, out.rows, counts, nb_trigrams, results, stream);   // (the counts of trigrams: the extraction's own)
 }
 
 }  // extern "C"

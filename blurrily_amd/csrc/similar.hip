@@ -294,7 +294,7 @@ int blurrily_storage_find_batch_similar(trigram_map m, const char* packed, const
                                         uint16_t limit, uint32_t min_permille, trigram_match results, uint32_t* counts,
                                         uint32_t* row_ntri) {
   if (!m || !counts || min_permille > 1000 || (n && limit && !results) || (n && (!packed || !offsets)) ||
-      n > 0xFFFFFFF0ull) {
+      n > kMaxBatchNeedles) {
     errno = EINVAL;
     return -1;
   }
@@ -324,7 +324,7 @@ int blurrily_storage_find_similar(trigram_map m, const char* needle, uint16_t li
 int blurrily_storage_find_references_similar(trigram_map m, const uint32_t* references, size_t n, uint16_t limit,
                                              uint32_t min_permille, trigram_match results, uint32_t* counts,
                                              uint32_t* row_ntri, uint32_t* nb_trigrams) {
-  if (!m || !counts || min_permille > 1000 || (n && limit && !results) || (n && !references) || n > 0xFFFFFFF0ull) {
+  if (!m || !counts || min_permille > 1000 || (n && limit && !results) || (n && !references) || n > kMaxBatchNeedles) {
     errno = EINVAL;
     return -1;
   }
