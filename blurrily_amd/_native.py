@@ -36,6 +36,82 @@ class DeviceInfo(C.Structure):
     ]
 
 
+_vp, _vpp = C.c_void_p, C.POINTER(C.c_void_p)
+# every entry point of include/blurrily_storage.h: name -> (restype, argtypes)
+_ENTRIES = {
+    "blurrily_storage_new": (C.c_int, [_vpp]),
+    "blurrily_storage_load": (C.c_int, [_vpp, C.c_char_p]),
+    "blurrily_storage_close": (C.c_int, [_vpp]),
+    "blurrily_storage_mark": (None, [_vp]),
+    "blurrily_storage_save": (C.c_int, [_vp, C.c_char_p]),
+    "blurrily_storage_put": (C.c_int, [_vp, C.c_char_p, C.c_uint32, C.c_uint32]),
+    "blurrily_storage_delete": (C.c_int, [_vp, C.c_uint32]),
+    "blurrily_storage_find": (C.c_int, [_vp, C.c_char_p, C.c_uint16, C.c_void_p]),
+    "blurrily_storage_stats": (C.c_int, [_vp, C.POINTER(TrigramStat)]),
+    "blurrily_storage_put_many": (C.c_long, [_vp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
+    "blurrily_storage_find_batch": (C.c_int, [_vp, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint16,
+                                              C.c_void_p, C.c_void_p]),
+    "blurrily_storage_find_batch_device": (C.c_int, [_vp, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                                     C.c_uint16, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                     C.c_void_p]),
+    "blurrily_storage_find_batch_raw": (C.c_int, [_vp, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint16,
+                                                  C.c_void_p, C.c_void_p, C.c_void_p]),
+    "blurrily_normalize_batch_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p]),
+    "blurrily_storage_sync_device": (C.c_int, [_vp]),
+    "blurrily_tokeniser_parse_string": (C.c_int, [C.c_char_p, C.c_void_p]),
+    "blurrily_storage_device_info": (C.c_int, [_vp, C.POINTER(DeviceInfo)]),
+    "blurrily_storage_set_timing": (None, [_vp, C.c_int]),
+    "blurrily_storage_set_stats": (None, [_vp, C.c_int]),
+    "blurrily_storage_find_stats": (C.c_int, [_vp, C.c_void_p]),
+    "blurrily_storage_set_option": (C.c_int, [_vp, C.c_char_p, C.c_longlong]),
+    "blurrily_storage_get_option": (C.c_int, [_vp, C.c_char_p, C.POINTER(C.c_longlong)]),
+    "blurrily_storage_find_path_flags": (C.c_int, [_vp, C.c_void_p, C.c_size_t]),
+    "blurrily_storage_device_info_sized": (C.c_size_t, [_vp, C.c_void_p, C.c_size_t]),
+    "blurrily_storage_tune": (C.c_int, [_vp, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_uint16]),
+    "blurrily_storage_last_kernels": (C.c_size_t, [_vp, C.c_char_p, C.c_size_t]),
+    # by reference (reference storage.h:72-87's commented-out get, and find by a stored reference)
+    "blurrily_storage_get": (C.c_int, [_vp, C.c_uint32, C.c_void_p, C.c_int, C.c_void_p]),
+    "blurrily_storage_get_batch": (C.c_int, [_vp, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_size_t]),
+    "blurrily_storage_find_references": (C.c_int, [_vp, C.c_void_p, C.c_size_t, C.c_uint16, C.c_void_p, C.c_void_p,
+                                                   C.c_void_p]),
+    "blurrily_storage_find_references_device": (C.c_int, [_vp, C.c_void_p, C.c_size_t, C.c_uint16, C.c_void_p,
+                                                          C.c_void_p, C.c_void_p, C.c_void_p]),
+    # scoped find: a fixed set of references, and finds among them only
+    "blurrily_scope_new": (C.c_int, [_vp, C.c_void_p, C.c_size_t, _vpp]),
+    "blurrily_scope_close": (C.c_int, [_vpp]),
+    "blurrily_scope_members": (C.c_int, [_vp, C.POINTER(C.c_uint32)]),
+    "blurrily_storage_find_in": (C.c_int, [_vp, _vp, C.c_char_p, C.c_uint16, C.c_void_p]),
+    "blurrily_storage_find_batch_in": (C.c_int, [_vp, _vp, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint16,
+                                                 C.c_void_p, C.c_void_p]),
+    "blurrily_storage_find_batch_in_device": (C.c_int, [_vp, _vp, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                                        C.c_uint16, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # a scope per needle: batched scoped find and find-by-reference, each needle among its own scope
+    "blurrily_storage_find_batch_each_in": (C.c_int, [_vp, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                                      C.c_void_p, C.c_size_t, C.c_uint16, C.c_void_p, C.c_void_p]),
+    "blurrily_storage_find_batch_each_in_device": (C.c_int, [_vp, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                                             C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint16,
+                                                             C.c_void_p, C.c_void_p, C.c_void_p]),
+    "blurrily_storage_find_references_each_in": (C.c_int, [_vp, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                                           C.c_size_t, C.c_uint16, C.c_void_p, C.c_void_p,
+                                                           C.c_void_p]),
+    # threshold find: every row at or above a bar of matches
+    "blurrily_storage_find_batch_above": (C.c_int, [_vp, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32,
+                                                    C.c_void_p, C.c_uint64, C.c_void_p]),
+    "blurrily_storage_find_above": (C.c_int, [_vp, C.c_char_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64,
+                                              C.POINTER(C.c_uint64)]),
+    "blurrily_storage_find_references_above": (C.c_int, [_vp, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32,
+                                                         C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+    # similarity find: the best rows by trigram Jaccard similarity
+    "blurrily_storage_find_batch_similar": (C.c_int, [_vp, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint16,
+                                                      C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "blurrily_storage_find_similar": (C.c_int, [_vp, C.c_char_p, C.c_uint16, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "blurrily_storage_find_references_similar": (C.c_int, [_vp, C.c_void_p, C.c_size_t, C.c_uint16, C.c_uint32,
+                                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+EXPORTED_SYMBOLS = tuple(_ENTRIES)
+
 _lib = None
 
 
@@ -80,75 +156,7 @@ def lib():
             "(hipcc --offload-arch=gfx950).  blurrily_amd has no CPU fallback.")
     _one_hip_runtime()
     L = C.CDLL(LIB_PATH, use_errno=True)
-    vp, vpp = C.c_void_p, C.POINTER(C.c_void_p)
-    sig = {
-        "blurrily_storage_new": (C.c_int, [vpp]),
-        "blurrily_storage_load": (C.c_int, [vpp, C.c_char_p]),
-        "blurrily_storage_close": (C.c_int, [vpp]),
-        "blurrily_storage_mark": (None, [vp]),
-        "blurrily_storage_save": (C.c_int, [vp, C.c_char_p]),
-        "blurrily_storage_put": (C.c_int, [vp, C.c_char_p, C.c_uint32, C.c_uint32]),
-        "blurrily_storage_delete": (C.c_int, [vp, C.c_uint32]),
-        "blurrily_storage_find": (C.c_int, [vp, C.c_char_p, C.c_uint16, C.c_void_p]),
-        "blurrily_storage_stats": (C.c_int, [vp, C.POINTER(TrigramStat)]),
-        "blurrily_storage_put_many": (C.c_long, [vp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
-        "blurrily_storage_find_batch": (C.c_int, [vp, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint16,
-                                                  C.c_void_p, C.c_void_p]),
-        "blurrily_storage_find_batch_device": (C.c_int, [vp, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
-                                                         C.c_uint16, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                         C.c_void_p]),
-        "blurrily_storage_find_batch_raw": (C.c_int, [vp, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint16,
-                                                      C.c_void_p, C.c_void_p, C.c_void_p]),
-        "blurrily_normalize_batch_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
-                                                      C.c_void_p]),
-        "blurrily_storage_sync_device": (C.c_int, [vp]),
-        "blurrily_tokeniser_parse_string": (C.c_int, [C.c_char_p, C.c_void_p]),
-        "blurrily_storage_device_info": (C.c_int, [vp, C.POINTER(DeviceInfo)]),
-        "blurrily_storage_set_timing": (None, [vp, C.c_int]),
-        "blurrily_storage_set_stats": (None, [vp, C.c_int]),
-        "blurrily_storage_find_stats": (C.c_int, [vp, C.c_void_p]),
-        "blurrily_storage_find_path_flags": (C.c_int, [vp, C.c_void_p, C.c_size_t]),
-        "blurrily_storage_set_option": (C.c_int, [vp, C.c_char_p, C.c_longlong]),
-        "blurrily_storage_get_option": (C.c_int, [vp, C.c_char_p, C.POINTER(C.c_longlong)]),
-        "blurrily_storage_device_info_sized": (C.c_size_t, [vp, C.c_void_p, C.c_size_t]),
-        "blurrily_storage_tune": (C.c_int, [vp, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_uint16]),
-        "blurrily_storage_last_kernels": (C.c_size_t, [vp, C.c_char_p, C.c_size_t]),
-        "blurrily_storage_get": (C.c_int, [vp, C.c_uint32, C.c_void_p, C.c_int, C.c_void_p]),
-        "blurrily_storage_get_batch": (C.c_int, [vp, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                 C.c_size_t]),
-        "blurrily_storage_find_references": (C.c_int, [vp, C.c_void_p, C.c_size_t, C.c_uint16, C.c_void_p, C.c_void_p,
-                                                       C.c_void_p]),
-        "blurrily_storage_find_references_device": (C.c_int, [vp, C.c_void_p, C.c_size_t, C.c_uint16, C.c_void_p,
-                                                              C.c_void_p, C.c_void_p, C.c_void_p]),
-        "blurrily_scope_new": (C.c_int, [vp, C.c_void_p, C.c_size_t, vpp]),
-        "blurrily_scope_close": (C.c_int, [vpp]),
-        "blurrily_scope_members": (C.c_int, [vp, C.POINTER(C.c_uint32)]),
-        "blurrily_storage_find_in": (C.c_int, [vp, vp, C.c_char_p, C.c_uint16, C.c_void_p]),
-        "blurrily_storage_find_batch_in": (C.c_int, [vp, vp, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint16,
-                                                     C.c_void_p, C.c_void_p]),
-        "blurrily_storage_find_batch_in_device": (C.c_int, [vp, vp, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
-                                                            C.c_uint16, C.c_void_p, C.c_void_p, C.c_void_p]),
-        "blurrily_storage_find_batch_each_in": (C.c_int, [vp, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
-                                                          C.c_void_p, C.c_size_t, C.c_uint16, C.c_void_p, C.c_void_p]),
-        "blurrily_storage_find_batch_each_in_device": (C.c_int, [vp, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
-                                                                 C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint16,
-                                                                 C.c_void_p, C.c_void_p, C.c_void_p]),
-        "blurrily_storage_find_references_each_in": (C.c_int, [vp, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
-                                                               C.c_size_t, C.c_uint16, C.c_void_p, C.c_void_p,
-                                                               C.c_void_p]),
-        "blurrily_storage_find_batch_above": (C.c_int, [vp, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32,
-                                                        C.c_void_p, C.c_uint64, C.c_void_p]),
-        "blurrily_storage_find_above": (C.c_int, [vp, C.c_char_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64,
-                                                  C.POINTER(C.c_uint64)]),
-        "blurrily_storage_find_references_above": (C.c_int, [vp, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32,
-                                                             C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
-        "blurrily_storage_find_batch_similar": (C.c_int, [vp, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint16,
-                                                          C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
-        "blurrily_storage_find_similar": (C.c_int, [vp, C.c_char_p, C.c_uint16, C.c_uint32, C.c_void_p, C.c_void_p]),
-        "blurrily_storage_find_references_similar": (C.c_int, [vp, C.c_void_p, C.c_size_t, C.c_uint16, C.c_uint32,
-                                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    }
-    for name, (res, args) in sig.items():
+    for name, (res, args) in _ENTRIES.items():
         try:
             fn = getattr(L, name)
         except AttributeError:
@@ -161,33 +169,4 @@ def lib():
     return L
 
 
-EXPORTED_SYMBOLS = (
-    "blurrily_storage_new", "blurrily_storage_load", "blurrily_storage_close", "blurrily_storage_mark",
-    "blurrily_storage_save", "blurrily_storage_put", "blurrily_storage_delete", "blurrily_storage_find",
-    "blurrily_storage_stats", "blurrily_storage_put_many", "blurrily_storage_find_batch",
-    "blurrily_storage_find_batch_device", "blurrily_storage_find_batch_raw", "blurrily_normalize_batch_device",
-    "blurrily_storage_sync_device", "blurrily_tokeniser_parse_string",
-    "blurrily_storage_device_info", "blurrily_storage_set_timing",
-    "blurrily_storage_set_stats", "blurrily_storage_find_stats",
-    "blurrily_storage_set_option", "blurrily_storage_get_option", "blurrily_storage_find_path_flags",
-    "blurrily_storage_device_info_sized", "blurrily_storage_tune", "blurrily_storage_last_kernels",
-) + (
-    # by reference (reference storage.h:72-87's commented-out get, and find by a stored reference)
-    "blurrily_storage_get", "blurrily_storage_get_batch", "blurrily_storage_find_references",
-    "blurrily_storage_find_references_device",
-) + (
-    # scoped find: a fixed set of references, and finds among them only
-    "blurrily_scope_new", "blurrily_scope_close", "blurrily_scope_members", "blurrily_storage_find_in",
-    "blurrily_storage_find_batch_in", "blurrily_storage_find_batch_in_device",
-) + (
-    # a scope per needle: batched scoped find and find-by-reference, each needle among its own scope
-    "blurrily_storage_find_batch_each_in", "blurrily_storage_find_batch_each_in_device",
-    "blurrily_storage_find_references_each_in",
-) + (
-    # threshold find: every row at or above a bar of matches
-    "blurrily_storage_find_batch_above", "blurrily_storage_find_above", "blurrily_storage_find_references_above",
-) + (
-    # similarity find: the best rows by trigram Jaccard similarity
-    "blurrily_storage_find_batch_similar", "blurrily_storage_find_similar", "blurrily_storage_find_references_similar",
-)
 NO_SCOPE = 0xFFFFFFFF                                  # BLURRILY_NO_SCOPE: a needle of such a batch with no scope

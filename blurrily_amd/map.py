@@ -6,12 +6,17 @@
 normalisation, default weight/limit, clean-path save elision).  Same names, same argument
 meaning, same error behaviour -- so tests read like spec/blurrily/map_spec.rb.
 
+Every method reads: check open, convert the arguments, call the C function by name, shape the result.  What the
+conversions and the shaping share is in the helpers below, once each.
+
 The image has no Ruby; INTEGRATION.md shows the Ruby side of the same boundary.
 """
 import ctypes as C
 import os
 import re
 import unicodedata
+from contextlib import contextmanager as _contextmanager
+from errno import ERANGE as _ERANGE
 
 import numpy as np
 
@@ -31,12 +36,43 @@ def _raise_errno(path=None):
     raise OSError(err, os.strerror(err), path)
 
 
+def _check(res, path=None):
+    """The result of a C call that can fail: negative -> OSError from errno (with the path where one is given)."""
+    if res < 0:
+        _raise_errno(path)
+    return res
+
+
 def _u32(value, what):
     """NUM2UINT (map_ext.c:85-86): reject what does not fit an unsigned 32-bit integer."""
     v = int(value)
     if not 0 <= v <= _U32_MAX:
         raise OverflowError(f"{what} {value!r} out of range of unsigned int")
     return v
+
+
+def _permille(value):
+    mp = _u32(value, "min_permille")
+    if mp > 1000:
+        raise ValueError(f"min_permille {value!r} above 1000")
+    return mp
+
+
+def _find_limit(limit):
+    """The single finds' limit (map_ext.c:131-146), as the C function takes it."""
+    limit = int(limit)
+    if not -(1 << 31) <= limit <= _U32_MAX:
+        raise OverflowError("limit out of range")
+    if limit > 0x7FFFFFFF:
+        limit -= 1 << 32                      # NUM2UINT into an `int` (map_ext.c:135)
+    if limit <= 0:
+        limit = LIMIT_DEFAULT                 # map_ext.c:142-146
+    return limit & 0xFFFF                     # uint16_t parameter (storage.h:110)
+
+
+def _batch_limit(limit):
+    """The batched methods' limit: the uint16_t parameter, nothing else."""
+    return int(limit) & 0xFFFF
 
 
 def _pack(needles):
@@ -47,6 +83,51 @@ def _pack(needles):
     return b"".join(needles), offsets
 
 
+def _needles(packed, offsets):
+    """Packed needles as the C side takes them: (pointer to the bytes, contiguous uint64 offsets[n + 1], n).  Needles
+    that are all empty have no bytes to point to and get a dummy byte (NULL with n > 0 is an argument error to some
+    entries); NULL only for n == 0.  `packed` and an `offsets` that is already right are not copied: the caller's
+    stay alive through the call."""
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    n = len(offsets) - 1
+    buf = packed if isinstance(packed, np.ndarray) else np.frombuffer(packed, dtype=np.uint8)
+    return buf.ctypes.data if buf.size else (C.addressof(_NO_BYTES) if n > 0 else None), offsets, n
+
+
+def _blocks(n, limit, row_ntri=False, per_needle=0):
+    """What a batched find fills: rows[n, max(limit, 1), 3], counts[n], with `row_ntri` a word per row
+    [n, max(limit, 1)], and `per_needle` more blocks of [n]; all uint32.  Returns (what to hand back -- rows and
+    row_ntri cut to [:, :limit] --, the pointers for the C call in the same order)."""
+    room = max(limit, 1)
+    full = [np.zeros((n, room, 3), dtype=np.uint32), np.zeros(n, dtype=np.uint32)]
+    if row_ntri:
+        full.append(np.zeros((n, room), dtype=np.uint32))
+    full += [np.zeros(n, dtype=np.uint32) for _ in range(per_needle)]
+    return tuple(a[:, :limit] if a.ndim > 1 else a for a in full), [a.ctypes.data for a in full]
+
+
+def _call_growing(call, cap, needed, row=(), dtype=np.uint32):
+    """``call(pointer, cap)`` into a buffer of `cap` rows (np.empty: only the pages written are committed); when the
+    library answers ERANGE it has reported the room it needs (``needed()``), and the call is made once more with
+    that.  Returns the buffer filled."""
+    while True:
+        buf = np.empty((cap,) + row, dtype=dtype)
+        if call(buf.ctypes.data, cap) == 0:
+            return buf
+        if C.get_errno() != _ERANGE or needed() <= cap:
+            _raise_errno()
+        cap = needed()
+
+
+def _lists(rows, counts, row_ntri=None):
+    """rows[n, limit, 3] and counts[n] -> n lists of ``[ref, matches, weight]``; with row_ntri[n, limit], of
+    ``[ref, matches, weight, R]``."""
+    if row_ntri is None:
+        return [rows[i, :c].tolist() for i, c in enumerate(counts.tolist())]
+    return [[r + [t] for r, t in zip(rows[i, :c].tolist(), row_ntri[i, :c].tolist())]
+            for i, c in enumerate(counts.tolist())]
+
+
 class RawMap:
     """Thin object wrapper over a ``trigram_map`` handle (map_ext.c)."""
 
@@ -55,10 +136,8 @@ class RawMap:
     def __init__(self, _handle=None):
         self._lib = _native.lib()
         if _handle is None:
-            h = C.c_void_p()
-            if self._lib.blurrily_storage_new(C.byref(h)) < 0:      # map_ext.c:49-50
-                _raise_errno()
-            _handle = h
+            _handle = C.c_void_p()
+            _check(self._lib.blurrily_storage_new(C.byref(_handle)))          # map_ext.c:49-50
         self._h = _handle
         self._closed = False
 
@@ -66,10 +145,8 @@ class RawMap:
     @classmethod
     def load(cls, path):
         """map_ext.c:59-71 -- Errno::* on failure (ENOENT, EPROTO ...)."""
-        lib = _native.lib()
         h = C.c_void_p()
-        if lib.blurrily_storage_load(C.byref(h), os.fsencode(path)) < 0:
-            _raise_errno(path)
+        _check(_native.lib().blurrily_storage_load(C.byref(h), os.fsencode(path)), path)
         obj = cls.__new__(cls)
         RawMap.__init__(obj, _handle=h)
         return obj
@@ -105,25 +182,15 @@ class RawMap:
     def save(self, path):
         """map_ext.c:115-127."""
         self._check_open()
-        if self._lib.blurrily_storage_save(self._h, os.fsencode(path)) < 0:
-            _raise_errno(path)
+        _check(self._lib.blurrily_storage_save(self._h, os.fsencode(path)), path)
         return None
 
     def find(self, needle, limit):
         """map_ext.c:131-162: limit <= 0 -> LIMIT_DEFAULT; rows ``[ref, matches, weight]``."""
         self._check_open()
-        limit = int(limit)
-        if not -(1 << 31) <= limit <= _U32_MAX:
-            raise OverflowError("limit out of range")
-        if limit > 0x7FFFFFFF:
-            limit -= 1 << 32                      # NUM2UINT into an `int` (map_ext.c:135)
-        if limit <= 0:
-            limit = LIMIT_DEFAULT                 # map_ext.c:142-146
-        c_limit = limit & 0xFFFF                  # uint16_t parameter (storage.h:110)
+        c_limit = _find_limit(limit)
         rows = (_native.TrigramMatch * max(c_limit, 1))()
-        res = self._lib.blurrily_storage_find(self._h, _as_bytes(needle), c_limit, rows)
-        if res < 0:
-            _raise_errno()
+        res = _check(self._lib.blurrily_storage_find(self._h, _as_bytes(needle), c_limit, rows))
         return [[rows[k].reference, rows[k].matches, rows[k].weight] for k in range(res)]
 
     def stats(self):
@@ -137,8 +204,7 @@ class RawMap:
     def close(self):
         """map_ext.c:188-202."""
         self._check_open()
-        if self._lib.blurrily_storage_close(C.byref(self._h)) < 0:
-            _raise_errno()
+        _check(self._lib.blurrily_storage_close(C.byref(self._h)))
         self._closed = True
         return None
 
@@ -153,45 +219,29 @@ class RawMap:
 
     def put_many_packed(self, packed, offsets, refs, weights=None):
         self._check_open()
-        buf = np.frombuffer(packed, dtype=np.uint8) if not isinstance(packed, np.ndarray) else packed
-        res = self._lib.blurrily_storage_put_many(
-            self._h, buf.ctypes.data if buf.size else None, offsets.ctypes.data, refs.ctypes.data,
-            None if weights is None else weights.ctypes.data, len(refs))
-        if res < 0:
-            _raise_errno()
-        return res
+        data, offsets, _ = _needles(packed, offsets)
+        return _check(self._lib.blurrily_storage_put_many(
+            self._h, data, offsets.ctypes.data, refs.ctypes.data, None if weights is None else weights.ctypes.data,
+            len(refs)))
 
     def find_batch_packed(self, packed, offsets, limit):
         """n finds in one GPU batch.  Returns (rows[n, limit, 3] uint32, counts[n] uint32)."""
         self._check_open()
-        n = len(offsets) - 1
-        limit = int(limit) & 0xFFFF
-        rows = np.zeros((n, max(limit, 1), 3), dtype=np.uint32)
-        counts = np.zeros(n, dtype=np.uint32)
-        buf = np.frombuffer(packed, dtype=np.uint8) if not isinstance(packed, np.ndarray) else packed
-        res = self._lib.blurrily_storage_find_batch(
-            self._h, buf.ctypes.data if buf.size else None, offsets.ctypes.data, n, limit,
-            rows.ctypes.data, counts.ctypes.data)
-        if res < 0:
-            _raise_errno()
-        return rows[:, :limit, :], counts
+        limit = _batch_limit(limit)
+        data, offsets, n = _needles(packed, offsets)
+        out, ptrs = _blocks(n, limit)
+        _check(self._lib.blurrily_storage_find_batch(self._h, data, offsets.ctypes.data, n, limit, *ptrs))
+        return out
 
     def find_batch_raw_packed(self, packed, offsets, limit):
         """find_batch_packed over un-normalised ASCII needles: normalize_string runs on the device
         (blurrily_storage_find_batch_raw).  Returns (rows, counts, non_ascii[n] uint32)."""
         self._check_open()
-        n = len(offsets) - 1
-        limit = int(limit) & 0xFFFF
-        rows = np.zeros((n, max(limit, 1), 3), dtype=np.uint32)
-        counts = np.zeros(n, dtype=np.uint32)
-        flags = np.zeros(n, dtype=np.uint32)
-        buf = np.frombuffer(packed, dtype=np.uint8) if not isinstance(packed, np.ndarray) else packed
-        res = self._lib.blurrily_storage_find_batch_raw(
-            self._h, buf.ctypes.data if buf.size else None, offsets.ctypes.data, n, limit,
-            rows.ctypes.data, counts.ctypes.data, flags.ctypes.data)
-        if res < 0:
-            _raise_errno()
-        return rows[:, :limit, :], counts, flags
+        limit = _batch_limit(limit)
+        data, offsets, n = _needles(packed, offsets)
+        out, ptrs = _blocks(n, limit, per_needle=1)
+        _check(self._lib.blurrily_storage_find_batch_raw(self._h, data, offsets.ctypes.data, n, limit, *ptrs))
+        return out
 
     # -- by reference (reference storage.h:72-87's commented-out get; find what is like a stored entry) ---------
     def _refs(self, references):
@@ -208,10 +258,8 @@ class RawMap:
         self._check_open()
         codes = np.zeros(28 * 28 * 28, dtype=np.uint16)
         weight = C.c_uint32(0)
-        res = self._lib.blurrily_storage_get(self._h, _u32(reference, "reference"), C.byref(weight), len(codes),
-                                             codes.ctypes.data)
-        if res < 0:
-            _raise_errno()
+        res = _check(self._lib.blurrily_storage_get(self._h, _u32(reference, "reference"), C.byref(weight), len(codes),
+                                                    codes.ctypes.data))
         if res == 0:
             return None
         return int(weight.value), codes[:res].tolist()
@@ -223,21 +271,15 @@ class RawMap:
         refs = self._refs(references)
         n = len(refs)
         # each distinct reference once: their codes together are at most the map's trigram count (the library's
-        # extraction also reads each once), so one call always fits; np.zeros only commits the pages written
+        # extraction also reads each once), so one call always fits
         uniq, inv = np.unique(refs, return_inverse=True)
         n_u = len(uniq)
         w_u = np.zeros(n_u, dtype=np.uint32)
         offs_u = np.zeros(n_u + 1, dtype=np.uint64)
-        cap = max(1, min(self.stats()["trigrams"], n_u * 28 * 28 * 28))
-        while True:
-            codes_u = np.zeros(cap, dtype=np.uint16)
-            res = self._lib.blurrily_storage_get_batch(self._h, uniq.ctypes.data if n_u else None, n_u, w_u.ctypes.data,
-                                                       offs_u.ctypes.data, codes_u.ctypes.data, cap)
-            if res == 0:
-                break
-            if C.get_errno() != 34 or int(offs_u[n_u]) <= cap:    # ERANGE: offs_u[n_u] holds the size needed
-                _raise_errno()
-            cap = int(offs_u[n_u])
+        codes_u = _call_growing(
+            lambda codes, cap: self._lib.blurrily_storage_get_batch(
+                self._h, uniq.ctypes.data if n_u else None, n_u, w_u.ctypes.data, offs_u.ctypes.data, codes, cap),
+            max(1, min(self.stats()["trigrams"], n_u * 28 * 28 * 28)), lambda: int(offs_u[n_u]), dtype=np.uint16)
         # back to the caller's order, duplicates included
         starts = offs_u[:-1].astype(np.int64)[inv]
         lens = np.diff(offs_u.astype(np.int64))[inv]
@@ -253,27 +295,16 @@ class RawMap:
         self._check_open()
         refs = self._refs(references)
         n = len(refs)
-        limit = int(limit) & 0xFFFF
-        rows = np.zeros((n, max(limit, 1), 3), dtype=np.uint32)
-        counts = np.zeros(n, dtype=np.uint32)
-        ntri = np.zeros(n, dtype=np.uint32)
-        res = self._lib.blurrily_storage_find_references(self._h, refs.ctypes.data if n else None, n, limit,
-                                                         rows.ctypes.data, counts.ctypes.data, ntri.ctypes.data)
-        if res < 0:
-            _raise_errno()
-        return rows[:, :limit, :], counts, ntri
+        limit = _batch_limit(limit)
+        out, ptrs = _blocks(n, limit, per_needle=1)
+        _check(self._lib.blurrily_storage_find_references(self._h, refs.ctypes.data if n else None, n, limit, *ptrs))
+        return out
 
     def find_by_reference(self, reference, limit):
         """``find``'s rows for the string `reference` was put with ([] when the map does not hold it); `limit` as find's."""
         self._check_open()
-        limit = int(limit)
-        if not -(1 << 31) <= limit <= _U32_MAX:
-            raise OverflowError("limit out of range")
-        if limit > 0x7FFFFFFF:
-            limit -= 1 << 32
-        if limit <= 0:
-            limit = LIMIT_DEFAULT
-        rows, counts, _ = RawMap.find_batch_by_reference(self, [_u32(reference, "reference")], limit & 0xFFFF)
+        c_limit = _find_limit(limit)
+        rows, counts, _ = RawMap.find_batch_by_reference(self, [_u32(reference, "reference")], c_limit)
         return rows[0, :counts[0]].tolist()
 
     # -- scoped find (no reference counterpart: the reference keeps one map per scope, map_group.rb) -----------
@@ -283,56 +314,53 @@ class RawMap:
         self._check_open()
         refs = self._refs(references if isinstance(references, np.ndarray) else list(references))
         h = C.c_void_p()
-        if self._lib.blurrily_scope_new(self._h, refs.ctypes.data if len(refs) else None, len(refs), C.byref(h)) < 0:
-            _raise_errno()
+        _check(self._lib.blurrily_scope_new(self._h, refs.ctypes.data if len(refs) else None, len(refs), C.byref(h)))
         return Scope(self, h, np.unique(refs))
 
-    def _scope_of(self, scope):
-        """(Scope, whether it is one-shot) -- a plain iterable of references is made into a scope for one call."""
-        if isinstance(scope, Scope):
-            if scope._map is not self:
-                raise ValueError("the scope belongs to another map")
-            scope._check_open()
-            return scope, False
-        return self.scope(scope), True
+    def _own(self, scope):
+        """`scope`, checked: a Scope of this map, and open."""
+        if scope._map is not self:
+            raise ValueError("the scope belongs to another map")
+        scope._check_open()
+        return scope
+
+    @_contextmanager
+    def _scopes_of(self, scopes):
+        """``with self._scopes_of(scopes) as scs``: a Scope for each element -- a plain iterable of references is made
+        into a scope for this one call, and closed on the way out (also when making a later one fails)."""
+        once = []
+        try:
+            scs = []
+            for s in scopes:
+                if isinstance(s, Scope):
+                    scs.append(self._own(s))
+                else:
+                    once.append(self.scope(s))
+                    scs.append(once[-1])
+            yield scs
+        finally:
+            for sc in once:
+                sc.close()
+
+    @staticmethod
+    def _handles(scs):
+        """The scopes' handles as the ``blurrily_scope*`` array of the each-in entries (NULL for none)."""
+        return (C.c_void_p * len(scs))(*[sc._h.value for sc in scs]) if scs else None
 
     def find_batch_in(self, scope, packed, offsets, limit):
         """``find_batch_packed`` among the scope's members only.  Returns (rows[n, limit, 3] uint32, counts[n] uint32)."""
         self._check_open()
-        sc, once = self._scope_of(scope)
-        try:
-            n = len(offsets) - 1
-            limit = int(limit) & 0xFFFF
-            rows = np.zeros((n, max(limit, 1), 3), dtype=np.uint32)
-            counts = np.zeros(n, dtype=np.uint32)
-            buf = np.frombuffer(packed, dtype=np.uint8) if not isinstance(packed, np.ndarray) else packed
-            offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
-            res = self._lib.blurrily_storage_find_batch_in(
-                self._h, sc._h, buf.ctypes.data if buf.size else None, offsets.ctypes.data, n, limit,
-                rows.ctypes.data, counts.ctypes.data)
-            if res < 0:
-                _raise_errno()
-            return rows[:, :limit, :], counts
-        finally:
-            if once:
-                sc.close()
+        if not isinstance(scope, Scope):
+            with self.scope(scope) as one_shot:
+                return RawMap.find_batch_in(self, one_shot, packed, offsets, limit)
+        sc = self._own(scope)
+        limit = _batch_limit(limit)
+        data, offsets, n = _needles(packed, offsets)
+        out, ptrs = _blocks(n, limit)
+        _check(self._lib.blurrily_storage_find_batch_in(self._h, sc._h, data, offsets.ctypes.data, n, limit, *ptrs))
+        return out
 
     # -- a scope per needle (DESIGN.md section 13) -----------------------------------------------------------------
-    def _scopes_of(self, scopes):
-        """(Scopes, the one-shot ones among them to close after the call) -- see ``_scope_of``."""
-        got, once = [], []
-        try:
-            for s in scopes:
-                sc, o = self._scope_of(s)
-                got.append(sc)
-                if o:
-                    once.append(sc)
-        except BaseException:
-            for sc in once:
-                sc.close()
-            raise
-        return got, once
-
     @staticmethod
     def _which(which, n):
         """uint32[n]: a scope index per needle, None -> NO_SCOPE (the whole map)."""
@@ -346,26 +374,15 @@ class RawMap:
         """``find_batch_packed`` with a scope per needle: needle i among ``scopes[which[i]]`` only, or the whole map when
         ``which[i]`` is None.  Returns (rows[n, limit, 3] uint32, counts[n] uint32)."""
         self._check_open()
-        n = len(offsets) - 1
-        which = self._which(which, n)
-        scs, once = self._scopes_of(scopes)
-        try:
-            limit = int(limit) & 0xFFFF
-            rows = np.zeros((n, max(limit, 1), 3), dtype=np.uint32)
-            counts = np.zeros(n, dtype=np.uint32)
-            buf = np.frombuffer(packed, dtype=np.uint8) if not isinstance(packed, np.ndarray) else packed
-            offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
-            hs = (C.c_void_p * max(len(scs), 1))(*[sc._h.value for sc in scs])
-            res = self._lib.blurrily_storage_find_batch_each_in(
-                self._h, hs if scs else None, len(scs), which.ctypes.data if n else None,
-                buf.ctypes.data if buf.size else None, offsets.ctypes.data, n, limit, rows.ctypes.data,
-                counts.ctypes.data)
-            if res < 0:
-                _raise_errno()
-            return rows[:, :limit, :], counts
-        finally:
-            for sc in once:
-                sc.close()
+        which = self._which(which, len(offsets) - 1)
+        with self._scopes_of(scopes) as scs:
+            limit = _batch_limit(limit)
+            data, offsets, n = _needles(packed, offsets)
+            out, ptrs = _blocks(n, limit)
+            _check(self._lib.blurrily_storage_find_batch_each_in(
+                self._h, self._handles(scs), len(scs), which.ctypes.data if n else None, data, offsets.ctypes.data, n,
+                limit, *ptrs))
+            return out
 
     def find_batch_by_reference_each_in(self, scopes, which, references, limit):
         """``find_batch_by_reference`` with a scope per reference, as ``find_batch_each_in``.
@@ -374,82 +391,52 @@ class RawMap:
         refs = self._refs(references)
         n = len(refs)
         which = self._which(which, n)
-        scs, once = self._scopes_of(scopes)
-        try:
-            limit = int(limit) & 0xFFFF
-            rows = np.zeros((n, max(limit, 1), 3), dtype=np.uint32)
-            counts = np.zeros(n, dtype=np.uint32)
-            ntri = np.zeros(n, dtype=np.uint32)
-            hs = (C.c_void_p * max(len(scs), 1))(*[sc._h.value for sc in scs])
-            res = self._lib.blurrily_storage_find_references_each_in(
-                self._h, hs if scs else None, len(scs), which.ctypes.data if n else None,
-                refs.ctypes.data if n else None, n, limit, rows.ctypes.data, counts.ctypes.data, ntri.ctypes.data)
-            if res < 0:
-                _raise_errno()
-            return rows[:, :limit, :], counts, ntri
-        finally:
-            for sc in once:
-                sc.close()
+        with self._scopes_of(scopes) as scs:
+            limit = _batch_limit(limit)
+            out, ptrs = _blocks(n, limit, per_needle=1)
+            _check(self._lib.blurrily_storage_find_references_each_in(
+                self._h, self._handles(scs), len(scs), which.ctypes.data if n else None,
+                refs.ctypes.data if n else None, n, limit, *ptrs))
+            return out
 
     def join_within(self, scopes, limit):
         """The blocked self-join: every member of every scope searched among its own scope (``find_by_reference``
         restricted to it), in one GPU batch.  Returns (references[k] uint32, which[k] uint32: the scope of each,
         rows: k lists of [ref, matches, weight]) over the members the map holds, scope after scope."""
         self._check_open()
-        scs, once = self._scopes_of(scopes)
-        try:
+        with self._scopes_of(scopes) as scs:
             parts = [sc._refs if sc._refs is not None else np.zeros(0, np.uint32) for sc in scs]
             refs = np.concatenate(parts).astype(np.uint32) if parts else np.zeros(0, np.uint32)
             which = np.repeat(np.arange(len(parts), dtype=np.uint32), [len(p) for p in parts])
             rows, counts, ntri = self.find_batch_by_reference_each_in(scs, which, refs, limit)
-        finally:
-            for sc in once:
-                sc.close()
         held = np.nonzero(ntri)[0]
-        return refs[held], which[held], [rows[i, :counts[i]].tolist() for i in held.tolist()]
+        return refs[held], which[held], _lists(rows[held], counts[held])
 
     def find_in(self, scope, needle, limit):
         """``find`` among the scope's members only (rows ``[ref, matches, weight]``); `limit` as find's."""
         self._check_open()
-        limit = int(limit)
-        if not -(1 << 31) <= limit <= _U32_MAX:
-            raise OverflowError("limit out of range")
-        if limit > 0x7FFFFFFF:
-            limit -= 1 << 32
-        if limit <= 0:
-            limit = LIMIT_DEFAULT
-        c_limit = limit & 0xFFFF
-        sc, once = self._scope_of(scope)
-        try:
-            rows = (_native.TrigramMatch * max(c_limit, 1))()
-            res = self._lib.blurrily_storage_find_in(self._h, sc._h, _as_bytes(needle), c_limit, rows)
-            if res < 0:
-                _raise_errno()
-            return [[rows[k].reference, rows[k].matches, rows[k].weight] for k in range(res)]
-        finally:
-            if once:
-                sc.close()
+        c_limit = _find_limit(limit)
+        if not isinstance(scope, Scope):
+            with self.scope(scope) as one_shot:
+                return RawMap.find_in(self, one_shot, needle, limit)
+        sc = self._own(scope)
+        rows = (_native.TrigramMatch * max(c_limit, 1))()
+        res = _check(self._lib.blurrily_storage_find_in(self._h, sc._h, _as_bytes(needle), c_limit, rows))
+        return [[rows[k].reference, rows[k].matches, rows[k].weight] for k in range(res)]
 
     # -- threshold find (no reference counterpart): every row at or above a bar of matches -------------------------
     @staticmethod
     def _bar(min_matches, min_permille):
-        mm, mp = _u32(min_matches, "min_matches"), _u32(min_permille, "min_permille")
-        if mp > 1000:
-            raise ValueError(f"min_permille {min_permille!r} above 1000")
-        return mm, mp
+        return _u32(min_matches, "min_matches"), _permille(min_permille)
 
-    def _above(self, call, n):
-        """One threshold call with room for a guessed number of rows, and once more with the exact room on ERANGE
-        (the library then reports what it needs).  Returns (rows[R, 3] uint32, row_off[n + 1] uint64)."""
+    @staticmethod
+    def _above(call, n):
+        """One threshold call ``call(rows, cap, row_off)`` with room for a guessed number of rows (and for the exact
+        number if that was too few).  Returns (rows[R, 3] uint32, row_off[n + 1] uint64)."""
         row_off = np.zeros(n + 1, dtype=np.uint64)
-        cap = max(1024, 16 * n)
-        while True:
-            rows = np.empty((cap, 3), dtype=np.uint32)
-            if call(rows.ctypes.data, cap, row_off.ctypes.data) == 0:
-                return rows[:int(row_off[n])], row_off
-            if C.get_errno() != 34 or int(row_off[n]) <= cap:      # ERANGE: row_off[n] holds the room needed
-                _raise_errno()
-            cap = int(row_off[n])
+        rows = _call_growing(lambda rows, cap: call(rows, cap, row_off.ctypes.data), max(1024, 16 * n),
+                             lambda: int(row_off[n]), row=(3,))
+        return rows[:int(row_off[n])], row_off
 
     def find_batch_above_packed(self, packed, offsets, min_matches=0, min_permille=0):
         """Every row of each needle with at least its bar of matches, bar = max(1, min_matches, ceil(min_permille * T /
@@ -457,10 +444,7 @@ class RawMap:
         uint64): needle i's rows are rows[row_off[i]:row_off[i + 1]]."""
         self._check_open()
         mm, mp = self._bar(min_matches, min_permille)
-        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
-        n = len(offsets) - 1
-        buf = np.frombuffer(packed, dtype=np.uint8) if not isinstance(packed, np.ndarray) else packed
-        data = buf.ctypes.data if buf.size else (None if n == 0 else C.addressof(_NO_BYTES))   # (n empty needles)
+        data, offsets, n = _needles(packed, offsets)
         return self._above(lambda rows, cap, off: self._lib.blurrily_storage_find_batch_above(
             self._h, data, offsets.ctypes.data, n, mm, mp, rows, cap, off), n)
 
@@ -470,14 +454,9 @@ class RawMap:
         mm, mp = self._bar(min_matches, min_permille)
         s = _as_bytes(needle)
         total = C.c_uint64(0)
-        cap = 1024
-        while True:
-            rows = np.empty((cap, 3), dtype=np.uint32)
-            if self._lib.blurrily_storage_find_above(self._h, s, mm, mp, rows.ctypes.data, cap, C.byref(total)) == 0:
-                return rows[:total.value].tolist()
-            if C.get_errno() != 34 or total.value <= cap:
-                _raise_errno()
-            cap = total.value
+        rows = _call_growing(lambda rows, cap: self._lib.blurrily_storage_find_above(
+            self._h, s, mm, mp, rows, cap, C.byref(total)), 1024, lambda: total.value, row=(3,))
+        return rows[:total.value].tolist()
 
     def find_batch_by_reference_above(self, references, min_matches=0, min_permille=0):
         """``find_batch_above_packed`` for stored references (each among its own rows; none for a reference the map
@@ -507,75 +486,46 @@ class RawMap:
         return refs[held], off, rows[at]
 
     # -- similarity find (no reference counterpart): the best rows by trigram Jaccard similarity --------------------
-    @staticmethod
-    def _floor(min_permille):
-        mp = _u32(min_permille, "min_permille")
-        if mp > 1000:
-            raise ValueError(f"min_permille {min_permille!r} above 1000")
-        return mp
-
     def find_batch_similar_packed(self, packed, offsets, limit, min_permille=0):
         """The best `limit` rows of each needle by trigram Jaccard similarity J = m / (T + R - m), at or above
         min_permille / 1000; J descending, then find's order.  Returns (rows[n, limit, 3] uint32, counts[n] uint32,
         row_ntri[n, limit] uint32: each row's R)."""
         self._check_open()
-        mp = self._floor(min_permille)
-        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
-        n = len(offsets) - 1
-        limit = int(limit) & 0xFFFF
-        rows = np.zeros((n, max(limit, 1), 3), dtype=np.uint32)
-        counts = np.zeros(n, dtype=np.uint32)
-        ntri = np.zeros((n, max(limit, 1)), dtype=np.uint32)
-        buf = np.frombuffer(packed, dtype=np.uint8) if not isinstance(packed, np.ndarray) else packed
-        data = buf.ctypes.data if buf.size else (None if n == 0 else C.addressof(_NO_BYTES))   # (n empty needles)
-        if self._lib.blurrily_storage_find_batch_similar(self._h, data, offsets.ctypes.data, n, limit, mp,
-                                                         rows.ctypes.data, counts.ctypes.data, ntri.ctypes.data) < 0:
-            _raise_errno()
-        return rows[:, :limit, :], counts, ntri[:, :limit]
+        mp = _permille(min_permille)
+        data, offsets, n = _needles(packed, offsets)
+        limit = _batch_limit(limit)
+        out, ptrs = _blocks(n, limit, row_ntri=True)
+        _check(self._lib.blurrily_storage_find_batch_similar(self._h, data, offsets.ctypes.data, n, limit, mp, *ptrs))
+        return out
 
     def find_similar(self, needle, limit, min_permille=0):
         """``find_batch_similar_packed`` for one needle: a list of ``[ref, matches, weight, R]``; `limit` as find's."""
         self._check_open()
-        mp = self._floor(min_permille)
-        limit = int(limit)
-        if not -(1 << 31) <= limit <= _U32_MAX:
-            raise OverflowError("limit out of range")
-        if limit > 0x7FFFFFFF:
-            limit -= 1 << 32
-        if limit <= 0:
-            limit = LIMIT_DEFAULT
-        c_limit = limit & 0xFFFF
+        mp = _permille(min_permille)
+        c_limit = _find_limit(limit)
         rows = np.zeros((max(c_limit, 1), 3), dtype=np.uint32)
         ntri = np.zeros(max(c_limit, 1), dtype=np.uint32)
-        res = self._lib.blurrily_storage_find_similar(self._h, _as_bytes(needle), c_limit, mp, rows.ctypes.data,
-                                                      ntri.ctypes.data)
-        if res < 0:
-            _raise_errno()
-        return [[int(r[0]), int(r[1]), int(r[2]), int(t)] for r, t in zip(rows[:res].tolist(), ntri[:res].tolist())]
+        res = _check(self._lib.blurrily_storage_find_similar(self._h, _as_bytes(needle), c_limit, mp, rows.ctypes.data,
+                                                             ntri.ctypes.data))
+        return [r + [t] for r, t in zip(rows[:res].tolist(), ntri[:res].tolist())]
 
     def find_batch_by_reference_similar(self, references, limit, min_permille=0):
         """``find_batch_similar_packed`` for stored references (each its own row at similarity 1; none for a reference
         the map does not hold).  Returns (rows[n, limit, 3] uint32, counts[n] uint32, row_ntri[n, limit] uint32,
         nb_trigrams[n] uint32)."""
         self._check_open()
-        mp = self._floor(min_permille)
+        mp = _permille(min_permille)
         refs = self._refs(references)
         n = len(refs)
-        limit = int(limit) & 0xFFFF
-        rows = np.zeros((n, max(limit, 1), 3), dtype=np.uint32)
-        counts = np.zeros(n, dtype=np.uint32)
-        ntri = np.zeros((n, max(limit, 1)), dtype=np.uint32)
-        nb = np.zeros(n, dtype=np.uint32)
-        if self._lib.blurrily_storage_find_references_similar(self._h, refs.ctypes.data if n else None, n, limit, mp,
-                                                              rows.ctypes.data, counts.ctypes.data, ntri.ctypes.data,
-                                                              nb.ctypes.data) < 0:
-            _raise_errno()
-        return rows[:, :limit, :], counts, ntri[:, :limit], nb
+        limit = _batch_limit(limit)
+        out, ptrs = _blocks(n, limit, row_ntri=True, per_needle=1)
+        _check(self._lib.blurrily_storage_find_references_similar(self._h, refs.ctypes.data if n else None, n, limit,
+                                                                  mp, *ptrs))
+        return out
 
     def sync_device(self):
         self._check_open()
-        if self._lib.blurrily_storage_sync_device(self._h) < 0:
-            _raise_errno()
+        _check(self._lib.blurrily_storage_sync_device(self._h))
 
     def device_info(self):
         self._check_open()
@@ -605,8 +555,7 @@ class RawMap:
         (uint32 array; bit i = PATH_FLAGS[i])."""
         self._check_open()
         out = np.zeros(n, dtype=np.uint32)
-        if self._lib.blurrily_storage_find_path_flags(self._h, out.ctypes.data, n) < 0:
-            _raise_errno()
+        _check(self._lib.blurrily_storage_find_path_flags(self._h, out.ctypes.data, n))
         return out
 
     def last_kernels(self):
@@ -620,29 +569,25 @@ class RawMap:
         """Measure now which sweep serves batches of n needles at this limit (blurrily_storage_tune): the needles
         given, repeated up to n, go through every sweep the class can take."""
         self._check_open()
-        buf = np.frombuffer(packed, dtype=np.uint8) if not isinstance(packed, np.ndarray) else packed
-        if self._lib.blurrily_storage_tune(self._h, buf.ctypes.data, offsets.ctypes.data, len(offsets) - 1, n, limit) < 0:
-            _raise_errno()
+        data, offsets, n_given = _needles(packed, offsets)
+        _check(self._lib.blurrily_storage_tune(self._h, data, offsets.ctypes.data, n_given, n, limit))
 
     def set_option(self, key, value):
         """A tunable of this map (include/blurrily_storage.h: blurrily_storage_set_option)."""
         self._check_open()
-        if self._lib.blurrily_storage_set_option(self._h, key.encode(), int(value)) < 0:
-            _raise_errno()
+        _check(self._lib.blurrily_storage_set_option(self._h, key.encode(), int(value)))
 
     def get_option(self, key):
         self._check_open()
         out = C.c_longlong(0)
-        if self._lib.blurrily_storage_get_option(self._h, key.encode(), C.byref(out)) < 0:
-            _raise_errno()
+        _check(self._lib.blurrily_storage_get_option(self._h, key.encode(), C.byref(out)))
         return int(out.value)
 
     def find_stats(self):
         """Counters of the last find call made while set_stats(True): a dict by STAT_NAMES."""
         self._check_open()
         out = (C.c_uint64 * 8)()
-        if self._lib.blurrily_storage_find_stats(self._h, out) < 0:
-            _raise_errno()
+        _check(self._lib.blurrily_storage_find_stats(self._h, out))
         return dict(zip(self.STAT_NAMES, (int(v) for v in out)))
 
     @property
@@ -673,16 +618,14 @@ class Scope:
         """How many of the scope's references the map holds now."""
         self._check_open()
         held = C.c_uint32()
-        if self._lib.blurrily_scope_members(self._h, C.byref(held)) < 0:
-            _raise_errno()
+        _check(self._lib.blurrily_scope_members(self._h, C.byref(held)))
         return held.value
 
     def close(self):
         if self._closed:
             return None
         self._closed = True
-        if self._lib.blurrily_scope_close(C.byref(self._h)) < 0:    # (it never touches the map)
-            _raise_errno()
+        _check(self._lib.blurrily_scope_close(C.byref(self._h)))    # (it never touches the map)
         return None
 
     def __enter__(self):
@@ -700,8 +643,7 @@ class Scope:
 
 def set_process_option(key, value):
     """A process-wide tunable ("host_threads", "build_trace"; include/blurrily_storage.h)."""
-    if _native.lib().blurrily_storage_set_option(None, key.encode(), int(value)) < 0:
-        _raise_errno()
+    _check(_native.lib().blurrily_storage_set_option(None, key.encode(), int(value)))
 
 
 def _as_bytes(s):
@@ -731,6 +673,17 @@ def normalize_string(needle):
         result = re.sub(r"[^a-z]", " ", result)
     result = re.sub(r"[ \t\r\n\f\v]+", " ", result)
     return result.strip(" \t\r\n\f\v").rstrip("\0 \t\r\n\f\v")
+
+
+def _limit_or_default(limit):
+    """Blurrily::Map's batched counterparts: a limit <= 0 means the default, as find's does."""
+    limit = int(limit)
+    return limit if limit > 0 else LIMIT_DEFAULT
+
+
+def _normalised(needles):
+    """The needles as ``find`` would send them, packed: (packed, offsets)."""
+    return _pack([_as_bytes(normalize_string(s)) for s in needles])
 
 
 class Map(RawMap):
@@ -777,11 +730,8 @@ class Map(RawMap):
 
     def find_batch_by_reference(self, references, limit=LIMIT_DEFAULT):
         """``[self.find_by_reference(r, limit) for r in references]`` in one GPU batch."""
-        limit = int(limit)
-        if limit <= 0:
-            limit = LIMIT_DEFAULT
-        rows, counts, _ = super().find_batch_by_reference(references, limit)
-        return [rows[i, :counts[i]].tolist() for i in range(len(counts))]
+        rows, counts, _ = super().find_batch_by_reference(references, _limit_or_default(limit))
+        return _lists(rows, counts)
 
     def find_in(self, scope, needle, limit=LIMIT_DEFAULT):
         """``find`` among the references of `scope` (a ``Scope`` or an iterable of references) only."""
@@ -789,25 +739,17 @@ class Map(RawMap):
 
     def find_batch_in(self, scope, needles, limit=LIMIT_DEFAULT):
         """``[self.find_in(scope, s, limit) for s in needles]`` in one GPU batch."""
-        limit = int(limit)
-        if limit <= 0:
-            limit = LIMIT_DEFAULT
-        packed, offsets = _pack([_as_bytes(normalize_string(s)) for s in needles])
-        rows, counts = super().find_batch_in(scope, packed, offsets, limit)
-        return [rows[i, :counts[i]].tolist() for i in range(len(needles))]
+        limit = _limit_or_default(limit)
+        return _lists(*super().find_batch_in(scope, *_normalised(needles), limit))
 
     def find_batch_each_in(self, scopes, which, needles, limit=LIMIT_DEFAULT):
         """``[self.find_in(scopes[w], s, limit) if w is not None else self.find(s, limit) for s, w in zip(needles,
         which)]`` in one GPU batch."""
-        limit = int(limit)
-        if limit <= 0:
-            limit = LIMIT_DEFAULT
-        packed, offsets = _pack([_as_bytes(normalize_string(s)) for s in needles])
-        rows, counts = super().find_batch_each_in(scopes, which, packed, offsets, limit)
-        return [rows[i, :counts[i]].tolist() for i in range(len(needles))]
+        limit = _limit_or_default(limit)
+        return _lists(*super().find_batch_each_in(scopes, which, *_normalised(needles), limit))
 
     def join_within(self, scopes, limit=LIMIT_DEFAULT):
-        return super().join_within(scopes, limit if int(limit) > 0 else LIMIT_DEFAULT)
+        return super().join_within(scopes, _limit_or_default(limit))
 
     def find_above(self, needle, min_matches=0, min_permille=0):
         """Every row of the normalised needle at or above its bar (``RawMap.find_above``)."""
@@ -815,9 +757,8 @@ class Map(RawMap):
 
     def find_batch_above(self, needles, min_matches=0, min_permille=0):
         """``[self.find_above(s, min_matches, min_permille) for s in needles]`` in one GPU batch."""
-        packed, offsets = _pack([_as_bytes(normalize_string(s)) for s in needles])
-        rows, row_off = super().find_batch_above_packed(packed, offsets, min_matches, min_permille)
-        return [rows[int(row_off[i]):int(row_off[i + 1])].tolist() for i in range(len(needles))]
+        rows, row_off = super().find_batch_above_packed(*_normalised(needles), min_matches, min_permille)
+        return [rows[lo:hi].tolist() for lo, hi in zip(row_off[:-1].tolist(), row_off[1:].tolist())]
 
     def find_similar(self, needle, limit=LIMIT_DEFAULT, min_permille=0):
         """The best rows of the normalised needle by trigram Jaccard similarity (``RawMap.find_similar``): a list of
@@ -826,19 +767,12 @@ class Map(RawMap):
 
     def find_batch_similar(self, needles, limit=LIMIT_DEFAULT, min_permille=0):
         """``[self.find_similar(s, limit, min_permille) for s in needles]`` in one GPU batch."""
-        limit = int(limit)
-        if limit <= 0:
-            limit = LIMIT_DEFAULT
-        packed, offsets = _pack([_as_bytes(normalize_string(s)) for s in needles])
-        rows, counts, ntri = super().find_batch_similar_packed(packed, offsets, limit, min_permille)
-        return [[r + [t] for r, t in zip(rows[i, :counts[i]].tolist(), ntri[i, :counts[i]].tolist())]
-                for i in range(len(needles))]
+        limit = _limit_or_default(limit)
+        return _lists(*super().find_batch_similar_packed(*_normalised(needles), limit, min_permille))
 
     def find_batch(self, needles, limit=LIMIT_DEFAULT):
         """``[self.find(s, limit) for s in needles]`` in one GPU batch."""
-        limit = int(limit)
-        if limit <= 0:
-            limit = LIMIT_DEFAULT
+        limit = _limit_or_default(limit)
         # ASCII needles go to the GPU as they are (normalize_string runs there); the others are
         # normalised here first -- NFKD is host work -- and pass through the device step unchanged
         raw = []
@@ -846,7 +780,6 @@ class Map(RawMap):
             b = _as_bytes(s)
             raw.append(b if b.isascii() else _as_bytes(normalize_string(b.decode("utf-8", "replace")
                                                                         if isinstance(s, bytes) else s)))
-        packed, offsets = _pack(raw)
-        rows, counts, flags = self.find_batch_raw_packed(packed, offsets, limit)
+        rows, counts, flags = self.find_batch_raw_packed(*_pack(raw), limit)
         assert not flags.any()
-        return [rows[i, :counts[i]].tolist() for i in range(len(needles))]
+        return _lists(rows, counts)

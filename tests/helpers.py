@@ -365,6 +365,29 @@ def resave_haystack():
     return m
 
 
+# ---- the C-ABI tests' shared pieces (tests/test_*_abi.py, test_ruby_glue_syntax.py) ----
+# the gem's own flags (ext/blurrily/extconf.rb:4-16), -Werror kept
+FLAGS = ["-std=c99", "-Wall", "-Wextra", "-Werror", "-DPLATFORM_LINUX", "-D_XOPEN_SOURCE=700", "-D_GNU_SOURCE=1",
+         "-D_FILE_OFFSET_BITS=64"]
+
+
+def compile_c(tmp_path, src):
+    """gcc over one C file with the gem's flags, headers from `tmp_path` (the recorded storage.h) and include/;
+    the finished process (returncode, stderr)."""
+    import subprocess
+    cmd = ["gcc", *FLAGS, "-I", str(tmp_path), "-I", os.path.join(ROOT, "include"), "-c", str(src),
+           "-o", str(tmp_path / "out.o")]
+    return subprocess.run(cmd, capture_output=True, text=True)
+
+
+def einval(call):
+    """`call()`, an entry point given a bad argument, answers -1 with errno EINVAL."""
+    import errno
+    C.set_errno(0)
+    assert call() == -1
+    assert C.get_errno() == errno.EINVAL
+
+
 def write_recorded_storage_h(directory):
     """A stand-in for the gem's ext/blurrily/storage.h, made from what tests/golden/ref_abi.json recorded of it:
     this repository's types, held to the recorded typedefs and row layout, and the nine functions declared with the

@@ -11,32 +11,12 @@ import numpy as np
 import pytest
 
 from blurrily_amd import Map, RawMap, _native
-from helpers import write_recorded_storage_h
+from helpers import compile_c, einval, write_recorded_storage_h
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = {"blurrily_storage_find_batch_above": 9, "blurrily_storage_find_above": 7,
        "blurrily_storage_find_references_above": 9}
-FLAGS = ["-std=c99", "-Wall", "-Wextra", "-Werror", "-DPLATFORM_LINUX", "-D_XOPEN_SOURCE=700", "-D_GNU_SOURCE=1",
-         "-D_FILE_OFFSET_BITS=64"]
 SRC = os.path.join(ROOT, "tests", "c", "header_compat_above.c")
-
-
-def _compile(tmp_path, src):
-    cmd = ["gcc", *FLAGS, "-I", str(tmp_path), "-I", os.path.join(ROOT, "include"), "-c", str(src),
-           "-o", str(tmp_path / "above.o")]
-    return subprocess.run(cmd, capture_output=True, text=True)
-
-
-def _has_gpu():
-    m = RawMap()
-    m.put(b"probe", 1, 0)
-    try:
-        m.sync_device()
-        return True
-    except OSError:
-        return False
-    finally:
-        m.close()
 
 
 def test_the_above_symbols_are_exported_with_argtypes():
@@ -58,7 +38,7 @@ def test_the_above_prototypes_compile_beside_the_reference_header(tmp_path, orde
         src.write_text(text)
     else:
         write_recorded_storage_h(tmp_path)
-    r = _compile(tmp_path, src)
+    r = compile_c(tmp_path, src)
     assert r.returncode == 0, r.stderr
 
 
@@ -70,13 +50,7 @@ def test_a_drifted_above_prototype_does_not_compile(tmp_path):
     assert drifted != text
     src = tmp_path / "drifted.c"
     src.write_text(drifted)
-    assert _compile(tmp_path, src).returncode != 0
-
-
-def _einval(call):
-    ctypes.set_errno(0)
-    assert call() == -1
-    assert ctypes.get_errno() == errno.EINVAL
+    assert compile_c(tmp_path, src).returncode != 0
 
 
 def test_argument_errors_are_einval_before_any_gpu():
@@ -89,24 +63,24 @@ def test_argument_errors_are_einval_before_any_gpu():
     row_off = np.zeros(2, dtype=np.uint64)
     refs = np.array([1], dtype=np.uint32)
     total = ctypes.c_uint64(0)
-    _einval(lambda: lib.blurrily_storage_find_batch_above(m.handle, packed, offs.ctypes.data, 1, 0, 1001,
+    einval(lambda: lib.blurrily_storage_find_batch_above(m.handle, packed, offs.ctypes.data, 1, 0, 1001,
                                                           rows.ctypes.data, 16, row_off.ctypes.data))
-    _einval(lambda: lib.blurrily_storage_find_batch_above(m.handle, packed, offs.ctypes.data, 1, 0, 500,
+    einval(lambda: lib.blurrily_storage_find_batch_above(m.handle, packed, offs.ctypes.data, 1, 0, 500,
                                                           rows.ctypes.data, 16, None))
-    _einval(lambda: lib.blurrily_storage_find_batch_above(m.handle, None, offs.ctypes.data, 1, 0, 500,
+    einval(lambda: lib.blurrily_storage_find_batch_above(m.handle, None, offs.ctypes.data, 1, 0, 500,
                                                           rows.ctypes.data, 16, row_off.ctypes.data))
-    _einval(lambda: lib.blurrily_storage_find_batch_above(m.handle, packed, None, 1, 0, 500,
+    einval(lambda: lib.blurrily_storage_find_batch_above(m.handle, packed, None, 1, 0, 500,
                                                           rows.ctypes.data, 16, row_off.ctypes.data))
-    _einval(lambda: lib.blurrily_storage_find_batch_above(None, packed, offs.ctypes.data, 1, 0, 500,
+    einval(lambda: lib.blurrily_storage_find_batch_above(None, packed, offs.ctypes.data, 1, 0, 500,
                                                           rows.ctypes.data, 16, row_off.ctypes.data))
-    _einval(lambda: lib.blurrily_storage_find_above(m.handle, b"san jose", 0, 1001, rows.ctypes.data, 16,
+    einval(lambda: lib.blurrily_storage_find_above(m.handle, b"san jose", 0, 1001, rows.ctypes.data, 16,
                                                     ctypes.byref(total)))
-    _einval(lambda: lib.blurrily_storage_find_above(m.handle, None, 0, 500, rows.ctypes.data, 16, ctypes.byref(total)))
-    _einval(lambda: lib.blurrily_storage_find_references_above(m.handle, refs.ctypes.data, 1, 0, 1001,
+    einval(lambda: lib.blurrily_storage_find_above(m.handle, None, 0, 500, rows.ctypes.data, 16, ctypes.byref(total)))
+    einval(lambda: lib.blurrily_storage_find_references_above(m.handle, refs.ctypes.data, 1, 0, 1001,
                                                                rows.ctypes.data, 16, row_off.ctypes.data, None))
-    _einval(lambda: lib.blurrily_storage_find_references_above(m.handle, refs.ctypes.data, 1, 0, 500,
+    einval(lambda: lib.blurrily_storage_find_references_above(m.handle, refs.ctypes.data, 1, 0, 500,
                                                                rows.ctypes.data, 16, None, None))
-    _einval(lambda: lib.blurrily_storage_find_references_above(m.handle, None, 1, 0, 500,
+    einval(lambda: lib.blurrily_storage_find_references_above(m.handle, None, 1, 0, 500,
                                                                rows.ctypes.data, 16, row_off.ctypes.data, None))
     m.close()
 
@@ -125,8 +99,8 @@ def test_the_python_surface_checks_the_bar():
     m.close()
 
 
-def test_valid_calls_without_a_gpu_are_enodev():
-    if _has_gpu():
+def test_valid_calls_without_a_gpu_are_enodev(has_gpu):
+    if has_gpu:
         pytest.skip("a GPU is usable here: tests/test_gpu_above.py covers the calls")
     lib = _native.lib()
     m = RawMap()

@@ -311,6 +311,21 @@ def test_map_surface_normalises_and_takes_plain_iterables(geo):
     mp.close()
 
 
+def test_a_scoped_batch_with_empty_needles_equals_the_single_finds():
+    """An empty needle is a valid find (no rows); a batch of nothing but empty needles has no bytes to point to."""
+    mp = Map()
+    for ref, s in ((1, "san jose"), (2, "san jose california"), (3, "santa cruz")):
+        mp.put(s, ref)
+    with mp.scope([1, 3]) as held:
+        for scope in (held, [1, 3]):
+            for needles in (["", "san jose", ""], [""], ["", "", ""], ["  ", "!"]):
+                assert mp.find_batch_in(scope, needles) == [mp.find_in(scope, s) for s in needles], needles
+        assert mp.find_in(held, "") == [] and mp.find_batch_in(held, ["", "san jose", ""])[1] != []
+        rows, counts = RawMap.find_batch_in(mp, held, b"", np.zeros(2, dtype=np.uint64), 10)
+        assert rows.shape == (1, 10, 3) and counts.tolist() == [0]
+    mp.close()
+
+
 def test_configs2_scale_every_97th_and_every_997th_reference(geonames_full):
     """configs[2]'s haystack: 4 096 needles within every 97th reference (beyond the direct strategy's size: the mask
     serves both) and every 997th (served directly when forced), the strategies against each other and 256 needles against

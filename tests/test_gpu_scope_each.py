@@ -391,6 +391,25 @@ def test_map_surface_normalises_and_joins_within_blocks():
     mp.close()
 
 
+def test_an_each_in_batch_with_empty_needles_equals_the_single_finds():
+    """An empty needle is a valid find (no rows); a batch of nothing but empty needles has no bytes to point to."""
+    mp = Map()
+    for ref, s in ((1, "san jose"), (2, "san jose california"), (3, "santa cruz")):
+        mp.put(s, ref)
+    with mp.scope([1, 3]) as held:
+        for scope in (held, [1, 3]):
+            for needles in (["", "san jose", ""], [""], ["", "", ""], ["  ", "!"]):
+                n = len(needles)
+                assert mp.find_batch_each_in([scope], [0] * n, needles) == [mp.find_in(scope, s) for s in needles]
+                which = [None if i % 2 else 1 for i in range(n)]
+                assert mp.find_batch_each_in([[2], scope], which, needles) == \
+                    [mp.find(s) if w is None else mp.find_in(scope, s) for s, w in zip(needles, which)], needles
+        assert mp.find_batch_each_in([held], [0, 0, 0], ["", "san jose", ""])[1] != []
+        rows, counts = RawMap.find_batch_each_in(mp, [held], [0], b"", np.zeros(2, dtype=np.uint64), 10)
+        assert rows.shape == (1, 10, 3) and counts.tolist() == [0]
+    mp.close()
+
+
 def test_configs2_scale_100k_needles_over_1000_blocks(geonames_full):
     """configs[2]'s haystack: every 8th reference in 1 000 blocks, 100 000 needles each in a block at random (a tenth
     with no scope); 200 needles from 20 blocks against the restatement"""

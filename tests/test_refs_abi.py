@@ -12,13 +12,11 @@ import pytest
 
 from blurrily_amd import Map, RawMap, _native
 from blurrily_amd.map import ClosedError
-from helpers import write_recorded_storage_h
+from helpers import FLAGS, compile_c, write_recorded_storage_h
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("blurrily_storage_get", "blurrily_storage_get_batch", "blurrily_storage_find_references",
        "blurrily_storage_find_references_device")
-FLAGS = ["-std=c99", "-Wall", "-Wextra", "-Werror", "-DPLATFORM_LINUX", "-D_XOPEN_SOURCE=700", "-D_GNU_SOURCE=1",
-         "-D_FILE_OFFSET_BITS=64"]
 
 
 def test_the_new_symbols_are_exported_with_argtypes():
@@ -43,9 +41,7 @@ def test_the_new_prototypes_compile_beside_the_reference_header(tmp_path, order)
         open(src, "w").write(text)
     else:
         write_recorded_storage_h(tmp_path)
-    cmd = ["gcc", *FLAGS, "-I", str(tmp_path), "-I", os.path.join(ROOT, "include"), "-c", src,
-           "-o", str(tmp_path / "refs.o")]
-    r = subprocess.run(cmd, capture_output=True, text=True)
+    r = compile_c(tmp_path, src)
     assert r.returncode == 0, r.stderr
 
 
@@ -57,9 +53,7 @@ def test_a_drifted_new_prototype_does_not_compile(tmp_path):
     assert drifted != text
     src = tmp_path / "drifted.c"
     src.write_text(drifted)
-    cmd = ["gcc", *FLAGS, "-I", str(tmp_path), "-I", os.path.join(ROOT, "include"), "-c", str(src),
-           "-o", str(tmp_path / "d.o")]
-    assert subprocess.run(cmd, capture_output=True, text=True).returncode != 0
+    assert compile_c(tmp_path, src).returncode != 0
 
 
 def test_by_reference_fails_loudly_without_a_gpu(has_gpu, capfd):

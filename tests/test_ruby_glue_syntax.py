@@ -20,6 +20,7 @@ import subprocess
 
 import pytest
 
+import helpers
 from helpers import load_golden, write_recorded_storage_h
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -27,8 +28,7 @@ GEM_EXT = os.environ.get("BLURRILY_GEM_EXT", "/root/reference/ext/blurrily")
 MOCK = os.path.join(ROOT, "tests", "c", "mock_ruby")
 GLUE = os.path.join(ROOT, "ruby", "ext", "blurrily")
 # the gem's own flags (ext/blurrily/extconf.rb:4-16), -Werror kept: the glue must be warning-free
-FLAGS = ["-std=c99", "-Wall", "-Wextra", "-Werror", "-DPLATFORM_LINUX", "-D_XOPEN_SOURCE=700", "-D_GNU_SOURCE=1",
-         "-D_FILE_OFFSET_BITS=64", "-I", MOCK]
+FLAGS = [*helpers.FLAGS, "-I", MOCK]
 INCLUDE = ["-I", os.path.join(ROOT, "include")]
 ABI = load_golden("ref_abi.json")
 

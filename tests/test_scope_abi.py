@@ -11,19 +11,11 @@ import numpy as np
 import pytest
 
 from blurrily_amd import Map, RawMap, Scope, _native
-from helpers import write_recorded_storage_h
+from helpers import FLAGS, compile_c, write_recorded_storage_h
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = {"blurrily_scope_new": 4, "blurrily_scope_close": 1, "blurrily_scope_members": 2, "blurrily_storage_find_in": 5,
        "blurrily_storage_find_batch_in": 8, "blurrily_storage_find_batch_in_device": 10}
-FLAGS = ["-std=c99", "-Wall", "-Wextra", "-Werror", "-DPLATFORM_LINUX", "-D_XOPEN_SOURCE=700", "-D_GNU_SOURCE=1",
-         "-D_FILE_OFFSET_BITS=64"]
-
-
-def _compile(tmp_path, src):
-    cmd = ["gcc", *FLAGS, "-I", str(tmp_path), "-I", os.path.join(ROOT, "include"), "-c", str(src),
-           "-o", str(tmp_path / "scope.o")]
-    return subprocess.run(cmd, capture_output=True, text=True)
 
 
 def test_the_scope_symbols_are_exported_with_argtypes():
@@ -45,7 +37,7 @@ def test_the_scope_prototypes_compile_beside_the_reference_header(tmp_path, orde
         src.write_text(text)
     else:
         write_recorded_storage_h(tmp_path)
-    r = _compile(tmp_path, src)
+    r = compile_c(tmp_path, src)
     assert r.returncode == 0, r.stderr
 
 
@@ -56,7 +48,7 @@ def test_a_drifted_scope_prototype_does_not_compile(tmp_path):
     assert drifted != text
     src = tmp_path / "drifted.c"
     src.write_text(drifted)
-    assert _compile(tmp_path, src).returncode != 0
+    assert compile_c(tmp_path, src).returncode != 0
 
 
 def _new_scope(m, refs):
@@ -187,6 +179,27 @@ def test_a_scoped_find_fails_loudly_without_a_gpu(has_gpu, capfd):
             call()
         assert e.value.errno == errno.ENODEV
     assert "no usable HIP device" in capfd.readouterr().err
+    m.close()
+
+
+def test_a_scoped_batch_of_nothing_but_empty_needles_is_a_valid_call(has_gpu):
+    """Such a batch has no bytes to point to; the binding passes a dummy byte (NULL with n > 0 is EINVAL), so the call
+    answers what any valid call does: its rows where a GPU is usable, ENODEV where none is."""
+    m = Map()
+    m.put("london", 123)
+    calls = (lambda: m.find_batch_in([123], [""]), lambda: m.find_batch_in([123], ["", "  ", ""]),
+             lambda: RawMap.find_batch_in(m, [123], b"", np.zeros(2, dtype=np.uint64), 10))
+    with m.scope([123]) as held:
+        calls += (lambda: m.find_batch_in(held, [""]),)
+        for call in calls:
+            if has_gpu:
+                call()
+                continue
+            with pytest.raises(OSError) as e:
+                call()
+            assert e.value.errno == errno.ENODEV
+    if has_gpu:
+        assert m.find_batch_in([123], [""]) == [m.find_in([123], "")] == [[]]
     m.close()
 
 

@@ -7,23 +7,16 @@ import errno
 import os
 import subprocess
 
+import numpy as np
 import pytest
 
 from blurrily_amd import Map, RawMap, _native
-from helpers import write_recorded_storage_h
+from helpers import compile_c, einval, write_recorded_storage_h
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = {"blurrily_storage_find_batch_each_in": 10, "blurrily_storage_find_batch_each_in_device": 12,
        "blurrily_storage_find_references_each_in": 10}
-FLAGS = ["-std=c99", "-Wall", "-Wextra", "-Werror", "-DPLATFORM_LINUX", "-D_XOPEN_SOURCE=700", "-D_GNU_SOURCE=1",
-         "-D_FILE_OFFSET_BITS=64"]
 SRC = os.path.join(ROOT, "tests", "c", "header_compat_scope_each.c")
-
-
-def _compile(tmp_path, src):
-    cmd = ["gcc", *FLAGS, "-I", str(tmp_path), "-I", os.path.join(ROOT, "include"), "-c", str(src),
-           "-o", str(tmp_path / "scope_each.o")]
-    return subprocess.run(cmd, capture_output=True, text=True)
 
 
 def test_the_each_in_symbols_are_exported_with_argtypes():
@@ -46,7 +39,7 @@ def test_the_each_in_prototypes_compile_beside_the_reference_header(tmp_path, or
         src.write_text(text)
     else:
         write_recorded_storage_h(tmp_path)
-    r = _compile(tmp_path, src)
+    r = compile_c(tmp_path, src)
     assert r.returncode == 0, r.stderr
 
 
@@ -62,7 +55,7 @@ def test_a_drifted_each_in_prototype_does_not_compile(tmp_path, drift):
     assert drifted != text
     src = tmp_path / "drifted.c"
     src.write_text(drifted)
-    assert _compile(tmp_path, src).returncode != 0
+    assert compile_c(tmp_path, src).returncode != 0
 
 
 def _scope(m, refs):
@@ -70,12 +63,6 @@ def _scope(m, refs):
     h = ctypes.c_void_p()
     assert _native.lib().blurrily_scope_new(m.handle, arr, len(refs), ctypes.byref(h)) == 0
     return h
-
-
-def _einval(call):
-    ctypes.set_errno(0)
-    assert call() == -1
-    assert ctypes.get_errno() == errno.EINVAL
 
 
 def test_every_argument_error_is_einval_before_a_gpu_is_asked_for(capfd):
@@ -106,16 +93,16 @@ def test_every_argument_error_is_einval_before_a_gpu_is_asked_for(capfd):
                                                                       2, 10, None, None, None)
 
     for make in (batch, by_ref):
-        _einval(make(two, 2, [0, 2]))                                  # which[i] >= n_scopes
-        _einval(make(two, 1, [0, 1]))
-        _einval(make(None, 0, [0, _native.NO_SCOPE]))                  # ... with no scopes at all
-        _einval(make(None, 2, [0, 1]))                                 # n_scopes > 0, scopes NULL
-        _einval(make((ctypes.c_void_p * 2)(a.value, None), 2, [0, 1]))            # a NULL handle
-        _einval(make((ctypes.c_void_p * 2)(a.value, foreign.value), 2, [0, 0]))   # a scope of another map
-    _einval(batch(two, 2, [0, 1], mp=other))                           # every scope is another map's
-    _einval(device(None, 2))
-    _einval(device((ctypes.c_void_p * 2)(a.value, foreign.value), 2))
-    _einval(lambda: lib.blurrily_storage_find_batch_each_in(None, two, 2, None, None, None, 0, 10, None, None))
+        einval(make(two, 2, [0, 2]))                                  # which[i] >= n_scopes
+        einval(make(two, 1, [0, 1]))
+        einval(make(None, 0, [0, _native.NO_SCOPE]))                  # ... with no scopes at all
+        einval(make(None, 2, [0, 1]))                                 # n_scopes > 0, scopes NULL
+        einval(make((ctypes.c_void_p * 2)(a.value, None), 2, [0, 1]))            # a NULL handle
+        einval(make((ctypes.c_void_p * 2)(a.value, foreign.value), 2, [0, 0]))   # a scope of another map
+    einval(batch(two, 2, [0, 1], mp=other))                           # every scope is another map's
+    einval(device(None, 2))
+    einval(device((ctypes.c_void_p * 2)(a.value, foreign.value), 2))
+    einval(lambda: lib.blurrily_storage_find_batch_each_in(None, two, 2, None, None, None, 0, 10, None, None))
     assert "no usable HIP device" not in capfd.readouterr().err      # (no GPU was asked for)
     for h in (a, b, foreign):
         assert lib.blurrily_scope_close(ctypes.byref(h)) == 0
@@ -153,6 +140,26 @@ def test_valid_calls_fail_loudly_without_a_gpu(has_gpu, capfd):
             call()
         assert e.value.errno == errno.ENODEV
     assert "no usable HIP device" in capfd.readouterr().err
+    m.close()
+
+
+def test_an_each_in_batch_of_nothing_but_empty_needles_is_a_valid_call(has_gpu):
+    """Such a batch has no bytes to point to; the binding passes a dummy byte (NULL with n > 0 is EINVAL), so the call
+    answers what any valid call does: its rows where a GPU is usable, ENODEV where none is."""
+    m = Map()
+    m.put("london", 1)
+    with m.scope([1]) as held:
+        for call in (lambda: m.find_batch_each_in([[1]], [0], [""]),
+                     lambda: m.find_batch_each_in([held, [1]], [0, None, 1], ["", "  ", ""]),
+                     lambda: RawMap.find_batch_each_in(m, [held], [0], b"", np.zeros(2, dtype=np.uint64), 10)):
+            if has_gpu:
+                call()
+                continue
+            with pytest.raises(OSError) as e:
+                call()
+            assert e.value.errno == errno.ENODEV
+    if has_gpu:
+        assert m.find_batch_each_in([[1]], [0], [""]) == [m.find_in([1], "")] == [[]]
     m.close()
 
 

@@ -11,32 +11,12 @@ import numpy as np
 import pytest
 
 from blurrily_amd import Map, RawMap, _native
-from helpers import write_recorded_storage_h
+from helpers import compile_c, einval, write_recorded_storage_h
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = {"blurrily_storage_find_batch_similar": 9, "blurrily_storage_find_similar": 6,
        "blurrily_storage_find_references_similar": 9}
-FLAGS = ["-std=c99", "-Wall", "-Wextra", "-Werror", "-DPLATFORM_LINUX", "-D_XOPEN_SOURCE=700", "-D_GNU_SOURCE=1",
-         "-D_FILE_OFFSET_BITS=64"]
 SRC = os.path.join(ROOT, "tests", "c", "header_compat_similar.c")
-
-
-def _compile(tmp_path, src):
-    cmd = ["gcc", *FLAGS, "-I", str(tmp_path), "-I", os.path.join(ROOT, "include"), "-c", str(src),
-           "-o", str(tmp_path / "similar.o")]
-    return subprocess.run(cmd, capture_output=True, text=True)
-
-
-def _has_gpu():
-    m = RawMap()
-    m.put(b"probe", 1, 0)
-    try:
-        m.sync_device()
-        return True
-    except OSError:
-        return False
-    finally:
-        m.close()
 
 
 def test_the_similar_symbols_are_exported_with_argtypes():
@@ -58,7 +38,7 @@ def test_the_similar_prototypes_compile_beside_the_reference_header(tmp_path, or
         src.write_text(text)
     else:
         write_recorded_storage_h(tmp_path)
-    r = _compile(tmp_path, src)
+    r = compile_c(tmp_path, src)
     assert r.returncode == 0, r.stderr
 
 
@@ -70,13 +50,7 @@ def test_a_drifted_similar_prototype_does_not_compile(tmp_path):
     assert drifted != text
     src = tmp_path / "drifted.c"
     src.write_text(drifted)
-    assert _compile(tmp_path, src).returncode != 0
-
-
-def _einval(call):
-    ctypes.set_errno(0)
-    assert call() == -1
-    assert ctypes.get_errno() == errno.EINVAL
+    assert compile_c(tmp_path, src).returncode != 0
 
 
 def test_argument_errors_are_einval_before_any_gpu():
@@ -92,23 +66,23 @@ def test_argument_errors_are_einval_before_any_gpu():
     batch = lib.blurrily_storage_find_batch_similar
     by_ref = lib.blurrily_storage_find_references_similar
     # min_permille > 1000
-    _einval(lambda: batch(m.handle, packed, offs.ctypes.data, 1, 10, 1001, rows.ctypes.data, counts.ctypes.data, None))
-    _einval(lambda: lib.blurrily_storage_find_similar(m.handle, b"san jose", 10, 1001, rows.ctypes.data, None))
-    _einval(lambda: by_ref(m.handle, refs.ctypes.data, 1, 10, 1001, rows.ctypes.data, counts.ctypes.data, None, None))
+    einval(lambda: batch(m.handle, packed, offs.ctypes.data, 1, 10, 1001, rows.ctypes.data, counts.ctypes.data, None))
+    einval(lambda: lib.blurrily_storage_find_similar(m.handle, b"san jose", 10, 1001, rows.ctypes.data, None))
+    einval(lambda: by_ref(m.handle, refs.ctypes.data, 1, 10, 1001, rows.ctypes.data, counts.ctypes.data, None, None))
     # counts NULL (with n == 0 too)
-    _einval(lambda: batch(m.handle, packed, offs.ctypes.data, 1, 10, 500, rows.ctypes.data, None, None))
-    _einval(lambda: batch(m.handle, None, None, 0, 10, 500, None, None, None))
-    _einval(lambda: by_ref(m.handle, refs.ctypes.data, 1, 10, 500, rows.ctypes.data, None, None, None))
+    einval(lambda: batch(m.handle, packed, offs.ctypes.data, 1, 10, 500, rows.ctypes.data, None, None))
+    einval(lambda: batch(m.handle, None, None, 0, 10, 500, None, None, None))
+    einval(lambda: by_ref(m.handle, refs.ctypes.data, 1, 10, 500, rows.ctypes.data, None, None, None))
     # results NULL with limit > 0 and n > 0
-    _einval(lambda: batch(m.handle, packed, offs.ctypes.data, 1, 10, 500, None, counts.ctypes.data, None))
-    _einval(lambda: lib.blurrily_storage_find_similar(m.handle, b"san jose", 10, 500, None, None))
-    _einval(lambda: by_ref(m.handle, refs.ctypes.data, 1, 10, 500, None, counts.ctypes.data, None, None))
+    einval(lambda: batch(m.handle, packed, offs.ctypes.data, 1, 10, 500, None, counts.ctypes.data, None))
+    einval(lambda: lib.blurrily_storage_find_similar(m.handle, b"san jose", 10, 500, None, None))
+    einval(lambda: by_ref(m.handle, refs.ctypes.data, 1, 10, 500, None, counts.ctypes.data, None, None))
     # packed or offsets NULL with n > 0; references NULL with n > 0; no needle; no map
-    _einval(lambda: batch(m.handle, None, offs.ctypes.data, 1, 10, 500, rows.ctypes.data, counts.ctypes.data, None))
-    _einval(lambda: batch(m.handle, packed, None, 1, 10, 500, rows.ctypes.data, counts.ctypes.data, None))
-    _einval(lambda: by_ref(m.handle, None, 1, 10, 500, rows.ctypes.data, counts.ctypes.data, None, None))
-    _einval(lambda: lib.blurrily_storage_find_similar(m.handle, None, 10, 500, rows.ctypes.data, None))
-    _einval(lambda: batch(None, packed, offs.ctypes.data, 1, 10, 500, rows.ctypes.data, counts.ctypes.data, None))
+    einval(lambda: batch(m.handle, None, offs.ctypes.data, 1, 10, 500, rows.ctypes.data, counts.ctypes.data, None))
+    einval(lambda: batch(m.handle, packed, None, 1, 10, 500, rows.ctypes.data, counts.ctypes.data, None))
+    einval(lambda: by_ref(m.handle, None, 1, 10, 500, rows.ctypes.data, counts.ctypes.data, None, None))
+    einval(lambda: lib.blurrily_storage_find_similar(m.handle, None, 10, 500, rows.ctypes.data, None))
+    einval(lambda: batch(None, packed, offs.ctypes.data, 1, 10, 500, rows.ctypes.data, counts.ctypes.data, None))
     m.close()
 
 
@@ -132,8 +106,8 @@ def test_the_python_surface_checks_its_arguments():
     m.close()
 
 
-def test_valid_calls_without_a_gpu_are_enodev():
-    if _has_gpu():
+def test_valid_calls_without_a_gpu_are_enodev(has_gpu):
+    if has_gpu:
         pytest.skip("a GPU is usable here: tests/test_gpu_similar.py covers the calls")
     lib = _native.lib()
     m = RawMap()

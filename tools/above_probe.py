@@ -12,7 +12,6 @@
 Writes the JSON object to --out after every step (a step that runs out of time leaves the ones before it).
 Usage: python tools/above_probe.py [--scale 1.0] [--out FILE] [--skip-join]"""
 import argparse
-import json
 import os
 import sys
 import time
@@ -25,20 +24,9 @@ for p in (ROOT, os.path.join(ROOT, "tools")):
         sys.path.insert(0, p)
 
 import workloads as W  # noqa: E402
-from blurrily_amd import Map, RawMap, _native  # noqa: E402
+from blurrily_amd import Map, _native  # noqa: E402
 
 ROW_BUDGET = 400_000_000                                     # rows a filled call may return here (12 B each)
-
-
-def best_of(fn, reps=2):
-    fn()
-    best = None
-    for _ in range(reps):
-        t0 = time.perf_counter()
-        out = fn()
-        dt = time.perf_counter() - t0
-        best = dt if best is None else min(best, dt)
-    return best, out
 
 
 def main():
@@ -50,23 +38,16 @@ def main():
     res = {"haystack": "configs[2] geonames", "scale": args.scale}
 
     def dump():
-        with open(args.out, "w") as f:
-            json.dump(res, f, indent=1)
-        print(json.dumps(res), flush=True)
+        W.dump_json(res, args.out)
 
-    hay, off = W.bench_haystack("geonames", args.scale)
-    n = len(off) - 1
-    m = RawMap()
-    refs = np.arange(1, n + 1, dtype=np.uint32)
-    t0 = time.perf_counter()
-    m.put_many_packed(hay, off, refs)
-    m.sync_device()
+    m, hay, off, refs, put_s, sync_s = W.bench_map("geonames", args.scale)
+    n = len(refs)
     res["references"] = n
-    res["build_s"] = round(time.perf_counter() - t0, 2)
+    res["build_s"] = round(put_s + sync_s, 2)
     q, qo = W.bench_needles(hay, off, "geonames", args.scale)
     nq = len(qo) - 1
     res["needles"] = nq
-    dt, (_, counts) = best_of(lambda: m.find_batch_packed(q, qo, 10))
+    dt, (_, counts) = W.best_of(lambda: m.find_batch_packed(q, qo, 10))
     res["find_batch_limit10"] = {"s": round(dt, 4), "needles_per_s": round(nq / dt), "rows_per_needle":
                                  round(float(counts.mean()), 3)}
     dump()
@@ -79,13 +60,13 @@ def main():
         return row_off.copy()
 
     for mp in (500, 700, 900):
-        dt, offs = best_of(lambda: count_only(mp))
+        dt, offs = W.best_of(lambda: count_only(mp))
         r = {"count_only_s": round(dt, 4), "count_only_needles_per_s": round(nq / dt),
              "rows_per_needle": round(int(offs[-1]) / nq, 3), "rows": int(offs[-1])}
         k = int(np.searchsorted(offs, ROW_BUDGET, side="right")) - 1      # needles whose rows fit the budget
         k = max(1, min(nq, k))
         qk, qok = q[:int(qo[k])], qo[:k + 1]
-        dt, (_, ro) = best_of(lambda: m.find_batch_above_packed(qk, qok, 0, mp))
+        dt, (_, ro) = W.best_of(lambda: m.find_batch_above_packed(qk, qok, 0, mp))
         r.update({"filled_needles": k, "filled_s": round(dt, 4), "filled_needles_per_s": round(k / dt),
                   "filled_rows": int(ro[-1]), "last_kernels": m.last_kernels()})
         res[f"above_{mp}"] = r
@@ -115,6 +96,7 @@ def main():
             res["join_above_800"].update({"s": round(time.perf_counter() - t0, 2), "references": int(len(jr)),
                                           "pairs_filled": int(joff[-1])})
             dump()
+
 
 if __name__ == "__main__":
     main()

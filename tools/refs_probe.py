@@ -29,7 +29,7 @@ for p in (ROOT, os.path.join(ROOT, "tools")):
 import torch  # noqa: E402
 
 import workloads as W  # noqa: E402
-from blurrily_amd import RawMap, _native  # noqa: E402
+from blurrily_amd import _native  # noqa: E402
 
 
 def _events_ms(fn, reps=3):
@@ -52,14 +52,9 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--extract-only", action="store_true")
     args = ap.parse_args()
-    hay, off = W.bench_haystack("geonames", args.scale)
-    n = len(off) - 1
-    m = RawMap()
-    refs = np.arange(1, n + 1, dtype=np.uint32)
-    m.put_many_packed(hay, off, refs)
-    t0 = time.perf_counter()
-    m.sync_device()
-    out = {"haystack": "geonames", "n_refs": n, "build_s": round(time.perf_counter() - t0, 2)}
+    m, hay, off, refs, _, sync_s = W.bench_map("geonames", args.scale)
+    n = len(refs)
+    out = {"haystack": "geonames", "n_refs": n, "build_s": round(sync_s, 2)}
     info = m.device_info()
     out["n_windows"] = info["n_windows"]
     bytes_before = info["device_bytes"]

@@ -100,12 +100,8 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--kernels-only", action="store_true")
     args = ap.parse_args()
-    hay, off = W.bench_haystack("geonames", args.scale)
-    n = len(off) - 1
-    m = RawMap()
-    refs = np.arange(1, n + 1, dtype=np.uint32)
-    m.put_many_packed(hay, off, refs)
-    m.sync_device()
+    m, hay, off, refs, _, _ = W.bench_map("geonames", args.scale)
+    n = len(refs)
     dev = torch.device("cuda", 0)
     rng = np.random.default_rng(31)
     member_sets = [np.sort(rng.choice(refs, 1000, replace=False)) for _ in range(256)]

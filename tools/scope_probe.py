@@ -29,7 +29,7 @@ for p in (ROOT, os.path.join(ROOT, "tools")):
 import torch  # noqa: E402
 
 import workloads as W  # noqa: E402
-from blurrily_amd import RawMap, _native  # noqa: E402
+from blurrily_amd import _native  # noqa: E402
 
 LIMIT = 10
 
@@ -85,12 +85,8 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--kernels-only", action="store_true")
     args = ap.parse_args()
-    hay, off = W.bench_haystack("geonames", args.scale)
-    n = len(off) - 1
-    m = RawMap()
-    refs = np.arange(1, n + 1, dtype=np.uint32)
-    m.put_many_packed(hay, off, refs)
-    m.sync_device()
+    m, hay, off, refs, _, _ = W.bench_map("geonames", args.scale)
+    n = len(refs)
     dev = torch.device("cuda", 0)
     rng = np.random.default_rng(12)
     sizes = sorted({s for s in [10 ** k for k in range(2, 7)] + [30000, 50000] if s < n}) + [n]   # (50 000: near the

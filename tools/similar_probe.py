@@ -13,7 +13,6 @@ Writes the JSON object to --out after every step (a step that runs out of time l
 Usage: python tools/similar_probe.py [--scale 1.0] [--out FILE]"""
 import argparse
 import ctypes as C
-import json
 import os
 import sys
 import time
@@ -26,22 +25,11 @@ for p in (ROOT, os.path.join(ROOT, "tools")):
         sys.path.insert(0, p)
 
 import workloads as W  # noqa: E402
-from blurrily_amd import RawMap, _native  # noqa: E402
+from blurrily_amd import _native  # noqa: E402
 
 ROW_BUDGET = 400_000_000                                     # rows a filled threshold call may return (section 14)
 PARITY = 1000                                                # needles whose workaround rows are re-ranked and compared
 LIMIT = 10
-
-
-def best_of(fn, reps=2):
-    fn()
-    best = None
-    for _ in range(reps):
-        t0 = time.perf_counter()
-        out = fn()
-        dt = time.perf_counter() - t0
-        best = dt if best is None else min(best, dt)
-    return best, out
 
 
 def n_trigrams(s):
@@ -73,31 +61,25 @@ def main():
     res = {"haystack": "configs[2] geonames", "scale": args.scale, "limit": LIMIT}
 
     def dump():
-        with open(args.out, "w") as f:
-            json.dump(res, f, indent=1)
-        print(json.dumps(res), flush=True)
+        W.dump_json(res, args.out)
 
-    hay, off = W.bench_haystack("geonames", args.scale)
-    n = len(off) - 1
-    m = RawMap()
-    t0 = time.perf_counter()
-    m.put_many_packed(hay, off, np.arange(1, n + 1, dtype=np.uint32))
-    m.sync_device()
+    m, hay, off, refs, put_s, sync_s = W.bench_map("geonames", args.scale)
+    n = len(refs)
     res["references"] = n
-    res["build_s"] = round(time.perf_counter() - t0, 2)
+    res["build_s"] = round(put_s + sync_s, 2)
     q, qo = W.bench_needles(hay, off, "geonames", args.scale)
     nq = len(qo) - 1
     res["needles"] = nq
     t0 = time.perf_counter()
     m.find_batch_similar_packed(q[:int(qo[1])], qo[:2], LIMIT, 0)      # the first call builds the per-rank table
     res["first_call_s"] = round(time.perf_counter() - t0, 4)
-    dt, (_, counts) = best_of(lambda: m.find_batch_packed(q, qo, LIMIT))
+    dt, (_, counts) = W.best_of(lambda: m.find_batch_packed(q, qo, LIMIT))
     res["find_batch_limit10"] = {"s": round(dt, 4), "needles_per_s": round(nq / dt),
                                  "rows_per_needle": round(float(counts.mean()), 3)}
     dump()
     got = {}
     for mp in (0, 300, 500, 700):
-        dt, out = best_of(lambda: m.find_batch_similar_packed(q, qo, LIMIT, mp))
+        dt, out = W.best_of(lambda: m.find_batch_similar_packed(q, qo, LIMIT, mp))
         got[mp] = out
         res[f"similar_{mp}"] = {"s": round(dt, 4), "needles_per_s": round(nq / dt),
                                 "rows_per_needle": round(float(out[1].mean()), 3), "last_kernels": m.last_kernels()}
@@ -119,8 +101,8 @@ def main():
             _, code_off, _ = m.get_batch(refs)
             return rows, row_off, refs, np.diff(code_off.astype(np.int64))
 
-        dt, (rows, row_off, refs, rr) = best_of(workaround)
-        dt_new, _ = best_of(lambda: m.find_batch_similar_packed(qk, qok, LIMIT, mp))
+        dt, (rows, row_off, refs, rr) = W.best_of(workaround)
+        dt_new, _ = W.best_of(lambda: m.find_batch_similar_packed(qk, qok, LIMIT, mp))
         R = np.zeros(n + 1, dtype=np.int64)
         R[refs.astype(np.int64)] = rr
         pk = min(PARITY, k)

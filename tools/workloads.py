@@ -179,3 +179,42 @@ def bench_needles(hay, hay_off, name, scale=1.0, rank=0, world=1):
         f_hay, f_off = geonames(max(1000, int(src["n"] * min(1.0, scale * 4))), src["vocab"], src["seed"])
         return queries(f_hay, f_off, n_q, seed)
     return queries(hay, hay_off, n_q, seed)
+
+
+# ---- what the feature probes share (refs_, scope_, scope_each_, above_ and similar_probe.py) ----
+
+def bench_map(name="geonames", scale=1.0):
+    """`name`'s haystack (configs[2]'s by default) in a RawMap, references 1..n, built and synced to the device.
+    Returns (map, packed, offsets, refs uint32[n], seconds in put_many_packed, seconds in sync_device)."""
+    import time
+    from blurrily_amd import RawMap
+    hay, off = bench_haystack(name, scale)
+    refs = np.arange(1, len(off), dtype=np.uint32)
+    m = RawMap()
+    t0 = time.perf_counter()
+    m.put_many_packed(hay, off, refs)
+    t1 = time.perf_counter()
+    m.sync_device()
+    return m, hay, off, refs, t1 - t0, time.perf_counter() - t1
+
+
+def best_of(fn, reps=2):
+    """(the best host-clock seconds of `reps` calls after a warm one, the last call's result)."""
+    import time
+    fn()
+    best = None
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        out = fn()
+        dt = time.perf_counter() - t0
+        best = dt if best is None else min(best, dt)
+    return best, out
+
+
+def dump_json(res, path):
+    """Write `res` to `path` and print it -- after every step of a probe, so that a step that runs out of time leaves
+    the ones before it."""
+    import json
+    with open(path, "w") as f:
+        json.dump(res, f, indent=1)
+    print(json.dumps(res), flush=True)
