@@ -109,6 +109,9 @@ _ENTRIES = {
     "blurrily_storage_find_similar": (C.c_int, [_vp, C.c_char_p, C.c_uint16, C.c_uint32, C.c_void_p, C.c_void_p]),
     "blurrily_storage_find_references_similar": (C.c_int, [_vp, C.c_void_p, C.c_size_t, C.c_uint16, C.c_uint32,
                                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # clusters: connected components of the similarity self-join, one label per reference
+    "blurrily_storage_cluster": (C.c_int, [_vp, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p,
+                                           C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
 }
 EXPORTED_SYMBOLS = tuple(_ENTRIES)
 
@@ -170,3 +173,4 @@ def lib():
 
 
 NO_SCOPE = 0xFFFFFFFF                                  # BLURRILY_NO_SCOPE: a needle of such a batch with no scope
+NO_CLUSTER = 0xFFFFFFFF                                # BLURRILY_NO_CLUSTER: the label of a reference the map does not hold

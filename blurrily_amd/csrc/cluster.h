@@ -1,0 +1,81 @@
+// cluster.h -- launch interface of the clustering kernels (cluster_kernels.hip): connected
+// components of the graph "J(a, b) >= min_permille / 1000" over a list of stored references, J = m / (T + R - m) as in
+// similar.h.  The pairs are never written: a sweep that finds an edge joins its ends in a union-find forest in device
+// memory and forgets it.
+//
+// Nodes are numbered by the caller's references sorted ascending without repeats (node u holds refs[u]; a reference
+// the map does not hold keeps its number and is no node).  A node's POSITION is where the extraction found it:
+// loc.x * kWindowRanks + loc.y, the delta image's windows numbered behind the base image's.  An edge is found from its
+// end at the higher position only, so each is found once.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <cstdint>
+
+#include "device_index.h"
+
+namespace blurrily {
+
+constexpr uint32_t kNoNode = 0xFFFFFFFFu;
+
+// What a call's launches add up and the host reads at the end.
+struct ClusterTotals {
+  unsigned long long edges;      // unions attempted: every edge once
+  uint32_t           clusters;   // roots among the nodes
+  uint32_t           error;      // non-zero: a bounded loop of the union-find ran out (the host answers EIO)
+};
+
+// node_of_pos[position] = u for every node u (kNoNode elsewhere: filled by the caller), parent[u] = u for u < n.
+struct ClusterNodesArgs {
+  const uint2*    loc;           // [n] where each reference was found (RefExtract::loc; x == 0xFFFFFFFF: nowhere)
+  const uint32_t* ntri;          // [n] its trigrams (0: the map does not hold it)
+  uint32_t        n;
+  uint32_t*       node_of_pos;   // [n_pos]
+  uint32_t*       parent;        // [n]
+};
+int launch_cluster_nodes(const ClusterNodesArgs& a, hipStream_t stream);
+
+// One image, needles [q_base, q_base + n) of the node numbering, in the front ends' layout (needle q's T = q_ntri[q]
+// codes at qcodes + qoff[q] + q).  Workgroup b sweeps windows [wr * per, wr * per + per) of needle q_base + b / tasks,
+// wr = b % tasks, tasks = ceil(n_windows / per), as far as they lie in front of the needle's own position.
+struct ClusterSweepArgs {
+  const uint2*    slice_se;
+  const uint16_t* ent;
+  const uint32_t* win_max_tri;
+  const uint32_t* win_min_tri;
+  const uint16_t* ntri_of_rank;
+  uint32_t        n_windows;
+  uint32_t        n_refs;
+  uint32_t        dense_min8;
+  uint32_t        per;           // windows per workgroup
+  uint32_t        win0;          // the image's first window in the positions' numbering
+  const uint16_t* qcodes;
+  const uint64_t* qoff;
+  const uint32_t* q_ntri;
+  const uint2*    loc;
+  uint32_t        q_base;
+  uint32_t        n;
+  uint32_t        n_nodes;       // the numbering's size: no chain of parents is longer
+  uint32_t        min_permille;
+  const uint32_t* node_of_pos;
+  uint32_t*       parent;
+  ClusterTotals*  totals;
+};
+int launch_cluster_sweep(const ClusterSweepArgs& a, hipStream_t stream);
+
+// After the last sweep: labels[i] = refs[root of inv[i]] (inv == nullptr: i itself), kNoNode for a reference that is no
+// node; totals->clusters += roots.
+struct ClusterLabelArgs {
+  const uint32_t* parent;        // [n_nodes]
+  const uint32_t* ntri;          // [n_nodes]
+  const uint32_t* refs;          // [n_nodes] ascending
+  const uint32_t* inv;           // [n] the caller's element i is node inv[i]
+  uint32_t        n_nodes;
+  uint32_t        n;
+  uint32_t*       labels;        // [n]
+  ClusterTotals*  totals;
+};
+int launch_cluster_label(const ClusterLabelArgs& a, hipStream_t stream);
+
+}  // namespace blurrily

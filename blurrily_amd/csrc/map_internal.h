@@ -10,6 +10,7 @@
 //   refs.hip         by reference: refs_extract, ExtractionOnHost, stage_reference_needles, get / find_references entries
 //   scope.hip        scoped find, a scope per needle
 //   above.hip, similar.hip   the threshold and similarity finds (their shared sort: segsort.h)
+//   cluster.hip      connected components of the similarity self-join (similar.hip's per-rank trigram table)
 #pragma once
 #include "../../include/blurrily_storage.h"
 
@@ -29,6 +30,7 @@
 #include "find_kernels.h"
 #include "hip_try.h"
 #include "host_index.h"
+#include "similar.h"
 
 struct trigram_map_t;
 
@@ -333,6 +335,24 @@ struct ExtractionOnHost {
   // (on the device reference i's codes sit at codes + qoff[i] + i, as a needle's do; `all` starts behind the pad)
   const uint16_t* codes_of(size_t i) const { return all.data() + (qoff[i] + i - n); }
 };
+
+// ---- similar.hip ------------------------------------------------------------------------------------------------------
+// An image's per-rank trigram counts (similar.h: SimilarTable), built at the first call that needs them and kept in a
+// registry beside the image.  A call's tables: those it found kept, and those it built and keeps -- or, where the
+// runtime gives no usable buffer ids, frees on the way out.
+struct SimilarTableEntry {
+  const DeviceIndex* ix;
+  const void*        ent;
+  unsigned long long ent_id;
+  int                device;
+  SimilarTable       t;
+  size_t             bytes;
+};
+struct SimilarTables {
+  std::vector<SimilarTableEntry> own;
+  ~SimilarTables();
+};
+int similar_table(DeviceIndex* ix, hipStream_t stream, SimilarTables& call, SimilarTable* out);
 
 }  // namespace detail
 }  // namespace blurrily

@@ -25,14 +25,6 @@ struct SimilarScratch {
 // what it held before.  An image is known by the allocation of its postings, under the runtime's process-wide buffer
 // id -- a rebuilt image (new postings), or a closed map's, no longer matches, and its table is freed at the next
 // similarity call on any map.  Where the runtime gives no ids, a call builds the tables it needs and frees them.
-struct SimilarTableEntry {
-  const DeviceIndex* ix;
-  const void*        ent;
-  unsigned long long ent_id;
-  int                device;
-  SimilarTable       t;
-  size_t             bytes;
-};
 std::mutex                     g_sim_mu;
 std::vector<SimilarTableEntry> g_sim_tables;
 
@@ -53,11 +45,12 @@ void free_table(SimilarTableEntry& e) {
   e.t = SimilarTable();
 }
 
-// A call's tables: those it found kept, and those it built and keeps -- or, without buffer ids, frees on the way out.
-struct SimilarTables {
-  std::vector<SimilarTableEntry> own;
-  ~SimilarTables() { for (auto& e : own) free_table(e); }
-};
+}  // namespace
+
+namespace blurrily {
+namespace detail {
+
+SimilarTables::~SimilarTables() { for (auto& e : own) free_table(e); }
 
 int similar_table(DeviceIndex* ix, hipStream_t stream, SimilarTables& call, SimilarTable* out) {
   std::lock_guard<std::mutex> lock(g_sim_mu);
@@ -95,6 +88,11 @@ int similar_table(DeviceIndex* ix, hipStream_t stream, SimilarTables& call, Simi
   }
   return 0;
 }
+
+}  // namespace detail
+}  // namespace blurrily
+
+namespace {
 
 // ---- the search -----------------------------------------------------------------------------------------------------
 // The sorted segments of a chunk's needles, one per image: sort what is not sorted yet (tiles in LDS, then merge passes

@@ -523,6 +523,34 @@ class RawMap:
                                                                   mp, *ptrs))
         return out
 
+    # -- clusters (no reference counterpart): connected components of the similarity self-join ----------------------
+    def cluster(self, references, min_permille):
+        """Single-linkage clusters of the stored references under "J >= min_permille / 1000" (blurrily_storage_cluster).
+        Returns (labels[n] uint32: the smallest reference of each reference's component, ``_native.NO_CLUSTER`` for
+        one the map does not hold; the number of components; the number of edges, each pair once)."""
+        self._check_open()
+        mp = _permille(min_permille)
+        refs = self._refs(references)
+        n = len(refs)
+        labels = np.zeros(n, dtype=np.uint32)
+        n_clusters, n_edges = C.c_uint32(0), C.c_uint64(0)
+        _check(self._lib.blurrily_storage_cluster(self._h, refs.ctypes.data if n else None, n, mp,
+                                                  labels.ctypes.data if n else None, C.byref(n_clusters),
+                                                  C.byref(n_edges)))
+        return labels, int(n_clusters.value), int(n_edges.value)
+
+    def duplicates(self, references, min_permille):
+        """The clusters of two or more references: a list of lists of references, each ascending, ordered by label."""
+        refs = self._refs(references)
+        labels, _, _ = self.cluster(refs, min_permille)
+        refs, at = np.unique(refs, return_index=True)
+        labels = labels[at]
+        held = labels != _native.NO_CLUSTER
+        refs, labels = refs[held], labels[held]
+        order = np.argsort(labels, kind="stable")               # (refs ascending within a label)
+        _, starts, sizes = np.unique(labels[order], return_index=True, return_counts=True)
+        return [refs[order[s:s + k]].tolist() for s, k in zip(starts.tolist(), sizes.tolist()) if k >= 2]
+
     def sync_device(self):
         self._check_open()
         _check(self._lib.blurrily_storage_sync_device(self._h))

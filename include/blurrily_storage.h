@@ -336,6 +336,29 @@ int blurrily_storage_find_references_similar(trigram_map haystack, const uint32_
                                              uint16_t limit, uint32_t min_permille, trigram_match results,
                                              uint32_t* counts, uint32_t* row_ntri, uint32_t* nb_trigrams);
 
+/* Clusters: connected components of the similarity self-join, computed on the device.  T, R, m
+ * and J = m / (T + R - m) as for the similarity find; the map is read as find reads it.
+ *   Nodes: the distinct references of the list that the map holds (a reference listed twice is one node).
+ *   Edges: unordered pairs {a, b} of distinct nodes with m >= 1 and 1000 * m >= min_permille * (T_a + T_b - m), in 64-bit
+ *          integers (min_permille 0: every pair sharing a trigram).  A reference the map holds but the list does not
+ *          name is no node and joins nothing.
+ *   Label: the smallest reference among the nodes of a node's connected component (itself, for a node without an
+ *          edge).  The labels depend on the map's contents, the list as a set and min_permille only: not on the
+ *          list's order, nor on the order in which the device joins nodes; two runs give identical bytes.
+ * labels[i] belongs to references[i]; a listed reference the map does not hold gets BLURRILY_NO_CLUSTER.  (A held
+ * reference of exactly that value cannot be told from an absent one by its label; blurrily_storage_get can.)
+ * n_clusters (may be NULL): the components; n_edges (may be NULL): the edges as defined above, each pair once -- labels
+ * alone cannot show that an edge was missed where another path joins the same nodes; this count can.  The pairs
+ * themselves never exist, on the device or the host.  n == 0: success, nothing written but the two counts (0).  With
+ * "devices" > 1 the primary device alone serves the call.
+ * 0, or -1 with errno: EINVAL before anything needs a GPU (haystack NULL, min_permille > 1000, references or labels NULL
+ * with n > 0, n above 0xFFFFFFF0 -- the call is not cut into chunks by references: every node must meet every other);
+ * ENODEV without a usable GPU; EIO if a bounded loop of the device's union-find ran out (not seen; the bound is
+ * a multiple of the longest chain there can be). */
+#define BLURRILY_NO_CLUSTER 0xFFFFFFFFu
+int blurrily_storage_cluster(trigram_map haystack, const uint32_t* references, size_t n, uint32_t min_permille,
+                             uint32_t* labels, uint32_t* n_clusters, uint64_t* n_edges);
+
 /* Tokeniser (ext/blurrily/tokeniser.h:34, tokeniser.c:59-119): `output` needs
  * strlen(input)+1 slots; returns the number of distinct codes, ascending. */
 int blurrily_tokeniser_parse_string(const char* input, uint16_t* output);
