@@ -112,6 +112,9 @@ _ENTRIES = {
     # clusters: connected components of the similarity self-join, one label per reference
     "blurrily_storage_cluster": (C.c_int, [_vp, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p,
                                            C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
+    # ... at several floors from one sweep: labels, components and edges per floor
+    "blurrily_storage_cluster_levels": (C.c_int, [_vp, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32, C.c_void_p,
+                                                  C.c_void_p, C.c_void_p]),
 }
 EXPORTED_SYMBOLS = tuple(_ENTRIES)
 
@@ -174,3 +177,4 @@ def lib():
 
 NO_SCOPE = 0xFFFFFFFF                                  # BLURRILY_NO_SCOPE: a needle of such a batch with no scope
 NO_CLUSTER = 0xFFFFFFFF                                # BLURRILY_NO_CLUSTER: the label of a reference the map does not hold
+CLUSTER_MAX_LEVELS = 8                                 # BLURRILY_CLUSTER_MAX_LEVELS: the floors one cluster_levels call takes

@@ -64,6 +64,18 @@ struct ClusterSweepArgs {
 };
 int launch_cluster_sweep(const ClusterSweepArgs& a, hipStream_t stream);
 
+// The same sweep for several floors at once (cluster_levels_kernels.hip): floors[0 .. n_floors)
+// strictly ascending, s.min_permille == floors[0].  Forest k of "J >= floors[k] / 1000" is the n_nodes words at
+// s.parent + k * n_nodes, and s.totals[k] takes level k's edges (an error goes to s.totals[0]).  The node tables and
+// the labels are the kernels above, once per level.
+constexpr uint32_t kClusterMaxLevels = 8;
+struct ClusterLevelsSweepArgs {
+  ClusterSweepArgs s;
+  uint32_t         n_floors;
+  uint32_t         floors[kClusterMaxLevels];
+};
+int launch_cluster_levels_sweep(const ClusterLevelsSweepArgs& a, hipStream_t stream);
+
 // After the last sweep: labels[i] = refs[root of inv[i]] (inv == nullptr: i itself), kNoNode for a reference that is no
 // node; totals->clusters += roots.
 struct ClusterLabelArgs {

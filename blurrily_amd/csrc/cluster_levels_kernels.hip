@@ -1,58 +1,57 @@
-// cluster_kernels.hip -- the clustering kernels (launch code: cluster.hip).
+// cluster_levels_kernels.hip -- the sweep of blurrily_storage_cluster_levels (launch code:
+// cluster_levels.hip): one sweep at the lowest floor, one union-find forest per floor.
 //
-// cluster_nodes_kernel: the node tables (cluster.h).
-// cluster_sweep_kernel: similar_sweep_kernel's all mode (similar_kernels.hip: a window's postings counted into LDS,
-// bytes or 16-bit halves; the floor's bars t and [rlo, rhi]; windows passed over by win_min_tri / win_max_tri; the
-// t - 1 largest dense slices left out and asked through their bitmaps) with another ending: a rank in front of the
-// needle's own position that passes the exact floor test and is a node is united with the needle's node, counted, and
-// forgotten.  A deleted rank is no node (the extraction passes it over), so the tombstones are not read.
-// cluster_label_kernel: every node's root, after the last sweep.
+// cluster_levels_sweep_kernel is cluster_sweep_kernel's sweep (cluster_kernels.hip: the counters, the floor's bars t
+// and [rlo, rhi], the windows passed over, the dense slices left out, each edge found from its end at the higher
+// position) run with p = floors[0] -- an edge at a higher floor is an edge at every lower one, so this sweep meets
+// every level's edges, each with its exact m, T and R in registers -- and with another ending: a rank that passes
+// floor 0's exact test and is a node gets its level lv, the number of floors k with 1000 m >= floors[k] (T + R - m),
+// is counted for levels 0 .. lv - 1 and united with the needle's node in forests 0 .. lv - 1.  The body is a copy of
+// cluster_sweep_kernel's, as that one is of similar_sweep_kernel's all mode, so that the device code of both stays
+// as it was.  The node tables and the labels are cluster_kernels.hip's kernels, launched once per level.
 //
-// The union-find forest, parent[]: hooking always puts the root with the larger number under the smaller, so
-//   (1) parent[x] <= x at all times, and every write lowers a word: a chain of parents strictly descends, has no
-//       cycle and at most n_nodes links;
-//   (2) a component's root is its lowest number, which -- the numbering being the references ascending -- holds its
-//       smallest reference: the label, whatever the order of the unions.
-// Workgroups all over the chip read and write the same words during one sweep.  A CU's L1 is never refreshed by other
-// CUs' stores and the XCDs' L2s are not coherent, so inside the sweep EVERY access to parent[] is an agent-scope
-// atomic (cluster_forest.h's pf_load, pf_cas, pf_min; nothing else touches it).  No access is ordered against any other and none
-// needs to be, because every value ever stored in parent[x] is an ancestor of x (or x itself) and stays one for ever:
-// links only change from x -> p to x -> (an ancestor of p), and a root only stops being one by a compare-and-swap
-// that saw it as a root.  Hence
-//   * a find that follows values read at any time, however old, walks up x's true chain and ends at a number that
-//     was x's root when read; "a and b reach the same number" proves them connected for good, so skipping that union
-//     is right;
-//   * "different roots" may be out of date, which costs a compare-and-swap: it succeeds only if parent[hi] is still hi
-//     at the coherence point (hi still a root: the hook loses nothing and keeps (1)), and otherwise returns the
-//     word's current value, an ancestor of hi, from which the loop goes on;
-//   * path halving stores by atomic min: of two ancestors of x the lower-numbered is the farther, still an ancestor.
-// Nothing waits for another workgroup.  Every loop is bounded by (1): a find takes at most n_nodes steps and every
-// lost compare-and-swap lowers the root in hand; the step budget below is a multiple of that, and running out of it
-// sets ClusterTotals::error instead of spinning.  The kernels before and after the sweeps meet parent[] across launch
-// boundaries and use plain accesses.
+// Per-level state lives in registers: the needle's last known root and a count per level, in arrays of
+// kClusterMaxLevels words that only unrolled loops index, the walk down the forests included, so that nothing goes
+// to scratch.  The counts are a histogram over lv; the workgroup's sum of it is taken from each level upwards
+// at the end, in the first words of the LDS counters, which every harvest leaves zero.
+//
+// Each forest by itself is cluster_kernels.hip's forest, and that file's argument applies to it unchanged: inside
+// the sweep every access to a parent word is an agent-scope relaxed atomic (cluster_forest.h), hooks put the higher
+// number under the lower, path halving stores by atomic min, and a step budget sets the error word when it runs out.
+//
+// The unions go from the top level down and stop early: a lane with an edge of level lv unites its ends in forest
+// lv - 1 first, then lv - 2, ..., and stops at the first forest in which it finds both ends under one root already.
+// That the forests below then hold the ends together too, once the sweeps are done:
+//   * a hook in forest k is only ever made by a lane whose edge passed floor k;
+//   * a lane that has hooked in forest k goes on to forest k - 1, where it unites the same ends or finds them
+//     together -- so when its launch ends, the ends of every edge behind a hook of forest k are connected in forest
+//     k - 1;
+//   * two nodes under one root in forest k are joined by a path of such hooked edges, hence connected in forest
+//     k - 1 when the launches that made the hooks have ended; by induction downwards, in every forest below k.
+// So "one root in forest k" lets the lane leave forests k - 1 .. 0 to the lanes that built that path (or to those
+// that built theirs), and the label kernel, which runs only after the last sweep, sees every forest complete.  A
+// lane whose budget runs out stops too, and the call fails.  The early stop does not touch the edge counts: they come
+// from lv alone.  BLURRILY_LEVELS_EARLY_STOP=0 builds the plain form (every forest 0 .. lv - 1 visited), which
+// DESIGN.md section 18 measures against.
 #include "cluster.h"
 #include "cluster_forest.h"
 #include "find_kernels.h"
 #include "hip_try.h"
 
+#ifndef BLURRILY_LEVELS_EARLY_STOP
+#define BLURRILY_LEVELS_EARLY_STOP 1
+#endif
+
 namespace blurrily {
 
 namespace {
 
-__global__ void cluster_nodes_kernel(const ClusterNodesArgs A) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= A.n) return;
-  A.parent[i] = i;
-  if (A.ntri[i] == 0) return;
-  const uint2 loc = A.loc[i];
-  A.node_of_pos[size_t(loc.x) * kWindowRanks + loc.y] = i;
-}
-
-__global__ __launch_bounds__(kCluThreads) void cluster_sweep_kernel(const ClusterSweepArgs a) {
+__global__ __launch_bounds__(kCluThreads) void cluster_levels_sweep_kernel(const ClusterLevelsSweepArgs A) {
+  const ClusterSweepArgs& a = A.s;
   __shared__ uint32_t cnt[kCluWords];
   __shared__ uint32_t left[(kNumCodes + 31) / 32];            // codes left out of this window's count
   __shared__ uint32_t d_len[kCluMaxDense], d_at[kCluMaxDense], d_code[kCluMaxDense], leave_at[kCluMaxDense];
-  __shared__ uint32_t s_nd, s_any, s_edges, s_err;
+  __shared__ uint32_t s_nd, s_any, s_err;
   const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
   const uint32_t tasks = (a.n_windows + a.per - 1u) / a.per;
   const uint32_t qi = blockIdx.x / tasks, wr = blockIdx.x % tasks;
@@ -66,7 +65,7 @@ __global__ __launch_bounds__(kCluThreads) void cluster_sweep_kernel(const Cluste
   // the windows in front of the needle's position: up to its own, of which the ranks below its own count
   const uint32_t w_begin = wr * a.per, w_end = min(min(a.n_windows, (wr + 1u) * a.per), qloc.x - a.win0 + 1u);
   if (w_begin >= w_end) return;
-  const uint32_t p = a.min_permille;
+  const uint32_t p = A.floors[0];                             // the sweep is the lowest floor's: it meets every level's edges
   const uint16_t* codes = a.qcodes + a.qoff[q] + uint64_t(q);
   const bool wide = T > 255u;                                 // byte counters hold at most 255 matches
   // the floor's bars: m >= ceil(p T / 1000), ceil(p T / 1000) <= R <= floor(1000 T / p)
@@ -75,11 +74,13 @@ __global__ __launch_bounds__(kCluThreads) void cluster_sweep_kernel(const Cluste
   const uint32_t rhi = p ? uint32_t(min<uint64_t>(1000ull * T / p, 0xFFFFFFFFull)) : 0xFFFFFFFFu;
   for (uint32_t i = tid; i < kCluWords; i += kCluThreads) cnt[i] = 0;
   for (uint32_t i = tid; i < (kNumCodes + 31) / 32; i += kCluThreads) left[i] = 0;
-  if (tid == 0) { s_edges = 0; s_err = 0; }
+  if (tid == 0) s_err = 0;
   __syncthreads();
 
-  uint32_t root = q;                                          // the needle's root as far as this lane knows
-  uint32_t mine = 0;                                          // edges this lane found
+  uint32_t root[kClusterMaxLevels];                           // the needle's root in each forest as far as this lane knows
+  uint32_t hist[kClusterMaxLevels];                           // edges this lane found, by level: hist[k] of them have lv == k + 1
+#pragma unroll
+  for (uint32_t k = 0; k < kClusterMaxLevels; ++k) { root[k] = q; hist[k] = 0; }
   bool ok = true;
   for (uint32_t w = w_begin; w < w_end; ++w) {
     const uint32_t wmin = a.win_min_tri[w], wmax = a.win_max_tri[w];
@@ -163,10 +164,22 @@ __global__ __launch_bounds__(kCluThreads) void cluster_sweep_kernel(const Cluste
           if (1000ull * m < uint64_t(p) * (uint64_t(T) + R - m)) continue;   // the floor, exactly
           const uint32_t other = a.node_of_pos[pos0 + r];
           if (other == kNoNode) continue;                     // held but not listed (or deleted): no node, no bridge
-          ++mine;
-          if (ok) {
+          // the edge's level: the floors it passes are a prefix, the floors ascending
+          uint32_t lv = 1;
+#pragma unroll
+          for (uint32_t k = 1; k < kClusterMaxLevels; ++k)
+            lv += k < A.n_floors && 1000ull * m >= uint64_t(A.floors[k]) * (uint64_t(T) + R - m);
+#pragma unroll
+          for (uint32_t k = 0; k < kClusterMaxLevels; ++k) hist[k] += lv == k + 1u;
+          bool go = ok;                                       // forests lv - 1 down to 0
+#pragma unroll
+          for (uint32_t i = 0; i < kClusterMaxLevels; ++i) {
+            const uint32_t k = kClusterMaxLevels - 1u - i;
+            if (!go || k >= lv) continue;
             uint64_t budget = 4ull * a.n_nodes + 64u;
-            ok = pf_unite(a.parent, &root, other, &budget);
+            bool hooked;
+            ok = pf_unite(a.parent + size_t(k) * a.n_nodes, &root[k], other, &budget, &hooked);
+            go = ok && (hooked || !BLURRILY_LEVELS_EARLY_STOP);   // (together here: together in every forest below, see above)
           }
         }
       }
@@ -174,66 +187,30 @@ __global__ __launch_bounds__(kCluThreads) void cluster_sweep_kernel(const Cluste
     }
     if (tid < nd) atomicAnd(&left[d_code[tid] >> 5], ~(1u << (d_code[tid] & 31u)));   // (cleared for the next window)
   }
-  if (mine) atomicAdd(&s_edges, mine);
+  // the workgroup's histogram in the first words of the counters (every harvest leaves them zero), summed from each
+  // level upwards: an edge of level lv counts for levels 0 .. lv - 1
+  __syncthreads();
+#pragma unroll
+  for (uint32_t k = 0; k < kClusterMaxLevels; ++k)
+    if (hist[k]) atomicAdd(&cnt[k], hist[k]);
   if (!ok) s_err = 1;
   __syncthreads();
-  if (tid == 0) {
-    if (s_edges) atomicAdd(&a.totals->edges, static_cast<unsigned long long>(s_edges));
-    if (s_err) atomicOr(&a.totals->error, 1u);
+  if (tid < A.n_floors) {
+    uint32_t edges = 0;
+    for (uint32_t k = tid; k < kClusterMaxLevels; ++k) edges += cnt[k];
+    if (edges) atomicAdd(&a.totals[tid].edges, static_cast<unsigned long long>(edges));
   }
-}
-
-// (one launch: thread i < n_nodes counts node i if it is a root, thread i < n labels the caller's element i)
-__global__ __launch_bounds__(256) void cluster_label_kernel(const ClusterLabelArgs A) {
-  __shared__ uint32_t s_roots, s_err;
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (threadIdx.x == 0) { s_roots = 0; s_err = 0; }
-  __syncthreads();
-  if (i < A.n_nodes && A.ntri[i] && A.parent[i] == i) atomicAdd(&s_roots, 1u);
-  if (i < A.n) {
-    uint32_t v = A.inv ? A.inv[i] : i, label = kNoNode;
-    if (A.ntri[v]) {
-      uint32_t steps = 0;
-      for (uint32_t up = A.parent[v]; up < v; up = A.parent[v]) {   // (at most n_nodes links: the chain descends)
-        v = up;
-        if (++steps > A.n_nodes) { s_err = 1; break; }
-      }
-      label = A.refs[v];
-    }
-    A.labels[i] = label;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    if (s_roots) atomicAdd(&A.totals->clusters, s_roots);
-    if (s_err) atomicOr(&A.totals->error, 1u);
-  }
+  if (tid == 0 && s_err) atomicOr(&a.totals[0].error, 1u);
 }
 
 }  // namespace
 
-int launch_cluster_nodes(const ClusterNodesArgs& a, hipStream_t stream) {
-  if (a.n == 0) return 0;
-  note_launch("cluster_nodes_kernel");
-  hipLaunchKernelGGL(cluster_nodes_kernel, dim3((a.n + 255u) / 256u), dim3(256), 0, stream, a);
-  BLURRILY_HIP_TRY(hipGetLastError());
-  return 0;
-}
-
-int launch_cluster_sweep(const ClusterSweepArgs& a, hipStream_t stream) {
-  if (a.n == 0 || a.n_windows == 0) return 0;
-  const uint64_t grid = uint64_t(a.n) * ((a.n_windows + a.per - 1u) / a.per);
-  if (grid > 0x7FFFFFFFull) { errno = EINVAL; return -1; }
-  note_launch("cluster_sweep_kernel");
-  hipLaunchKernelGGL(cluster_sweep_kernel, dim3(uint32_t(grid)), dim3(kCluThreads), 0, stream, a);
-  BLURRILY_HIP_TRY(hipGetLastError());
-  return 0;
-}
-
-int launch_cluster_label(const ClusterLabelArgs& a, hipStream_t stream) {
-  const uint32_t n = a.n > a.n_nodes ? a.n : a.n_nodes;
-  if (n == 0) return 0;
-  note_launch("cluster_label_kernel");
-  hipLaunchKernelGGL(cluster_label_kernel, dim3((n + 255u) / 256u), dim3(256), 0, stream, a);
+int launch_cluster_levels_sweep(const ClusterLevelsSweepArgs& a, hipStream_t stream) {
+  if (a.s.n == 0 || a.s.n_windows == 0) return 0;
+  const uint64_t grid = uint64_t(a.s.n) * ((a.s.n_windows + a.s.per - 1u) / a.s.per);
+  if (grid > 0x7FFFFFFFull || a.n_floors == 0 || a.n_floors > kClusterMaxLevels) { errno = EINVAL; return -1; }
+  note_launch("cluster_levels_sweep_kernel");
+  hipLaunchKernelGGL(cluster_levels_sweep_kernel, dim3(uint32_t(grid)), dim3(kCluThreads), 0, stream, a);
   BLURRILY_HIP_TRY(hipGetLastError());
   return 0;
 }

@@ -58,6 +58,16 @@ def _permille(value):
     return mp
 
 
+def _floors(floors):
+    """The floors of a cluster_levels call: 1 .. CLUSTER_MAX_LEVELS per-mille values, strictly ascending."""
+    fl = [_permille(f) for f in floors]
+    if not 1 <= len(fl) <= _native.CLUSTER_MAX_LEVELS:
+        raise ValueError(f"{len(fl)} floors: one call takes 1 to {_native.CLUSTER_MAX_LEVELS}")
+    if any(a >= b for a, b in zip(fl, fl[1:])):
+        raise ValueError(f"floors {fl!r} not strictly ascending")
+    return np.array(fl, dtype=np.uint32)
+
+
 def _find_limit(limit):
     """The single finds' limit (map_ext.c:131-146), as the C function takes it."""
     limit = int(limit)
@@ -538,6 +548,35 @@ class RawMap:
                                                   labels.ctypes.data if n else None, C.byref(n_clusters),
                                                   C.byref(n_edges)))
         return labels, int(n_clusters.value), int(n_edges.value)
+
+    def cluster_levels(self, references, floors):
+        """``cluster`` at several floors (strictly ascending, at most ``_native.CLUSTER_MAX_LEVELS``) from one sweep of
+        the device (blurrily_storage_cluster_levels).  Returns (labels[K, n] uint32, n_clusters[K] int64, n_edges[K]
+        int64): row k is what ``cluster(references, floors[k])`` returns."""
+        self._check_open()
+        fl = _floors(floors)
+        refs = self._refs(references)
+        n, k = len(refs), len(fl)
+        labels = np.zeros((k, n), dtype=np.uint32)
+        n_clusters, n_edges = np.zeros(k, dtype=np.uint32), np.zeros(k, dtype=np.uint64)
+        _check(self._lib.blurrily_storage_cluster_levels(self._h, refs.ctypes.data if n else None, n, fl.ctypes.data, k,
+                                                         labels.ctypes.data if n else None, n_clusters.ctypes.data,
+                                                         n_edges.ctypes.data))
+        return labels, n_clusters.astype(np.int64), n_edges.astype(np.int64)
+
+    def cluster_profile(self, references, floors):
+        """What a caller picks a floor by: per floor ``{floor, n_clusters, n_edges, largest, singletons}`` -- the
+        components, the edges, the nodes of the largest component and the components of one node -- from one
+        ``cluster_levels`` call and numpy over its labels."""
+        floors = list(floors)
+        refs = np.unique(self._refs(references))               # (a reference listed twice is one node)
+        labels, n_clusters, n_edges = self.cluster_levels(refs, floors)
+        profile = []
+        for k, floor in enumerate(floors):
+            _, sizes = np.unique(labels[k][labels[k] != _native.NO_CLUSTER], return_counts=True)
+            profile.append({"floor": int(floor), "n_clusters": int(n_clusters[k]), "n_edges": int(n_edges[k]),
+                            "largest": int(sizes.max()) if len(sizes) else 0, "singletons": int((sizes == 1).sum())})
+        return profile
 
     def duplicates(self, references, min_permille):
         """The clusters of two or more references: a list of lists of references, each ascending, ordered by label."""

@@ -359,6 +359,23 @@ int blurrily_storage_find_references_similar(trigram_map haystack, const uint32_
 int blurrily_storage_cluster(trigram_map haystack, const uint32_t* references, size_t n, uint32_t min_permille,
                              uint32_t* labels, uint32_t* n_clusters, uint64_t* n_edges);
 
+/* Cluster levels: the clusters above at several floors from one sweep -- the single-linkage
+ * dendrogram cut at up to BLURRILY_CLUSTER_MAX_LEVELS heights, for a caller who picks the floor afterwards.  floors[0 ..
+ * n_floors) are per mille, strictly ascending, each <= 1000; the device sweeps once, at floors[0], and keeps a forest
+ * per floor.  Nodes, edges, labels, BLURRILY_NO_CLUSTER, repeats, absent references, unlisted bridges, deletes and
+ * pending puts: exactly as for blurrily_storage_cluster.  Level k's outputs -- labels[k * n .. k * n + n), n_clusters[k]
+ * and n_edges[k] (either array may be NULL) -- are byte for byte what blurrily_storage_cluster returns for the same
+ * map, the same list and floors[k].  Levels nest: two references with one label at floors[k] have one label at every
+ * lower floor.  n == 0: success, nothing written but the counts given (0 each).  With "devices" > 1 the primary device
+ * alone serves the call.
+ * 0, or -1 with errno: EINVAL before anything needs a GPU and with nothing written (haystack or floors NULL, n_floors 0
+ * or above the cap, a floor above 1000, floors not strictly ascending, references or labels NULL with n > 0, n above
+ * 0xFFFFFFF0); ENODEV without a usable GPU; EIO if a bounded loop of the device's union-find ran out. */
+#define BLURRILY_CLUSTER_MAX_LEVELS 8
+int blurrily_storage_cluster_levels(trigram_map haystack, const uint32_t* references, size_t n,
+                                    const uint32_t* floors, uint32_t n_floors, uint32_t* labels, uint32_t* n_clusters,
+                                    uint64_t* n_edges);
+
 /* Tokeniser (ext/blurrily/tokeniser.h:34, tokeniser.c:59-119): `output` needs
  * strlen(input)+1 slots; returns the number of distinct codes, ascending. */
 int blurrily_tokeniser_parse_string(const char* input, uint16_t* output);
