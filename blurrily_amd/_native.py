@@ -115,6 +115,10 @@ _ENTRIES = {
     # ... at several floors from one sweep: labels, components and edges per floor
     "blurrily_storage_cluster_levels": (C.c_int, [_vp, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32, C.c_void_p,
                                                   C.c_void_p, C.c_void_p]),
+    # ... with each node's degree, each component's centre and whether a node shares an edge with its centre
+    "blurrily_storage_cluster_centres": (C.c_int, [_vp, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p,
+                                                   C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32),
+                                                   C.POINTER(C.c_uint64)]),
 }
 EXPORTED_SYMBOLS = tuple(_ENTRIES)
 

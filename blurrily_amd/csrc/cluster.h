@@ -90,4 +90,36 @@ struct ClusterLabelArgs {
 };
 int launch_cluster_label(const ClusterLabelArgs& a, hipStream_t stream);
 
+// Cluster centres (cluster_centres_kernels.hip): the same sweep once more, keeping per node what
+// the labels forget.  Count mode (mark == false) unites as cluster_sweep_kernel does and adds every edge to the degree
+// of both its ends; mark mode, after launch_cluster_centres, sets attached[u] for every node u that shares an edge
+// with its component's centre and does nothing else.
+struct ClusterCentresSweepArgs {
+  ClusterSweepArgs s;
+  uint32_t*        degree;       // [n_nodes] zeroed by the caller; count mode adds, mark mode reads
+  const uint32_t*  centre_of;    // [n_nodes] mark mode: the number of each node's centre
+  uint32_t*        attached;     // [n_nodes] mark mode: 1 is stored, nothing is read
+};
+int launch_cluster_centres_sweep(const ClusterCentresSweepArgs& a, bool mark, hipStream_t stream);
+
+// After the labels (parent[] final): best[root] = max over the component of degree << 32 | (0xFFFFFFFF - number), then,
+// across a launch boundary, centre_of[u] and attached[u] = (u is its centre) for every number (a number that is no node:
+// kNoNode and 0), and the caller's elements: centres[i] = refs[centre of inv[i]] (kNoNode for no node), degrees[i].
+struct ClusterCentresArgs {
+  const uint32_t*     parent;    // [n_nodes]
+  const uint32_t*     ntri;      // [n_nodes]
+  const uint32_t*     refs;      // [n_nodes] ascending
+  const uint32_t*     inv;       // [n] (nullptr: element i is node i)
+  const uint32_t*     degree;    // [n_nodes]
+  uint32_t            n_nodes;
+  uint32_t            n;
+  unsigned long long* best;      // [n_nodes] zeroed by the caller
+  uint32_t*           centre_of; // [n_nodes]
+  uint32_t*           attached;  // [n_nodes]
+  uint32_t*           centres;   // [n]
+  uint32_t*           degrees;   // [n]
+  ClusterTotals*      totals;
+};
+int launch_cluster_centres(const ClusterCentresArgs& a, hipStream_t stream);
+
 }  // namespace blurrily

@@ -578,6 +578,41 @@ class RawMap:
                             "largest": int(sizes.max()) if len(sizes) else 0, "singletons": int((sizes == 1).sum())})
         return profile
 
+    def cluster_centres(self, references, min_permille, attached=True):
+        """``cluster`` with what tells a tight group from a chain (blurrily_storage_cluster_centres).  Returns (labels[n],
+        degrees[n] uint32: each reference's edges; centres[n] uint32: the reference with the most edges in its
+        component, the smallest among equals, ``_native.NO_CLUSTER`` for one the map does not hold; attached[n] uint8:
+        1 for a centre and for a reference that shares an edge with its centre -- None with ``attached=False``, which
+        spares the device its second sweep; the number of components; the number of edges)."""
+        self._check_open()
+        mp = _permille(min_permille)
+        refs = self._refs(references)
+        n = len(refs)
+        labels, degrees, centres = (np.zeros(n, dtype=np.uint32) for _ in range(3))
+        att = np.zeros(n, dtype=np.uint8) if attached else None
+        n_clusters, n_edges = C.c_uint32(0), C.c_uint64(0)
+        ptr = lambda a: a.ctypes.data if n else None
+        _check(self._lib.blurrily_storage_cluster_centres(self._h, ptr(refs), n, mp, ptr(labels), ptr(degrees),
+                                                          ptr(centres), ptr(att) if attached else None,
+                                                          C.byref(n_clusters), C.byref(n_edges)))
+        return labels, degrees, centres, att, int(n_clusters.value), int(n_edges.value)
+
+    def cluster_shapes(self, references, min_permille):
+        """The components of two or more references, ordered by label: ``{label, size, edges, centre, attached, star}``
+        each -- its nodes, its edges, its centre, how many of its nodes are the centre or share an edge with it, and
+        whether all do (a star: every member is directly similar to the centre; otherwise a chain to look at again).
+        Numpy over one ``cluster_centres`` call."""
+        refs = np.unique(self._refs(references))               # (a reference listed twice is one node)
+        labels, degrees, centres, att, _, _ = self.cluster_centres(refs, min_permille)
+        held = labels != _native.NO_CLUSTER
+        labels, degrees, centres, att = labels[held], degrees[held], centres[held], att[held]
+        uniq, first, which, sizes = np.unique(labels, return_index=True, return_inverse=True, return_counts=True)
+        edges = np.bincount(which, weights=degrees.astype(np.float64), minlength=len(uniq)).astype(np.int64) // 2
+        marked = np.bincount(which, weights=att.astype(np.float64), minlength=len(uniq)).astype(np.int64)
+        return [{"label": int(uniq[k]), "size": int(sizes[k]), "edges": int(edges[k]), "centre": int(centres[first[k]]),
+                 "attached": int(marked[k]), "star": bool(marked[k] == sizes[k])}
+                for k in np.nonzero(sizes >= 2)[0].tolist()]
+
     def duplicates(self, references, min_permille):
         """The clusters of two or more references: a list of lists of references, each ascending, ordered by label."""
         refs = self._refs(references)

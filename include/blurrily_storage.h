@@ -376,6 +376,28 @@ int blurrily_storage_cluster_levels(trigram_map haystack, const uint32_t* refere
                                     const uint32_t* floors, uint32_t n_floors, uint32_t* labels, uint32_t* n_clusters,
                                     uint64_t* n_edges);
 
+/* Cluster centres: the clusters above with what a deduplication job needs to pick a survivor and to judge a cluster
+ * (DESIGN.md section 19).  Nodes, edges, labels, BLURRILY_NO_CLUSTER, repeats, absent references, unlisted bridges,
+ * deletes, pending puts and min_permille: exactly as for blurrily_storage_cluster, and labels, n_clusters and n_edges
+ * are byte for byte what that call returns for the same map, list and floor.
+ *   degrees[i]:  the edges at references[i]'s node (0 for a reference that is no node); over the nodes they sum to
+ *                2 * n_edges.
+ *   centres[i]:  the reference of the node with the highest degree in references[i]'s component, the smallest
+ *                reference among equal degrees (a node without an edge: itself); BLURRILY_NO_CLUSTER for no node.
+ *   attached[i]: 1 if references[i]'s node is its component's centre or shares an edge with it, else 0 (no node: 0).  A
+ *                component whose members are all attached is a star around its centre; an unattached member hangs
+ *                on a chain.
+ * All three depend on the map's contents, the list as a set and min_permille only; repeated elements get equal values.
+ * degrees, centres, attached, n_clusters and n_edges may each be NULL.  attached costs a second sweep of the device,
+ * which is not run when it is NULL.  n == 0: success, nothing written but the two counts (0).  With "devices" > 1 the
+ * primary device alone serves the call.
+ * 0, or -1 with errno: EINVAL before anything needs a GPU and with nothing written (haystack NULL, min_permille > 1000,
+ * references or labels NULL with n > 0, n above 0xFFFFFFF0); ENODEV without a usable GPU; EIO if a bounded loop of the
+ * device ran out. */
+int blurrily_storage_cluster_centres(trigram_map haystack, const uint32_t* references, size_t n, uint32_t min_permille,
+                                     uint32_t* labels, uint32_t* degrees, uint32_t* centres, uint8_t* attached,
+                                     uint32_t* n_clusters, uint64_t* n_edges);
+
 /* Tokeniser (ext/blurrily/tokeniser.h:34, tokeniser.c:59-119): `output` needs
  * strlen(input)+1 slots; returns the number of distinct codes, ascending. */
 int blurrily_tokeniser_parse_string(const char* input, uint16_t* output);
