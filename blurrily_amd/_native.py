@@ -119,6 +119,10 @@ _ENTRIES = {
     "blurrily_storage_cluster_centres": (C.c_int, [_vp, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p,
                                                    C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32),
                                                    C.POINTER(C.c_uint64)]),
+    # density-based clusters over the same edges: cores, borders and noise
+    "blurrily_storage_cluster_cores": (C.c_int, [_vp, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64),
+                                                 C.POINTER(C.c_uint64)]),
 }
 EXPORTED_SYMBOLS = tuple(_ENTRIES)
 
@@ -181,4 +185,5 @@ def lib():
 
 NO_SCOPE = 0xFFFFFFFF                                  # BLURRILY_NO_SCOPE: a needle of such a batch with no scope
 NO_CLUSTER = 0xFFFFFFFF                                # BLURRILY_NO_CLUSTER: the label of a reference the map does not hold
+KIND_NONE, KIND_NOISE, KIND_BORDER, KIND_CORE = 0, 1, 2, 3   # BLURRILY_KIND_*: the kinds of a cluster_cores call
 CLUSTER_MAX_LEVELS = 8                                 # BLURRILY_CLUSTER_MAX_LEVELS: the floors one cluster_levels call takes

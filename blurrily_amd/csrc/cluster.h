@@ -122,4 +122,46 @@ struct ClusterCentresArgs {
 };
 int launch_cluster_centres(const ClusterCentresArgs& a, hipStream_t stream);
 
+// Cluster cores (cluster_cores_kernels.hip): density-based clusters over the same edges.  A node
+// is core when degree >= min_degree; only an edge between two cores unites.  Two sweeps: degree mode (unite == false)
+// adds every edge to the degree of both its ends and to totals->t.edges and touches no parent; unite mode, across a
+// launch boundary, reads the final degrees, unites the core-core edges (counted in ClusterCoresTotals::core_edges) and
+// raises anchor[b] for a non-core b with a core neighbour a to degree[a] << 32 | (0xFFFFFFFF - a): the highest degree
+// wins, the lowest number among equals.  0 stays in anchor[b] when no core touches b (a key has a degree >= 1 on top).
+struct ClusterCoresTotals {
+  ClusterTotals      t;          // edges from degree mode, clusters from the labels, error from either
+  unsigned long long core_edges; // unions attempted in unite mode: every edge between two cores once
+};
+struct ClusterCoresSweepArgs {
+  ClusterSweepArgs    s;         // (s.totals is not used: the sweep adds to `totals` below)
+  uint32_t*           degree;    // [n_nodes] zeroed by the caller; degree mode adds, unite mode reads
+  unsigned long long* anchor;    // [n_nodes] zeroed by the caller; unite mode raises
+  uint32_t            min_degree;
+  ClusterCoresTotals* totals;
+};
+int launch_cluster_cores_sweep(const ClusterCoresSweepArgs& a, bool unite, hipStream_t stream);
+
+// The kinds of blurrily_storage_cluster_cores' `kinds` (BLURRILY_KIND_* of include/blurrily_storage.h).
+constexpr uint8_t kKindNone = 0, kKindNoise = 1, kKindBorder = 2, kKindCore = 3;
+
+// After the last sweep (parent[], degree[] and anchor[] final): totals->t.clusters += the cores that are their own
+// root, and per element i of the caller's, for its number v = inv[i]: no node -> kNoNode, 0, kKindNone; a core ->
+// refs[root of v]; anchor[v] != 0 -> refs[root of 0xFFFFFFFF - low32(anchor[v])], a border; else refs[v], noise.
+struct ClusterCoresLabelArgs {
+  const uint32_t*           parent;   // [n_nodes]
+  const uint32_t*           ntri;     // [n_nodes]
+  const uint32_t*           refs;     // [n_nodes] ascending
+  const uint32_t*           inv;      // [n] (nullptr: element i is node i)
+  const uint32_t*           degree;   // [n_nodes]
+  const unsigned long long* anchor;   // [n_nodes]
+  uint32_t                  n_nodes;
+  uint32_t                  n;
+  uint32_t                  min_degree;
+  uint32_t*                 labels;   // [n]
+  uint32_t*                 degrees;  // [n]
+  uint8_t*                  kinds;    // [n]
+  ClusterCoresTotals*       totals;
+};
+int launch_cluster_cores_label(const ClusterCoresLabelArgs& a, hipStream_t stream);
+
 }  // namespace blurrily

@@ -625,6 +625,38 @@ class RawMap:
         _, starts, sizes = np.unique(labels[order], return_index=True, return_counts=True)
         return [refs[order[s:s + k]].tolist() for s, k in zip(starts.tolist(), sizes.tolist()) if k >= 2]
 
+    def cluster_cores(self, references, min_permille, min_degree):
+        """Density-based clusters over ``cluster``'s edges (blurrily_storage_cluster_cores): a reference with at least
+        ``min_degree`` edges is a core, only edges between cores unite, a reference that is no core joins the cluster
+        of its core neighbour with the most edges (the smallest among equals) as a border, or is noise.  Returns
+        (labels[n] uint32: the smallest core of the cluster, a noise reference itself, ``_native.NO_CLUSTER`` for one
+        the map does not hold; degrees[n] uint32; kinds[n] uint8: ``_native.KIND_NONE``, ``KIND_NOISE``,
+        ``KIND_BORDER``, ``KIND_CORE``; the number of clusters; the number of edges; the edges between cores)."""
+        self._check_open()
+        mp = _permille(min_permille)
+        md = _u32(min_degree, "min_degree")
+        refs = self._refs(references)
+        n = len(refs)
+        labels, degrees = (np.zeros(n, dtype=np.uint32) for _ in range(2))
+        kinds = np.zeros(n, dtype=np.uint8)
+        n_clusters, n_edges, n_core_edges = C.c_uint32(0), C.c_uint64(0), C.c_uint64(0)
+        ptr = lambda a: a.ctypes.data if n else None
+        _check(self._lib.blurrily_storage_cluster_cores(self._h, ptr(refs), n, mp, md, ptr(labels), ptr(degrees),
+                                                        ptr(kinds), C.byref(n_clusters), C.byref(n_edges),
+                                                        C.byref(n_core_edges)))
+        return labels, degrees, kinds, int(n_clusters.value), int(n_edges.value), int(n_core_edges.value)
+
+    def dense_duplicates(self, references, min_permille, min_degree):
+        """The clusters of ``cluster_cores``: a list of lists of references, cores and borders, each ascending,
+        ordered by label; noise is left out.  Numpy over one ``cluster_cores`` call."""
+        refs = np.unique(self._refs(references))               # (a reference listed twice is one node)
+        labels, _, kinds, _, _, _ = self.cluster_cores(refs, min_permille, min_degree)
+        member = kinds >= _native.KIND_BORDER
+        refs, labels = refs[member], labels[member]
+        order = np.argsort(labels, kind="stable")               # (refs ascending within a label)
+        _, starts, sizes = np.unique(labels[order], return_index=True, return_counts=True)
+        return [refs[order[s:s + k]].tolist() for s, k in zip(starts.tolist(), sizes.tolist())]
+
     def sync_device(self):
         self._check_open()
         _check(self._lib.blurrily_storage_sync_device(self._h))

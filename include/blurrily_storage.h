@@ -398,6 +398,38 @@ int blurrily_storage_cluster_centres(trigram_map haystack, const uint32_t* refer
                                      uint32_t* labels, uint32_t* degrees, uint32_t* centres, uint8_t* attached,
                                      uint32_t* n_clusters, uint64_t* n_edges);
 
+/* Cluster cores: density-based clusters (DBSCAN) over the edges above, which a chain of sparsely connected nodes cannot
+ * bridge.  Nodes, edges, degrees, BLURRILY_NO_CLUSTER, repeats, absent references, unlisted
+ * bridges, deletes, pending puts and min_permille: exactly as for blurrily_storage_cluster_centres.
+ *   Core:    a node with degree >= min_degree.
+ *   Cluster: a connected component of the graph that keeps only the edges whose both ends are cores; its label is the
+ *            smallest reference among its cores.
+ *   Border:  a node that is no core and has a core neighbour.  It takes the label of its anchor's cluster, the anchor
+ *            being its core neighbour of the highest degree, the smallest reference among equals.  A border joins one
+ *            cluster and never merges two.
+ *   Noise:   a node that is neither.  Its label is its own reference, so the labels partition the nodes as
+ *            blurrily_storage_cluster's do; its kind tells it from a cluster.
+ *   kinds[i]:     BLURRILY_KIND_NONE for a reference that is no node (label BLURRILY_NO_CLUSTER, degree 0), else
+ *                 BLURRILY_KIND_NOISE, BLURRILY_KIND_BORDER or BLURRILY_KIND_CORE.
+ *   n_clusters:   the components of cores.  n_edges: every edge, byte for byte blurrily_storage_cluster's.
+ *   n_core_edges: the edges with both ends core, each once -- labels cannot show that the second sweep missed an edge
+ *                 where another path joins the same cores; this count can.
+ * All outputs depend on the map's contents, the list as a set, min_permille and min_degree only.  min_degree 0: every
+ * node is a core, and labels, n_clusters and n_edges are blurrily_storage_cluster's, n_core_edges == n_edges.
+ * min_degree 1: the nodes with an edge keep blurrily_storage_cluster's labels, its singletons are noise.
+ * degrees, kinds, n_clusters, n_edges and n_core_edges may each be NULL.  The device sweeps twice.  n == 0: success,
+ * nothing written but the three counts (0).  With "devices" > 1 the primary device alone serves the call.
+ * 0, or -1 with errno: EINVAL before anything needs a GPU and with nothing written (haystack NULL, min_permille > 1000,
+ * references or labels NULL with n > 0, n above 0xFFFFFFF0); ENODEV without a usable GPU; EIO if a bounded loop of the
+ * device ran out. */
+#define BLURRILY_KIND_NONE   0
+#define BLURRILY_KIND_NOISE  1
+#define BLURRILY_KIND_BORDER 2
+#define BLURRILY_KIND_CORE   3
+int blurrily_storage_cluster_cores(trigram_map haystack, const uint32_t* references, size_t n, uint32_t min_permille,
+                                   uint32_t min_degree, uint32_t* labels, uint32_t* degrees, uint8_t* kinds,
+                                   uint32_t* n_clusters, uint64_t* n_edges, uint64_t* n_core_edges);
+
 /* Tokeniser (ext/blurrily/tokeniser.h:34, tokeniser.c:59-119): `output` needs
  * strlen(input)+1 slots; returns the number of distinct codes, ascending. */
 int blurrily_tokeniser_parse_string(const char* input, uint16_t* output);
