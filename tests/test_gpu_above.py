@@ -12,16 +12,12 @@ import pytest
 import workloads as W
 from blurrily_amd import Map, RawMap, _native
 from blurrily_amd.map import _pack
+from above_truth import Truth, bar
 from helpers import ORACLE_CASES, HIP_CASES, Oracle, hip_case_inputs, oracle_case_inputs
 
 pytestmark = pytest.mark.gpu
-NUM_CODES = 28 * 28 * 28
 MATCHES = (0, 1, 2, 3)
 PERMILLE = (0, 1, 500, 999, 1000)
-
-
-def bar(T, mm, mp):
-    return max(1, mm, (mp * T + 999) // 1000)
 
 
 def want_rows(full, T, mm, mp):
@@ -131,35 +127,6 @@ def test_batch_shapes_with_a_huge_segment_beside_empty_ones():
             assert g == want_rows(full[s], len(Oracle.tokenise(s)), 1, mp), s
         if mp == 0:
             assert int(row_off[2049] - row_off[2048]) > 1000      # the one-letter needle's segment
-
-
-class Truth:
-    """The map's contents restated in numpy: a reference's matches are the needle's distinct codes among its own; rows
-    by (matches desc, weight asc, reference asc)."""
-
-    def __init__(self, strings, refs, weights):
-        self.refs = np.asarray(refs, dtype=np.int64)
-        self.weights = np.array([w if w else len(s) for s, w in zip(strings, weights)], dtype=np.int64)
-        codes = [Oracle.tokenise(s) for s in strings]
-        lens = np.array([len(c) for c in codes], dtype=np.int64)
-        self.flat = np.array([c for cs in codes for c in cs], dtype=np.int64)
-        self.starts = np.zeros(len(codes), dtype=np.int64)
-        self.starts[1:] = np.cumsum(lens)[:-1]
-        self.has = lens > 0
-
-    def rows(self, needle, mm, mp):
-        codes = Oracle.tokenise(needle)
-        T = len(codes)
-        t = bar(T, mm, mp)
-        if T == 0 or t > T:
-            return []
-        mask = np.zeros(NUM_CODES, dtype=bool)
-        mask[codes] = True
-        matches = np.add.reduceat(mask[self.flat].astype(np.int64), self.starts)
-        matches[~self.has] = 0
-        keep = np.nonzero(matches >= t)[0]
-        order = keep[np.lexsort((self.refs[keep], self.weights[keep], -matches[keep]))]
-        return [[int(self.refs[i]), int(matches[i]), int(self.weights[i])] for i in order]
 
 
 def test_a_multi_window_haystack_equals_the_numpy_restatement():

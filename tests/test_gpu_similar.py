@@ -13,30 +13,11 @@ import workloads as W
 from blurrily_amd import Map, RawMap
 from blurrily_amd.map import _pack
 from helpers import ORACLE_CASES, HIP_CASES, Oracle, hip_case_inputs, oracle_case_inputs
+from similar_truth import Truth, cut, ranked
 
 pytestmark = pytest.mark.gpu
-NUM_CODES = 28 * 28 * 28
 LIMITS = (1, 10, 65, 121, 1000)
 FLOORS = (0, 1, 300, 500, 999, 1000)
-
-
-def ranked(cands, T):
-    """cands: (ref, m, weight, R) of every reference with m >= 1 -> [ref, m, weight, R] rows in result order: J
-    descending (exact fractions), then matches descending, weight ascending, reference ascending."""
-    keys = sorted((-Fraction(m, T + R - m), -m, w, ref, R) for ref, m, w, R in cands if m >= 1)
-    return [[ref, -nm, w, R] for _, nm, w, ref, R in keys]
-
-
-def cut(rows, T, limit, p):
-    """The rows at or above the floor (J >= p / 1000 is a prefix of the ranked rows), cut at `limit`."""
-    out = []
-    if T == 0:
-        return out
-    for r in rows:
-        if len(out) == limit or 1000 * r[1] < p * (T + r[3] - r[1]):
-            break
-        out.append(r)
-    return out
 
 
 def rerank(cands, T, limit, p):
@@ -110,33 +91,6 @@ def test_rows_equal_the_oracle_reranked_at_every_limit_and_floor(kind, n, _limit
                 assert got[i] == c.want(s, limit, p), (kind, s, limit, p)
     for s in needles[:20]:
         assert c.m.find_similar(s, 10, 300) == c.want(s, 10, 300), s
-
-
-class Truth:
-    """The map's contents restated in numpy: m is the needle's distinct codes among a reference's own, R the count of
-    its own."""
-
-    def __init__(self, strings, refs, weights):
-        self.refs = np.asarray(refs, dtype=np.int64)
-        self.weights = np.array([w if w else len(s) for s, w in zip(strings, weights)], dtype=np.int64)
-        codes = [Oracle.tokenise(s) for s in strings]
-        self.R = np.array([len(c) for c in codes], dtype=np.int64)
-        self.flat = np.array([c for cs in codes for c in cs], dtype=np.int64)
-        self.starts = np.zeros(len(codes), dtype=np.int64)
-        self.starts[1:] = np.cumsum(self.R)[:-1]
-        self._ranked = {}
-
-    def rows(self, needle, limit, p):
-        codes = Oracle.tokenise(needle)
-        if needle not in self._ranked:
-            mask = np.zeros(NUM_CODES, dtype=bool)
-            mask[codes] = True
-            matches = np.add.reduceat(mask[self.flat].astype(np.int64), self.starts)
-            matches[self.R == 0] = 0
-            i = np.nonzero(matches >= 1)[0]
-            cands = zip(self.refs[i].tolist(), matches[i].tolist(), self.weights[i].tolist(), self.R[i].tolist())
-            self._ranked[needle] = ranked(cands, len(codes))
-        return cut(self._ranked[needle], len(codes), limit, p)
 
 
 _BIG = {}
