@@ -123,6 +123,10 @@ _ENTRIES = {
     "blurrily_storage_cluster_cores": (C.c_int, [_vp, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p,
                                                  C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64),
                                                  C.POINTER(C.c_uint64)]),
+    # the clusters of old and new references together, from the old ones' labels and a sweep of the new ones alone
+    "blurrily_storage_cluster_extend": (C.c_int, [_vp, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                                  C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32),
+                                                  C.POINTER(C.c_uint64)]),
 }
 EXPORTED_SYMBOLS = tuple(_ENTRIES)
 

@@ -164,4 +164,32 @@ struct ClusterCoresLabelArgs {
 };
 int launch_cluster_cores_label(const ClusterCoresLabelArgs& a, hipStream_t stream);
 
+// Cluster extend (cluster_extend_kernels.hip): the forest started from labels the caller holds
+// for the OLD nodes, and only the NEW nodes swept.  is_new is a bit per number (bit u & 31 of word u >> 5).
+// The seeds, in a launch of their own before the sweeps: old element i (node inv[i], or i) is united with the node
+// that holds old_labels[i], looked up among refs[], unless either of the two is no node or is new.
+struct ClusterExtendSeedArgs {
+  const uint32_t* old_labels;    // [n_old] the caller's
+  const uint32_t* inv;           // [n_old] (nullptr: element i is node i)
+  const uint32_t* refs;          // [n_nodes] ascending
+  const uint32_t* ntri;          // [n_nodes]
+  const uint32_t* is_new;        // [(n_nodes + 31) / 32]
+  uint32_t        n_old;
+  uint32_t        n_nodes;
+  uint32_t*       parent;        // [n_nodes]
+  ClusterTotals*  totals;
+};
+int launch_cluster_extend_seed(const ClusterExtendSeedArgs& a, hipStream_t stream);
+
+// cluster_sweep_kernel's sweep with the new nodes as the only needles: needle b / tasks of the launch is node
+// new_nodes[s.q_base + b / tasks], and it sweeps EVERY window of the image, whichever image it lives in.  A candidate
+// that is the needle is skipped, an old node is united wherever it lies, a new node only from the end at the higher
+// position.
+struct ClusterExtendSweepArgs {
+  ClusterSweepArgs s;            // (s.q_base and s.n count in new_nodes)
+  const uint32_t*  new_nodes;    // the new nodes' numbers
+  const uint32_t*  is_new;       // [(n_nodes + 31) / 32]
+};
+int launch_cluster_extend_sweep(const ClusterExtendSweepArgs& a, hipStream_t stream);
+
 }  // namespace blurrily

@@ -1,5 +1,5 @@
 // cluster_host.h -- what the clustering entries' translation units share on the host side (cluster.hip,
-// cluster_levels.hip, cluster_centres.hip): a call's launch chunk, its device scratch and the node numbering.
+// cluster_levels.hip, cluster_centres.hip, cluster_cores.hip, cluster_extend.hip): a call's launch chunk, its device scratch and the node numbering.
 #pragma once
 #include <algorithm>
 #include <vector>

@@ -657,6 +657,36 @@ class RawMap:
         _, starts, sizes = np.unique(labels[order], return_index=True, return_counts=True)
         return [refs[order[s:s + k]].tolist() for s, k in zip(starts.tolist(), sizes.tolist())]
 
+    def cluster_extend(self, old_refs, old_labels, new_refs, min_permille):
+        """The clusters of ``old_refs`` and ``new_refs`` together, from the labels the caller holds for the old ones
+        (blurrily_storage_cluster_extend): only the new references sweep the map, the old ones start from
+        ``old_labels``.  With ``old_labels`` from ``cluster(old_refs, min_permille)`` on the map as it is now and the
+        lists disjoint, the result is ``cluster``'s over both lists; a group that lost a member to a delete is
+        re-clustered on its own first (``cluster`` over its remaining members).  Returns (labels_old[n_old] uint32,
+        labels_new[n_new] uint32, the number of components, the number of edges with a new end, each once)."""
+        self._check_open()
+        mp = _permille(min_permille)
+        old, new = self._refs(old_refs), self._refs(new_refs)
+        seeds = self._refs(old_labels)
+        if len(seeds) != len(old):
+            raise ValueError(f"{len(seeds)} old labels for {len(old)} old references")
+        labels_old, labels_new = np.zeros(len(old), dtype=np.uint32), np.zeros(len(new), dtype=np.uint32)
+        n_clusters, n_edges = C.c_uint32(0), C.c_uint64(0)
+        ptr = lambda a: a.ctypes.data if len(a) else None
+        _check(self._lib.blurrily_storage_cluster_extend(self._h, ptr(old), ptr(seeds), len(old), ptr(new), len(new), mp,
+                                                         ptr(labels_old), ptr(labels_new), C.byref(n_clusters),
+                                                         C.byref(n_edges)))
+        return labels_old, labels_new, int(n_clusters.value), int(n_edges.value)
+
+    def cluster_changes(self, old_refs, old_labels, labels_old):
+        """What a database update after ``cluster_extend`` needs: (the old references whose label moved, their new
+        labels), in the list's order.  Numpy only."""
+        old, was, now = self._refs(old_refs), self._refs(old_labels), self._refs(labels_old)
+        if not len(old) == len(was) == len(now):
+            raise ValueError("old_refs, old_labels and labels_old differ in length")
+        moved = was != now
+        return old[moved], now[moved]
+
     def sync_device(self):
         self._check_open()
         _check(self._lib.blurrily_storage_sync_device(self._h))

@@ -430,6 +430,38 @@ int blurrily_storage_cluster_cores(trigram_map haystack, const uint32_t* referen
                                    uint32_t min_degree, uint32_t* labels, uint32_t* degrees, uint8_t* kinds,
                                    uint32_t* n_clusters, uint64_t* n_edges, uint64_t* n_core_edges);
 
+/* Cluster extend: the clusters of old and new references together, from labels the caller already holds for the old
+ * ones -- what a job that has clustered its map does after a put, without sweeping the old references again (DESIGN.md
+ * section 22).  T, R, m, J, the edge test, BLURRILY_NO_CLUSTER, deletes, pending puts and a reference put again: exactly
+ * as for blurrily_storage_cluster.
+ *   Nodes:  the distinct references of old_refs and new_refs together that the map holds.  A node named by new_refs is
+ *           NEW, whatever old_refs says of it; every other node is OLD.
+ *   Seeds:  a pair (old_refs[i], old_labels[i]) whose two ends are both old nodes joins them.  A pair with an end that
+ *           is not held, not listed or new does not exist.  A label need not be a component's smallest reference: any
+ *           listed old reference serves (must-link stars or chains).
+ *   Edges:  blurrily_storage_cluster's edges that have at least one new end.  Pairs of two old nodes are not looked
+ *           at: the seeds speak for them.
+ *   Label:  the smallest reference among the nodes of a node's component in the graph of seeds plus edges.
+ * labels_old[i] belongs to old_refs[i], labels_new[j] to new_refs[j]; a listed reference the map does not hold gets
+ * BLURRILY_NO_CLUSTER.  n_clusters (may be NULL): the components; n_edges (may be NULL): the edges above, each once --
+ * seeds are not counted.  All outputs depend on the map's contents, the two lists as sets of pairs and min_permille
+ * only: not on the lists' order, the images the references live in, or the order of the device's unions.
+ * The contract: when old_labels is what blurrily_storage_cluster(old_refs, min_permille) returns on the map as it is
+ * now and the two lists are disjoint, the two label arrays together and n_clusters are byte for byte what
+ * blurrily_storage_cluster gives for the two lists in one, and n_edges is that call's minus the old call's.
+ * A seed group is taken on trust.  A delete, or a put-again, of a member may have split a group, and the seeds cannot
+ * show that: run blurrily_storage_cluster over that one group's remaining members, put its labels into old_labels, then
+ * extend.  n_new == 0: the components of the seeds alone, n_edges 0; n_old == 0: blurrily_storage_cluster(new_refs).
+ * Both 0: success, nothing written but the two counts (0).  With "devices" > 1 the primary device alone serves the call.
+ * 0, or -1 with errno: EINVAL before anything needs a GPU and with nothing written (haystack NULL, min_permille > 1000,
+ * old_refs, old_labels or labels_old NULL with n_old > 0, new_refs or labels_new NULL with n_new > 0, n_old + n_new
+ * above 0xFFFFFFF0); ENODEV without a usable GPU; EIO if a bounded loop of the device's union-find ran out.  The labels
+ * are written only on success. */
+int blurrily_storage_cluster_extend(trigram_map haystack, const uint32_t* old_refs, const uint32_t* old_labels,
+                                    size_t n_old, const uint32_t* new_refs, size_t n_new, uint32_t min_permille,
+                                    uint32_t* labels_old, uint32_t* labels_new, uint32_t* n_clusters,
+                                    uint64_t* n_edges);
+
 /* Tokeniser (ext/blurrily/tokeniser.h:34, tokeniser.c:59-119): `output` needs
  * strlen(input)+1 slots; returns the number of distinct codes, ascending. */
 int blurrily_tokeniser_parse_string(const char* input, uint16_t* output);
