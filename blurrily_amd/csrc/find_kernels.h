@@ -93,7 +93,7 @@ enum : uint32_t {
   kPathResweep      = 1u << 3,    // a step swept again after the candidate pool overflowed
   kPathCompaction   = 1u << 4,    // the pool compacted in mid-sweep (threshold tightened)
   kPathSkipped      = 1u << 5,    // steps stepped over: no reference of the window can reach the threshold
-  kPathRingOverflow = 1u << 6,    // more units than the descriptor ring holds: every wave walked the table
+  kPathRingOverflow = 1u << 6,    // RESERVED: set by no kernel (the ring-overflow walk it named is gone); the bit keeps its place
   kPathPipelined    = 1u << 7,    // sweep_pipelined (65..128 distinct trigrams, wide counters)
   kPathWide         = 1u << 8,    // 16-bit counters (more than 127 distinct trigrams)
   kPathChunked      = 1u << 9,    // slice table staged through LDS in chunks (more than 128 distinct trigrams)

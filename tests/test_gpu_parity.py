@@ -216,6 +216,18 @@ def _check_batch(m, o, needles, limit):
         assert got == want, (nd, limit, got[:5], want[:5])
 
 
+def _path_flags(m, needles, limit):
+    """{name: bool array over the needles} of one counted call (RawMap.PATH_FLAGS): the kernel paths each find took."""
+    packed = b"".join(needles)
+    off = np.zeros(len(needles) + 1, dtype=np.uint64)
+    off[1:] = np.cumsum([len(x) for x in needles])
+    m.set_stats(True)
+    m.find_batch_packed(packed, off, limit)
+    flags = m.find_path_flags(len(needles))
+    m.set_stats(False)
+    return {name: (flags >> i) & 1 != 0 for i, name in enumerate(RawMap.PATH_FLAGS)}
+
+
 @pytest.mark.parametrize("n,limit", [(1, 10), (50, 3), (3000, 10), (70000, 10), (140000, 100)])
 def test_words_vs_oracle(n, limit):
     hay, off = W.words(n, seed=100 + n)
@@ -253,6 +265,10 @@ def test_long_needles_use_wide_counters():
     long2 = (b"abcdefghijklmnopqrstuvwxyz " * 40)[:1000]
     _check_batch(m, o, [long1, long2, strings[0], b"x" * 300], 10)
     _check_batch(m, o, [long1, long2], 300)
+    # the path the name says: 16-bit counters for the needle of more than 127 trigrams, and for that one alone
+    assert len(Oracle.tokenise(long1)) > 128 and max(len(Oracle.tokenise(x)) for x in (long2, strings[0], b"x" * 300)) <= 64
+    f = _path_flags(m, [long1, long2, strings[0], b"x" * 300], 10)
+    assert f["wide"].tolist() == [True, False, False, False] and f["chunked"][0] and not f["ring_overflow"].any()
 
 
 def test_arbitrary_bytes_needles():
@@ -347,6 +363,11 @@ def test_very_long_needles_and_haystack_strings():
     assert max(len(Oracle.tokenise(nd)) for nd in needles) > 1000
     _check_batch(m, o, needles, 10)
     _check_batch(m, o, needles[:3], 700)
+    # the path the docstring names: 16-bit counters and the slice table staged in chunks, for every needle beyond 128 trigrams
+    T = np.array([len(Oracle.tokenise(nd)) for nd in needles])
+    f = _path_flags(m, needles, 10)
+    assert (T > 128).sum() == 4 and np.array_equal(f["wide"], T > 128) and np.array_equal(f["chunked"], T > 128)
+    assert not f["pipelined"][T > 128].any() and not f["ring_overflow"].any()
 
 
 @pytest.mark.parametrize("n", [65519, 65520, 65521, 65535, 65536, 131039, 131040, 131041])
@@ -367,9 +388,12 @@ def test_window_boundaries_and_cross_window_ties(n):
 
 
 def test_dense_and_empty_windows_mixed():
-    """Windows whose slices hold more units than the kernel's unit ring (one string repeated
-    70 000 times) next to ordinary windows and windows with nothing for the needle: the
-    ring-overflow walk, the ring path and the skipped steps in one sweep."""
+    """Windows whose slices hold more units than the kernel's unit ring held (one string repeated
+    70 000 times) next to ordinary windows and windows with nothing for the needle: slices of
+    tens of thousands of postings streamed from a step's published table, ordinary steps and
+    stepped-over windows in one sweep.  (The descriptor ring and its overflow walk went when the
+    manager wave began to publish whole tables; "ring_overflow" is a reserved bit that no kernel
+    sets.)"""
     hay, off = W.words(150000, seed=21)
     n = len(off) - 1
     m, o = RawMap(), Oracle()
@@ -386,6 +410,11 @@ def test_dense_and_empty_windows_mixed():
     needles = [b"london", b"londno", b"lon", b"zzzzqqqq", b"zq", b"don"] + W.unpack(hay, off)[:200]
     for limit in (1, 10, 300):
         _check_batch(m, o, needles, limit)
+    # the paths the docstring names.  b"london" has 7 trigrams and 70 000 twins in window 0 (weight 6); at limit 1 its
+    # threshold is 7 matches at a rank of window 0, so the windows behind need 8 -- more than the needle has: stepped over
+    f = _path_flags(m, needles, 1)
+    assert f["skipped"][0] and f["nibble"][0] and not f["byte"][0]
+    assert not f["ring_overflow"].any() and not f["wide"].any()
 
 
 def test_every_batch_size_regime_on_a_many_window_haystack():
@@ -448,6 +477,12 @@ def test_long_needles_over_short_reference_windows():
     for i, nd in enumerate(needles):
         assert rows[i, :counts[i]].tolist() == o.find(nd, 10), nd
         assert np.array_equal(rows[i], rows[i + len(needles)])
+    # the paths the docstring names: windows 0 and 1 hold references of at most 15 trigrams (7 and 11; window 3 holds 16),
+    # so whole needles of 16 .. 64 trigrams take 4-bit counters there AND byte counters in the rest, shorter ones 4-bit alone
+    T = np.array([len(Oracle.tokenise(nd)) for nd in big])
+    f = _path_flags(m, big, 10)
+    assert (T > 15).sum() > 1000 and np.array_equal(f["byte"], T > 15) and f["nibble"].all()
+    assert not (f["ranged"] | f["pipelined"] | f["wide"] | f["ring_overflow"]).any()
 
 
 _FUZZ_FIRST = int(os.environ.get("BLURRILY_FUZZ_FIRST", "0"))           # soak runs: BLURRILY_FUZZ_FIRST=10 BLURRILY_FUZZ_SEEDS=50
