@@ -109,6 +109,17 @@ _ENTRIES = {
     "blurrily_storage_find_similar": (C.c_int, [_vp, C.c_char_p, C.c_uint16, C.c_uint32, C.c_void_p, C.c_void_p]),
     "blurrily_storage_find_references_similar": (C.c_int, [_vp, C.c_void_p, C.c_size_t, C.c_uint16, C.c_uint32,
                                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # scoped similarity find: the similarity find among a scope's members, one scope or a scope per needle
+    "blurrily_storage_find_batch_similar_in": (C.c_int, [_vp, _vp, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint16,
+                                                         C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "blurrily_storage_find_similar_in": (C.c_int, [_vp, _vp, C.c_char_p, C.c_uint16, C.c_uint32, C.c_void_p,
+                                                   C.c_void_p]),
+    "blurrily_storage_find_batch_similar_each_in": (C.c_int, [_vp, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                                              C.c_void_p, C.c_size_t, C.c_uint16, C.c_uint32,
+                                                              C.c_void_p, C.c_void_p, C.c_void_p]),
+    "blurrily_storage_find_references_similar_each_in": (C.c_int, [_vp, C.c_void_p, C.c_size_t, C.c_void_p,
+                                                                   C.c_void_p, C.c_size_t, C.c_uint16, C.c_uint32,
+                                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     # clusters: connected components of the similarity self-join, one label per reference
     "blurrily_storage_cluster": (C.c_int, [_vp, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p,
                                            C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),

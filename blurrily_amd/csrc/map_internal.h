@@ -8,7 +8,7 @@
 //   host_batch.hip   host-buffer batches: needle_len, longest_needle, BatchBlocks; the chunked pipeline,
 //                    find_batch_host, find_few
 //   refs.hip         by reference: refs_extract, ExtractionOnHost, stage_reference_needles, get / find_references entries
-//   scope.hip        scoped find, a scope per needle
+//   scope.hip        scoped find, a scope per needle, the scoped similarity find
 //   above.hip, similar.hip   the threshold and similarity finds (their shared sort: segsort.h)
 //   cluster.hip      connected components of the similarity self-join (similar.hip's per-rank trigram table)
 #pragma once
@@ -353,6 +353,16 @@ struct SimilarTables {
   ~SimilarTables();
 };
 int similar_table(DeviceIndex* ix, hipStream_t stream, SimilarTables& call, SimilarTable* out);
+// device scratch of one similarity call, freed on the way out (b[8], b[9]: the scoped calls' own)
+struct SimilarScratch {
+  DeviceBuffer b[10];
+  ~SimilarScratch() { for (auto& x : b) x.release(); }
+};
+// The top-`limit` rows of n needles over the map as it is now, to host memory: results / row_ntri [n * limit],
+// counts [n].  sm: a scoped call's masks, in the tombstone bitmaps' place.
+int similar_run(trigram_map m, size_t n, const NeedleView& N, uint32_t limit, uint32_t min_permille,
+                trigram_match results, uint32_t* counts, uint32_t* row_ntri, hipStream_t stream, SimilarScratch& S,
+                const ScopeMasks* sm = nullptr);
 
 }  // namespace detail
 }  // namespace blurrily

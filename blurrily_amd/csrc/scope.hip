@@ -1,6 +1,9 @@
 // scope.hip -- scoped find and a scope per needle (blurrily_scope_*, blurrily_storage_find_in / _find_batch_in[_device],
-// _find_batch_each_in[_device], _find_references_each_in; DESIGN.md sections 12 and 13).
+// _find_batch_each_in[_device], _find_references_each_in; DESIGN.md sections 12 and 13) and the scoped similarity find
+// (blurrily_storage_find_batch_similar_in, _find_similar_in, _find_batch_similar_each_in,
+// _find_references_similar_each_in; section 24).
 #include "map_internal.h"
+#include "scope_similar.h"
 
 using namespace blurrily;
 using namespace blurrily::detail;
@@ -618,6 +621,225 @@ int blurrily_storage_find_references_each_in(trigram_map m, const blurrily_scope
   N.rn = &x.needles;
   if (each_run(m, P, N, n, limit, out.rows, out.counts, true, true, stream) < 0) return -1;
   return B.copy_out(out.counts, x.needles.ntri, out.rows, counts, nb_trigrams, results, stream);   // (the counts of trigrams: the extraction's own)
+}
+
+}  // extern "C"
+
+// ---- scoped similarity find (blurrily_storage_find_batch_similar_in / _find_similar_in / _find_batch_similar_each_in /
+// _find_references_similar_each_in) ---------------------------------------------------------------
+// The similarity find's rows (section 15) among a scope's members only, the strategies chosen as the scoped find
+// chooses them: the similarity sweep with the scope's masks in the tombstone bitmaps' place (any scope, any limit), or
+// the members scored directly (scope_similar_kernels.hip).  The each-in entries group their needles with each_plan: the
+// direct ones in one launch, a sweep per masked scope and one for the NO_SCOPE group over their compacted needles; the
+// rows come back to the host per group and are put in the caller's order there.
+namespace {
+
+int similar_check(const uint32_t* counts, uint32_t min_permille, size_t n, uint16_t limit, const void* results,
+                  bool needles) {
+  if (!counts || min_permille > 1000 || (n && limit && !results) || (n && !needles) || n > kMaxBatchNeedles) {
+    errno = EINVAL;
+    return -1;
+  }
+  return 0;
+}
+
+// The direct launch's device output for nd workgroups (zeroed: a needle's rows past its count read 0, as the sweep's do).
+struct DirectOut {
+  trigram_match rows;
+  uint32_t *rntri, *counts;
+  size_t rows_bytes, rn_bytes;
+  int reserve(DeviceBuffer& b, size_t nd, uint16_t limit, hipStream_t stream) {
+    rows_bytes = align_up(std::max<size_t>(nd * limit * sizeof(trigram_match_t), 16), 256);
+    rn_bytes = align_up(std::max<size_t>(nd * limit * 4, 16), 256);
+    const size_t bytes = rows_bytes + rn_bytes + align_up(nd * 4, 256);
+    if (b.reserve(bytes, stream) < 0) return -1;
+    unsigned char* p = static_cast<unsigned char*>(b.p);
+    rows = reinterpret_cast<trigram_match>(p);
+    rntri = reinterpret_cast<uint32_t*>(p + rows_bytes);
+    counts = reinterpret_cast<uint32_t*>(p + rows_bytes + rn_bytes);
+    BLURRILY_HIP_TRY(hipMemsetAsync(p, 0, bytes, stream));
+    return 0;
+  }
+  // to host arrays of nd needles (waits for the stream)
+  int read(size_t nd, uint16_t limit, trigram_match h_rows, uint32_t* h_counts, uint32_t* h_rntri, hipStream_t stream) const {
+    BLURRILY_HIP_TRY(hipMemcpyAsync(h_counts, counts, nd * 4, hipMemcpyDeviceToHost, stream));
+    BLURRILY_HIP_TRY(hipMemcpyAsync(h_rows, rows, nd * limit * sizeof(trigram_match_t), hipMemcpyDeviceToHost, stream));
+    if (h_rntri) BLURRILY_HIP_TRY(hipMemcpyAsync(h_rntri, rntri, nd * limit * 4, hipMemcpyDeviceToHost, stream));
+    BLURRILY_HIP_TRY(hipStreamSynchronize(stream));
+    return 0;
+  }
+};
+
+// The planned each-in call.  strings: the needles on the device as strings (null for references); V: as code lists
+// (references always; strings when a group is swept).
+int similar_each_run(trigram_map m, const EachPlan& P, const char* d_packed, const uint64_t* d_offsets,
+                     const NeedleView* V, size_t n, uint16_t limit, uint32_t min_permille, trigram_match results,
+                     uint32_t* counts, uint32_t* row_ntri, SimilarScratch& S, hipStream_t stream) {
+  const size_t nd = P.order.size(), ng = P.idx.size();
+  if (P.any_empty) std::memset(counts, 0, n * 4);
+  std::vector<trigram_match_t> h_rows;
+  std::vector<uint32_t> h_counts, h_rntri;
+  auto put_back = [&](size_t k, uint32_t q) {           // group-local needle k is the caller's q
+    counts[q] = h_counts[k];
+    std::memcpy(results + size_t(q) * limit, h_rows.data() + k * limit, size_t(limit) * sizeof(trigram_match_t));
+    if (row_ntri) std::memcpy(row_ntri + size_t(q) * limit, h_rntri.data() + k * limit, size_t(limit) * 4);
+  };
+  auto host_room = [&](size_t k) {
+    h_rows.resize(k * limit); h_counts.resize(k);
+    if (row_ntri) h_rntri.resize(k * limit);
+  };
+  // one upload: scope table | order | idx
+  size_t at = 0;
+  auto take = [&](size_t bytes) { const size_t here = at; at += align_up(std::max<size_t>(bytes, 8), 256); return here; };
+  const size_t o_tab = take(P.table.size() * sizeof(ScopeDirect)), o_ord = take(nd * sizeof(uint2)), o_idx = take(ng * 4);
+  const size_t up = at, o_gq = take(ng * 8), o_gn = take(ng * 4);
+  m->h_each.assign(up, 0);
+  unsigned char* h = m->h_each.data();
+  if (!P.table.empty()) std::memcpy(h + o_tab, P.table.data(), P.table.size() * sizeof(ScopeDirect));
+  if (nd) std::memcpy(h + o_ord, P.order.data(), nd * sizeof(uint2));
+  if (ng) std::memcpy(h + o_idx, P.idx.data(), ng * 4);
+  if (m->ws_each.reserve(at, stream) < 0) return -1;
+  unsigned char* d = static_cast<unsigned char*>(m->ws_each.p);
+  BLURRILY_HIP_TRY(hipMemcpyAsync(d, h, up, hipMemcpyHostToDevice, stream));
+  // every needle served directly: one launch
+  if (nd) {
+    DirectOut out;
+    if (out.reserve(S.b[9], nd, limit, stream) < 0) return -1;
+    ScopeSimilarArgs a{};
+    if (d_packed) { a.packed = d_packed; a.offsets = d_offsets; }
+    else { a.codes = V->codes; a.qoff = V->qoff; a.ntri = V->ntri; }
+    a.order = reinterpret_cast<const uint2*>(d + o_ord); a.scopes = reinterpret_cast<const ScopeDirect*>(d + o_tab);
+    a.n = uint32_t(nd); a.max_members = P.max_members; a.limit = limit; a.min_permille = min_permille;
+    a.rows = out.rows; a.row_ntri = row_ntri ? out.rntri : nullptr; a.counts = out.counts;
+    if (launch_scope_similar(a, stream) < 0) return -1;
+    host_room(nd);
+    if (out.read(nd, limit, h_rows.data(), h_counts.data(), row_ntri ? h_rntri.data() : nullptr, stream) < 0) return -1;
+    for (size_t b = 0; b < nd; ++b) put_back(b, P.order[b].x);
+  }
+  // a sweep per group over its needles, compacted
+  const uint32_t* d_idx = reinterpret_cast<const uint32_t*>(d + o_idx);
+  for (size_t g = 0; g + 1 < P.group_start.size(); ++g) {
+    const size_t k0 = P.group_start[g], cnt = P.group_start[g + 1] - k0;
+    const blurrily_scope sc = P.group_scope[g];
+    const ScopeMasks sm{sc ? static_cast<const uint32_t*>(sc->d_mask[0].p) : nullptr,
+                        sc && sc->has_delta ? static_cast<const uint32_t*>(sc->d_mask[1].p) : nullptr};
+    uint64_t* gq = reinterpret_cast<uint64_t*>(d + o_gq) + k0;
+    uint32_t* gn = reinterpret_cast<uint32_t*>(d + o_gn) + k0;
+    if (launch_scope_similar_gather(V->qoff, V->ntri, d_idx + k0, uint32_t(cnt), gq, gn, stream) < 0) return -1;
+    host_room(cnt);
+    if (similar_run(m, cnt, NeedleView{V->codes, gq, gn}, limit, min_permille, h_rows.data(), h_counts.data(),
+                    row_ntri ? h_rntri.data() : nullptr, stream, S, sc ? &sm : nullptr) < 0)
+      return -1;
+    for (size_t k = 0; k < cnt; ++k) put_back(k, P.idx[k0 + k]);
+  }
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int blurrily_storage_find_batch_similar_in(trigram_map m, blurrily_scope sc, const char* packed, const uint64_t* offsets,
+                                           size_t n, uint16_t limit, uint32_t min_permille, trigram_match results,
+                                           uint32_t* counts, uint32_t* row_ntri) {
+  if (scope_check(m, sc) < 0 || similar_check(counts, min_permille, n, limit, results, packed && offsets) < 0) return -1;
+  DeviceScope scope(m->dev.device);
+  hipStream_t stream = nullptr;
+  if (scope_prepare(m, sc, stream) < 0) return -1;     // (without a GPU this is what fails, with ENODEV)
+  if (n == 0) return 0;
+  NameScope names(&m->last_kernels);
+  m->last_kernels.clear();
+  if (limit == 0 || sc->n_held == 0) { std::memset(counts, 0, n * 4); return 0; }
+  SimilarScratch S;
+  if (scope_takes_direct(m, sc, limit)) {
+    const BatchBlocks B(n, size_t(offsets[n]), 0, false);
+    if (S.b[8].reserve(B.in_bytes, stream) < 0) return -1;
+    unsigned char* d_in = static_cast<unsigned char*>(S.b[8].p);
+    if (B.copy_in(d_in, packed, offsets, stream) < 0) return -1;
+    DirectOut out;
+    if (out.reserve(S.b[9], n, limit, stream) < 0) return -1;
+    ScopeSimilarArgs a{};
+    a.packed = B.in(d_in).packed; a.offsets = B.in(d_in).offsets;
+    a.one = ScopeDirect{sc->m_off, sc->m_codes, sc->m_ref, sc->m_weight, sc->n_direct, 0u};
+    a.n = uint32_t(n); a.max_members = sc->n_direct; a.limit = limit; a.min_permille = min_permille;
+    a.rows = out.rows; a.row_ntri = row_ntri ? out.rntri : nullptr; a.counts = out.counts;
+    if (launch_scope_similar(a, stream) < 0) return -1;
+    return out.read(n, limit, results, counts, row_ntri, stream);
+  }
+  const ScopeMasks sm{static_cast<const uint32_t*>(sc->d_mask[0].p),
+                      sc->has_delta ? static_cast<const uint32_t*>(sc->d_mask[1].p) : nullptr};
+  NeedleView N;
+  if (stage_string_needles(m, packed, offsets, n, S.b[6], stream, &N) < 0) return -1;
+  return similar_run(m, n, N, limit, min_permille, results, counts, row_ntri, stream, S, &sm);
+}
+
+int blurrily_storage_find_similar_in(trigram_map m, blurrily_scope sc, const char* needle, uint16_t limit,
+                                     uint32_t min_permille, trigram_match results, uint32_t* row_ntri) {
+  if (!needle) { errno = EINVAL; return -1; }
+  const uint64_t offsets[2] = {0, std::strlen(needle)};
+  uint32_t count = 0;
+  if (blurrily_storage_find_batch_similar_in(m, sc, needle, offsets, 1, limit, min_permille, results, &count, row_ntri) < 0)
+    return -1;
+  return int(count);
+}
+
+int blurrily_storage_find_batch_similar_each_in(trigram_map m, const blurrily_scope* scopes, size_t n_scopes,
+                                                const uint32_t* which, const char* packed, const uint64_t* offsets,
+                                                size_t n, uint16_t limit, uint32_t min_permille, trigram_match results,
+                                                uint32_t* counts, uint32_t* row_ntri) {
+  if (each_check(m, scopes, n_scopes) < 0 ||
+      similar_check(counts, min_permille, n, limit, results, which && packed && offsets) < 0 ||
+      each_check_which(which, n, n_scopes) < 0)
+    return -1;
+  DeviceScope scope(m->dev.device);
+  hipStream_t stream = nullptr;
+  if (map_ready(m, stream) < 0) return -1;
+  if (n == 0) return 0;
+  m->last_kernels.clear();
+  if (limit == 0) { std::memset(counts, 0, n * 4); return 0; }
+  EachPlan P;
+  if (each_plan(m, scopes, n_scopes, which, n, limit, stream, &P) < 0) return -1;
+  NameScope names(&m->last_kernels);                     // (the scopes' preparation is no part of the find)
+  SimilarScratch S;
+  NeedleView V{};
+  const BatchBlocks B(n, size_t(offsets[n]), 0, false);
+  unsigned char* d_in = nullptr;
+  if (!P.idx.empty()) {                                  // a swept group: tokenised, the strings in front of the codes
+    if (stage_string_needles(m, packed, offsets, n, S.b[6], stream, &V) < 0) return -1;
+    d_in = static_cast<unsigned char*>(S.b[6].p);
+  } else if (!P.order.empty()) {
+    if (S.b[8].reserve(B.in_bytes, stream) < 0) return -1;
+    d_in = static_cast<unsigned char*>(S.b[8].p);
+    if (B.copy_in(d_in, packed, offsets, stream) < 0) return -1;
+  } else {
+    std::memset(counts, 0, n * 4);
+    return 0;
+  }
+  return similar_each_run(m, P, B.in(d_in).packed, B.in(d_in).offsets, &V, n, limit, min_permille, results, counts,
+                          row_ntri, S, stream);
+}
+
+int blurrily_storage_find_references_similar_each_in(trigram_map m, const blurrily_scope* scopes, size_t n_scopes,
+                                                     const uint32_t* which, const uint32_t* references, size_t n,
+                                                     uint16_t limit, uint32_t min_permille, trigram_match results,
+                                                     uint32_t* counts, uint32_t* row_ntri, uint32_t* nb_trigrams) {
+  if (each_check(m, scopes, n_scopes) < 0 ||
+      similar_check(counts, min_permille, n, limit, results, which && references) < 0 ||
+      each_check_which(which, n, n_scopes) < 0)
+    return -1;
+  DeviceScope scope(m->dev.device);
+  hipStream_t stream = nullptr;
+  if (map_ready(m, stream) < 0) return -1;
+  if (n == 0) return 0;
+  m->last_kernels.clear();
+  EachPlan P;
+  if (limit && each_plan(m, scopes, n_scopes, which, n, limit, stream, &P) < 0) return -1;
+  SimilarScratch S;
+  NeedleView V;                                          // (after every scope's preparation: both use ws_refs)
+  if (stage_reference_needles(m, references, n, S.b[6], stream, nb_trigrams, &V) < 0) return -1;
+  NameScope names(&m->last_kernels);                     // (the preparation and the extraction are no part of the find)
+  if (limit == 0 || (P.idx.empty() && P.order.empty())) { std::memset(counts, 0, n * 4); return 0; }
+  return similar_each_run(m, P, nullptr, nullptr, &V, n, limit, min_permille, results, counts, row_ntri, S, stream);
 }
 
 }  // extern "C"

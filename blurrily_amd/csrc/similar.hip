@@ -14,12 +14,6 @@ namespace {
 constexpr size_t   kSimChunkNeedles = size_t(1) << 20;   // needles per sweep launch
 constexpr uint64_t kSimChunkKeys    = uint64_t(1) << 24; // keys (16 B, twice: keys and sorted keys) or rows per chunk
 
-// device scratch of one call, freed on the way out
-struct SimilarScratch {
-  DeviceBuffer b[10];
-  ~SimilarScratch() { for (auto& x : b) x.release(); }
-};
-
 // ---- per-rank trigram counts, one table per device image -------------------------------------------------------------
 // A table is built at the first similarity call on an image and kept beside it: an image that never serves one holds
 // what it held before.  An image is known by the allocation of its postings, under the runtime's process-wide buffer
@@ -113,14 +107,19 @@ int similar_finish(uint32_t n_img, SimilarKey* const keys[2], SimilarKey* const 
   return launch_similar_rows(r, stream);
 }
 
-// The top-`limit` rows of n needles over the map as it is now: results / row_ntri [n * limit], counts [n].
-int similar_run(trigram_map m, size_t n, const NeedleView& N, uint32_t limit, uint32_t min_permille,
-                trigram_match results, uint32_t* counts, uint32_t* row_ntri, hipStream_t stream, SimilarScratch& S) {
+}  // namespace
+
+// The top-`limit` rows of n needles over the map as it is now: results / row_ntri [n * limit], counts [n].  sm: a
+// scoped call's masks, in the tombstone bitmaps' place (they exclude the deleted ranks too).
+int blurrily::detail::similar_run(trigram_map m, size_t n, const NeedleView& N, uint32_t limit, uint32_t min_permille,
+                                  trigram_match results, uint32_t* counts, uint32_t* row_ntri, hipStream_t stream,
+                                  SimilarScratch& S, const ScopeMasks* sm) {
   const MapImages I = map_images(m);
   const uint32_t n_img = I.n;
   const bool with_delta = n_img > 1;
   DeviceIndex* const* img = I.img;
-  const uint32_t* const* tomb = I.tomb;
+  const uint32_t* const masks[2] = {sm ? sm->base : nullptr, sm ? sm->delta : nullptr};
+  const uint32_t* const* tomb = sm ? masks : I.tomb;
   SimilarTables call;
   SimilarTable tab[2];
   for (uint32_t i = 0; i < n_img; ++i)
@@ -283,8 +282,6 @@ int similar_run(trigram_map m, size_t n, const NeedleView& N, uint32_t limit, ui
   }
   return 0;
 }
-
-}  // namespace
 
 extern "C" {
 

@@ -533,6 +533,83 @@ class RawMap:
                                                                   mp, *ptrs))
         return out
 
+    # -- scoped similarity find: the similarity find among a scope's members -------------------
+    def find_batch_similar_in_packed(self, scope, packed, offsets, limit, min_permille=0):
+        """``find_batch_similar_packed`` among the scope's members only (a ``Scope`` or an iterable of references).
+        Returns (rows[n, limit, 3] uint32, counts[n] uint32, row_ntri[n, limit] uint32)."""
+        self._check_open()
+        mp = _permille(min_permille)
+        if not isinstance(scope, Scope):
+            with self.scope(scope) as one_shot:
+                return RawMap.find_batch_similar_in_packed(self, one_shot, packed, offsets, limit, mp)
+        sc = self._own(scope)
+        data, offsets, n = _needles(packed, offsets)
+        limit = _batch_limit(limit)
+        out, ptrs = _blocks(n, limit, row_ntri=True)
+        _check(self._lib.blurrily_storage_find_batch_similar_in(self._h, sc._h, data, offsets.ctypes.data, n, limit, mp,
+                                                                *ptrs))
+        return out
+
+    def find_similar_in(self, scope, needle, limit, min_permille=0):
+        """``find_similar`` among the scope's members only: a list of ``[ref, matches, weight, R]``."""
+        self._check_open()
+        mp = _permille(min_permille)
+        c_limit = _find_limit(limit)
+        if not isinstance(scope, Scope):
+            with self.scope(scope) as one_shot:
+                return RawMap.find_similar_in(self, one_shot, needle, limit, mp)
+        sc = self._own(scope)
+        rows = np.zeros((max(c_limit, 1), 3), dtype=np.uint32)
+        ntri = np.zeros(max(c_limit, 1), dtype=np.uint32)
+        res = _check(self._lib.blurrily_storage_find_similar_in(self._h, sc._h, _as_bytes(needle), c_limit, mp,
+                                                                rows.ctypes.data, ntri.ctypes.data))
+        return [r + [t] for r, t in zip(rows[:res].tolist(), ntri[:res].tolist())]
+
+    def find_batch_similar_each_in(self, scopes, which, packed, offsets, limit, min_permille=0):
+        """``find_batch_similar_packed`` with a scope per needle: needle i among ``scopes[which[i]]`` only, or the whole
+        map when ``which[i]`` is None.  Returns (rows[n, limit, 3] uint32, counts[n] uint32, row_ntri[n, limit])."""
+        self._check_open()
+        mp = _permille(min_permille)
+        which = self._which(which, len(offsets) - 1)
+        with self._scopes_of(scopes) as scs:
+            limit = _batch_limit(limit)
+            data, offsets, n = _needles(packed, offsets)
+            out, ptrs = _blocks(n, limit, row_ntri=True)
+            _check(self._lib.blurrily_storage_find_batch_similar_each_in(
+                self._h, self._handles(scs), len(scs), which.ctypes.data if n else None, data, offsets.ctypes.data, n,
+                limit, mp, *ptrs))
+            return out
+
+    def find_batch_by_reference_similar_each_in(self, scopes, which, references, limit, min_permille=0):
+        """``find_batch_by_reference_similar`` with a scope per reference.  Returns (rows[n, limit, 3] uint32,
+        counts[n] uint32, row_ntri[n, limit] uint32, nb_trigrams[n] uint32)."""
+        self._check_open()
+        mp = _permille(min_permille)
+        refs = self._refs(references)
+        n = len(refs)
+        which = self._which(which, n)
+        with self._scopes_of(scopes) as scs:
+            limit = _batch_limit(limit)
+            out, ptrs = _blocks(n, limit, row_ntri=True, per_needle=1)
+            _check(self._lib.blurrily_storage_find_references_similar_each_in(
+                self._h, self._handles(scs), len(scs), which.ctypes.data if n else None,
+                refs.ctypes.data if n else None, n, limit, mp, *ptrs))
+            return out
+
+    def join_similar_within(self, scopes, limit, min_permille=0):
+        """The blocked similarity self-join: every member of every scope ranked by similarity among its own scope, in
+        one GPU batch.  Returns (references[k] uint32, which[k] uint32: the scope of each, rows: k lists of
+        [ref, matches, weight, R]) over the members the map holds, scope after scope."""
+        self._check_open()
+        with self._scopes_of(scopes) as scs:
+            parts = [sc._refs if sc._refs is not None else np.zeros(0, np.uint32) for sc in scs]
+            refs = np.concatenate(parts).astype(np.uint32) if parts else np.zeros(0, np.uint32)
+            which = np.repeat(np.arange(len(parts), dtype=np.uint32), [len(p) for p in parts])
+            rows, counts, rntri, ntri = self.find_batch_by_reference_similar_each_in(scs, which, refs, limit,
+                                                                                     min_permille)
+        held = np.nonzero(ntri)[0]
+        return refs[held], which[held], _lists(rows[held], counts[held], rntri[held])
+
     # -- clusters (no reference counterpart): connected components of the similarity self-join ----------------------
     def cluster(self, references, min_permille):
         """Single-linkage clusters of the stored references under "J >= min_permille / 1000" (blurrily_storage_cluster).
@@ -933,6 +1010,19 @@ class Map(RawMap):
         """``[self.find_similar(s, limit, min_permille) for s in needles]`` in one GPU batch."""
         limit = _limit_or_default(limit)
         return _lists(*super().find_batch_similar_packed(*_normalised(needles), limit, min_permille))
+
+    def find_similar_in(self, scope, needle, limit=LIMIT_DEFAULT, min_permille=0):
+        """``find_similar`` among the references of `scope` (a ``Scope`` or an iterable of references) only."""
+        return super().find_similar_in(scope, normalize_string(needle), limit, min_permille)
+
+    def find_batch_similar_each_in(self, scopes, which, needles, limit=LIMIT_DEFAULT, min_permille=0):
+        """``[self.find_similar_in(scopes[w], s, limit, min_permille) if w is not None else self.find_similar(s, limit,
+        min_permille) for s, w in zip(needles, which)]`` in one GPU batch."""
+        limit = _limit_or_default(limit)
+        return _lists(*super().find_batch_similar_each_in(scopes, which, *_normalised(needles), limit, min_permille))
+
+    def join_similar_within(self, scopes, limit=LIMIT_DEFAULT, min_permille=0):
+        return super().join_similar_within(scopes, _limit_or_default(limit), min_permille)
 
     def find_batch(self, needles, limit=LIMIT_DEFAULT):
         """``[self.find(s, limit) for s in needles]`` in one GPU batch."""

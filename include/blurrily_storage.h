@@ -336,6 +336,39 @@ int blurrily_storage_find_references_similar(trigram_map haystack, const uint32_
                                              uint16_t limit, uint32_t min_permille, trigram_match results,
                                              uint32_t* counts, uint32_t* row_ntri, uint32_t* nb_trigrams);
 
+/* Scoped similarity find: the similarity find among a scope's members only.  A needle's rows
+ * are the rows of ALL references passing the similarity find's row test, in its order, with every row whose reference
+ * is not a held member of the scope removed, cut at `limit` -- not the unscoped call's rows at some limit, filtered.
+ * T, R, m, the row test and the order are the similarity find's; membership is the scoped find's, read against the map
+ * as it is at each call (a deleted member is not found; one put after the scope was made is, pending or folded; one
+ * deleted and put again is found with its new trigrams and its new R; an empty scope, or one with no held member,
+ * gives no rows).  T == 0: no rows; limit == 0: counts 0.  results, counts and row_ntri (optional) are laid out as for
+ * blurrily_storage_find_batch_similar, host memory.  With "devices" > 1 the primary device alone serves the call.
+ * 0, or -1 with errno.  EINVAL, before anything needs a GPU and with nothing written: a NULL map, a NULL scope or a
+ * scope of another map, which[i] >= n_scopes (other than BLURRILY_NO_SCOPE), n_scopes > 0 with scopes NULL, counts
+ * NULL, results NULL with n and limit non-zero, needles (or which) NULL with n > 0, n above the batch's cap,
+ * min_permille > 1000.  Valid arguments without a usable GPU: ENODEV. */
+int blurrily_storage_find_batch_similar_in(trigram_map haystack, blurrily_scope scope, const char* packed,
+                                           const uint64_t* offsets, size_t n, uint16_t limit, uint32_t min_permille,
+                                           trigram_match results, uint32_t* counts, uint32_t* row_ntri);
+/* One needle: the row count, or -1 with errno. */
+int blurrily_storage_find_similar_in(trigram_map haystack, blurrily_scope scope, const char* needle, uint16_t limit,
+                                     uint32_t min_permille, trigram_match results, uint32_t* row_ntri);
+/* A scope per needle: element i is the single-scope call on scopes[which[i]], or blurrily_storage_find_similar when
+ * which[i] == BLURRILY_NO_SCOPE. */
+int blurrily_storage_find_batch_similar_each_in(trigram_map haystack, const blurrily_scope* scopes, size_t n_scopes,
+                                                const uint32_t* which, const char* packed, const uint64_t* offsets,
+                                                size_t n, uint16_t limit, uint32_t min_permille,
+                                                trigram_match results, uint32_t* counts, uint32_t* row_ntri);
+/* blurrily_storage_find_references_similar with a scope per reference: an absent reference gets no rows and
+ * nb_trigrams[i] == 0 (nb_trigrams may be NULL); a held one that is a member of its own scope is its own row at
+ * similarity 1 (first unless another member has the same trigram set). */
+int blurrily_storage_find_references_similar_each_in(trigram_map haystack, const blurrily_scope* scopes,
+                                                     size_t n_scopes, const uint32_t* which,
+                                                     const uint32_t* references, size_t n, uint16_t limit,
+                                                     uint32_t min_permille, trigram_match results, uint32_t* counts,
+                                                     uint32_t* row_ntri, uint32_t* nb_trigrams);
+
 /* Clusters: connected components of the similarity self-join, computed on the device.  T, R, m
  * and J = m / (T + R - m) as for the similarity find; the map is read as find reads it.
  *   Nodes: the distinct references of the list that the map holds (a reference listed twice is one node).
