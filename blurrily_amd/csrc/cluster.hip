@@ -1,7 +1,6 @@
 // cluster.hip -- blurrily_storage_cluster (include/blurrily_storage.h): single-linkage clusters
-// of stored references under a floor of trigram Jaccard similarity, one label per reference.  It drives the map's
-// internals (map_internal.h: the by-reference front end, the images, the similarity find's per-rank trigram table);
-// the kernels are cluster_kernels.hip's.
+// of stored references under a floor of trigram Jaccard similarity, one label per reference.  The call sequence is
+// ClusterCall's (cluster_host.h), with one forest and nothing of its own; the kernels are cluster_kernels.hip's.
 #include "map_internal.h"
 #include "cluster.h"
 #include "cluster_host.h"
@@ -24,60 +23,16 @@ extern "C" int blurrily_storage_cluster(trigram_map m, const uint32_t* reference
   NameScope names(&m->last_kernels);
   m->last_kernels.clear();
 
-  std::vector<uint32_t> uniq, inv;
-  number_nodes(references, n, uniq, inv);
-  const size_t nu = uniq.size();
-  ClusterScratch S;
-  if (S.refs.reserve(nu * 4, stream) < 0 || S.parent.reserve(nu * 4, stream) < 0 ||
-      S.labels.reserve(n * 4, stream) < 0 || S.totals.reserve(sizeof(ClusterTotals), stream) < 0 ||
-      (!inv.empty() && S.inv.reserve(n * 4, stream) < 0))
+  ClusterCall c(m, stream);
+  if (c.begin(references, n, 1, sizeof(ClusterTotals)) < 0) return -1;
+  ClusterTotals* d_totals = static_cast<ClusterTotals*>(c.d_totals);
+  if (c.sweep(c.nu, min_permille, d_totals, [&](const ClusterSweepArgs& a) { return launch_cluster_sweep(a, stream); }) < 0)
     return -1;
-  uint32_t* d_refs = static_cast<uint32_t*>(S.refs.p);
-  ClusterTotals* d_totals = static_cast<ClusterTotals*>(S.totals.p);
-  BLURRILY_HIP_TRY(hipMemcpyAsync(d_refs, uniq.data(), nu * 4, hipMemcpyHostToDevice, stream));
-  if (!inv.empty()) BLURRILY_HIP_TRY(hipMemcpyAsync(S.inv.p, inv.data(), n * 4, hipMemcpyHostToDevice, stream));
-  BLURRILY_HIP_TRY(hipMemsetAsync(d_totals, 0, sizeof(ClusterTotals), stream));
-
-  RefExtract x;                                                // the by-reference front end (section 11)
-  if (refs_extract(m, d_refs, nu, stream, &x) < 0) return -1;
-  const MapImages I = map_images(m);                           // (the images the extraction looked the references up in)
-  SimilarTables call;
-  SimilarTable tab[2];
-  for (uint32_t i = 0; i < I.n; ++i)
-    if (similar_table(I.img[i], stream, call, &tab[i]) < 0) return -1;
-
-  // the node tables: a word per position of both images, a parent per number
-  const uint64_t n_pos = (uint64_t(I.img[0]->n_windows) + (I.n > 1 ? I.img[1]->n_windows : 0u)) * kWindowRanks;
-  if (n_pos > 0xFFFFFFFFull) { errno = ENOMEM; return -1; }
-  if (S.node_of_pos.reserve(std::max<size_t>(n_pos * 4, 16), stream) < 0) return -1;
-  BLURRILY_HIP_TRY(hipMemsetAsync(S.node_of_pos.p, 0xFF, n_pos * 4, stream));   // (kNoNode)
-  ClusterNodesArgs na{x.loc, x.needles.ntri, uint32_t(nu), static_cast<uint32_t*>(S.node_of_pos.p),
-                      static_cast<uint32_t*>(S.parent.p)};
-  if (launch_cluster_nodes(na, stream) < 0) return -1;
-
-  for (uint32_t i = 0; i < I.n; ++i) {
-    const DeviceIndex& ix = *I.img[i];
-    for (size_t s = 0; s < nu; s += kClusterChunkNeedles) {
-      const size_t nc = std::min(kClusterChunkNeedles, nu - s);
-      ClusterSweepArgs a{};
-      a.slice_se = ix.d_slice_se; a.ent = ix.d_ent; a.win_max_tri = ix.d_win_max_tri; a.win_min_tri = tab[i].win_min_tri;
-      a.ntri_of_rank = tab[i].ntri_of_rank; a.n_windows = ix.n_windows; a.n_refs = ix.n_refs; a.dense_min8 = ix.dense_min8;
-      a.per = windows_per_workgroup(m, ix, nc); a.win0 = i ? x.win0_delta : 0u;
-      a.qcodes = x.needles.codes; a.qoff = x.needles.qoff; a.q_ntri = x.needles.ntri; a.loc = x.loc;
-      a.q_base = uint32_t(s); a.n = uint32_t(nc); a.n_nodes = uint32_t(nu); a.min_permille = min_permille;
-      a.node_of_pos = na.node_of_pos; a.parent = na.parent; a.totals = d_totals;
-      if (launch_cluster_sweep(a, stream) < 0) return -1;
-    }
-  }
-
-  ClusterLabelArgs la{na.parent, x.needles.ntri, d_refs, inv.empty() ? nullptr : static_cast<const uint32_t*>(S.inv.p),
-                      uint32_t(nu), uint32_t(n), static_cast<uint32_t*>(S.labels.p), d_totals};
-  if (launch_cluster_label(la, stream) < 0) return -1;
+  if (launch_cluster_label(c.label_args(), stream) < 0) return -1;
   ClusterTotals totals{};
-  BLURRILY_HIP_TRY(hipMemcpyAsync(&totals, d_totals, sizeof totals, hipMemcpyDeviceToHost, stream));
-  BLURRILY_HIP_TRY(hipMemcpyAsync(labels, S.labels.p, n * 4, hipMemcpyDeviceToHost, stream));
-  BLURRILY_HIP_TRY(hipStreamSynchronize(stream));
-  if (totals.error) { errno = EIO; return -1; }
+  if (c.read_totals(&totals) < 0) return -1;
+  BLURRILY_HIP_TRY(hipMemcpyAsync(labels, c.d_labels, n * 4, hipMemcpyDeviceToHost, stream));
+  if (c.wait(&totals) < 0) return -1;
   if (n_clusters) *n_clusters = totals.clusters;
   if (n_edges) *n_edges = totals.edges;
   return 0;

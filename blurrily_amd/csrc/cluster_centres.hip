@@ -1,25 +1,14 @@
 // cluster_centres.hip -- blurrily_storage_cluster_centres (include/blurrily_storage.h): the
 // clusters of blurrily_storage_cluster with each node's degree, each component's centre and whether a node shares an
-// edge with its centre.  It follows cluster.hip step for step, with four more words per number on the device (degree,
-// centre, attached, and the 64-bit word the centres are chosen in) and, when the caller asks for `attached`, a second
-// sweep; the sweeps and the centres are cluster_centres_kernels.hip's, the node tables and the labels
-// cluster_kernels.hip's kernels as they are.
+// edge with its centre.  The call sequence is ClusterCall's (cluster_host.h), with four more words per number on the
+// device and, when the caller asks for `attached`, a second sweep; the sweeps and the centres are
+// cluster_centres_kernels.hip's, the node tables and the labels cluster_kernels.hip's kernels as they are.
 #include "map_internal.h"
 #include "cluster.h"
 #include "cluster_host.h"
 
 using namespace blurrily;
 using namespace blurrily::detail;
-
-namespace {
-
-// what a call holds on the device beyond ClusterScratch, freed on the way out
-struct CentresScratch {
-  DeviceBuffer degree, best, centre_of, attached, degrees, centres;
-  ~CentresScratch() { for (DeviceBuffer* b : {&degree, &best, &centre_of, &attached, &degrees, &centres}) b->release(); }
-};
-
-}  // namespace
 
 extern "C" int blurrily_storage_cluster_centres(trigram_map m, const uint32_t* references, size_t n,
                                                 uint32_t min_permille, uint32_t* labels, uint32_t* degrees,
@@ -38,89 +27,41 @@ extern "C" int blurrily_storage_cluster_centres(trigram_map m, const uint32_t* r
   NameScope names(&m->last_kernels);
   m->last_kernels.clear();
 
-  std::vector<uint32_t> uniq, inv;
-  number_nodes(references, n, uniq, inv);
-  const size_t nu = uniq.size();
-  ClusterScratch S;
-  CentresScratch X;
-  if (S.refs.reserve(nu * 4, stream) < 0 || S.parent.reserve(nu * 4, stream) < 0 ||
-      S.labels.reserve(n * 4, stream) < 0 || S.totals.reserve(sizeof(ClusterTotals), stream) < 0 ||
-      (!inv.empty() && S.inv.reserve(n * 4, stream) < 0) || X.degree.reserve(nu * 4, stream) < 0 ||
-      X.best.reserve(nu * 8, stream) < 0 || X.centre_of.reserve(nu * 4, stream) < 0 ||
-      X.attached.reserve(nu * 4, stream) < 0 || X.degrees.reserve(n * 4, stream) < 0 ||
-      X.centres.reserve(n * 4, stream) < 0)
+  ClusterCall c(m, stream);
+  if (c.begin(references, n, 1, sizeof(ClusterTotals)) < 0) return -1;
+  const size_t nu = c.nu;
+  ClusterTotals* d_totals = static_cast<ClusterTotals*>(c.d_totals);
+  // four more things per number (degree, the 64-bit word the centres are chosen in, centre, attached), two per element
+  uint32_t *d_degree, *d_centre_of, *d_attached, *d_degrees, *d_centres;
+  unsigned long long* d_best;
+  if (c.more(d_degree, nu * 4, true) < 0 || c.more(d_best, nu * 8, true) < 0 || c.more(d_centre_of, nu * 4) < 0 ||
+      c.more(d_attached, nu * 4) < 0 || c.more(d_degrees, n * 4) < 0 || c.more(d_centres, n * 4) < 0)
     return -1;
-  uint32_t* d_refs = static_cast<uint32_t*>(S.refs.p);
-  uint32_t* d_degree = static_cast<uint32_t*>(X.degree.p);
-  ClusterTotals* d_totals = static_cast<ClusterTotals*>(S.totals.p);
-  BLURRILY_HIP_TRY(hipMemcpyAsync(d_refs, uniq.data(), nu * 4, hipMemcpyHostToDevice, stream));
-  if (!inv.empty()) BLURRILY_HIP_TRY(hipMemcpyAsync(S.inv.p, inv.data(), n * 4, hipMemcpyHostToDevice, stream));
-  BLURRILY_HIP_TRY(hipMemsetAsync(d_totals, 0, sizeof(ClusterTotals), stream));
-  BLURRILY_HIP_TRY(hipMemsetAsync(d_degree, 0, nu * 4, stream));
-  BLURRILY_HIP_TRY(hipMemsetAsync(X.best.p, 0, nu * 8, stream));
-
-  RefExtract x;                                                // the by-reference front end (section 11)
-  if (refs_extract(m, d_refs, nu, stream, &x) < 0) return -1;
-  const MapImages I = map_images(m);                           // (the images the extraction looked the references up in)
-  SimilarTables call;
-  SimilarTable tab[2];
-  for (uint32_t i = 0; i < I.n; ++i)
-    if (similar_table(I.img[i], stream, call, &tab[i]) < 0) return -1;
-
-  // the node tables: a word per position of both images, a parent per number
-  const uint64_t n_pos = (uint64_t(I.img[0]->n_windows) + (I.n > 1 ? I.img[1]->n_windows : 0u)) * kWindowRanks;
-  if (n_pos > 0xFFFFFFFFull) { errno = ENOMEM; return -1; }
-  if (S.node_of_pos.reserve(std::max<size_t>(n_pos * 4, 16), stream) < 0) return -1;
-  BLURRILY_HIP_TRY(hipMemsetAsync(S.node_of_pos.p, 0xFF, n_pos * 4, stream));   // (kNoNode)
-  ClusterNodesArgs na{x.loc, x.needles.ntri, uint32_t(nu), static_cast<uint32_t*>(S.node_of_pos.p),
-                      static_cast<uint32_t*>(S.parent.p)};
-  if (launch_cluster_nodes(na, stream) < 0) return -1;
 
   // one sweep over every image and chunk: the unions and the degrees, or (mark) the nodes attached to their centres
-  auto sweeps = [&](bool mark) -> int {
-    for (uint32_t i = 0; i < I.n; ++i) {
-      const DeviceIndex& ix = *I.img[i];
-      for (size_t s = 0; s < nu; s += kClusterChunkNeedles) {
-        const size_t nc = std::min(kClusterChunkNeedles, nu - s);
-        ClusterCentresSweepArgs A{};
-        ClusterSweepArgs& a = A.s;
-        a.slice_se = ix.d_slice_se; a.ent = ix.d_ent; a.win_max_tri = ix.d_win_max_tri; a.win_min_tri = tab[i].win_min_tri;
-        a.ntri_of_rank = tab[i].ntri_of_rank; a.n_windows = ix.n_windows; a.n_refs = ix.n_refs; a.dense_min8 = ix.dense_min8;
-        a.per = windows_per_workgroup(m, ix, nc); a.win0 = i ? x.win0_delta : 0u;
-        a.qcodes = x.needles.codes; a.qoff = x.needles.qoff; a.q_ntri = x.needles.ntri; a.loc = x.loc;
-        a.q_base = uint32_t(s); a.n = uint32_t(nc); a.n_nodes = uint32_t(nu); a.min_permille = min_permille;
-        a.node_of_pos = na.node_of_pos; a.parent = na.parent; a.totals = d_totals;
-        A.degree = d_degree; A.centre_of = static_cast<const uint32_t*>(X.centre_of.p);
-        A.attached = static_cast<uint32_t*>(X.attached.p);
-        if (launch_cluster_centres_sweep(A, mark, stream) < 0) return -1;
-      }
-    }
-    return 0;
+  auto sweeps = [&](bool mark) {
+    return c.sweep(nu, min_permille, d_totals, [&](const ClusterSweepArgs& a) {
+      return launch_cluster_centres_sweep({a, d_degree, d_centre_of, d_attached}, mark, stream);
+    });
   };
   if (sweeps(false) < 0) return -1;
-
-  const uint32_t* d_inv = inv.empty() ? nullptr : static_cast<const uint32_t*>(S.inv.p);
-  ClusterLabelArgs la{na.parent, x.needles.ntri, d_refs, d_inv, uint32_t(nu), uint32_t(n),
-                      static_cast<uint32_t*>(S.labels.p), d_totals};
+  const ClusterLabelArgs la = c.label_args();
   if (launch_cluster_label(la, stream) < 0) return -1;
-  ClusterCentresArgs ca{na.parent, x.needles.ntri, d_refs, d_inv, d_degree, uint32_t(nu), uint32_t(n),
-                        static_cast<unsigned long long*>(X.best.p), static_cast<uint32_t*>(X.centre_of.p),
-                        static_cast<uint32_t*>(X.attached.p), static_cast<uint32_t*>(X.centres.p),
-                        static_cast<uint32_t*>(X.degrees.p), d_totals};
+  ClusterCentresArgs ca{la.parent, la.ntri, la.refs, la.inv, d_degree, la.n_nodes, la.n, d_best, d_centre_of, d_attached,
+                        d_centres, d_degrees, d_totals};
   if (launch_cluster_centres(ca, stream) < 0) return -1;
   if (attached && sweeps(true) < 0) return -1;                 // (nobody asked: the second sweep is not run)
 
   ClusterTotals totals{};
   std::vector<uint32_t> att(attached ? nu : 0);                // the device's words per number; bytes per element below
-  BLURRILY_HIP_TRY(hipMemcpyAsync(&totals, d_totals, sizeof totals, hipMemcpyDeviceToHost, stream));
-  BLURRILY_HIP_TRY(hipMemcpyAsync(labels, S.labels.p, n * 4, hipMemcpyDeviceToHost, stream));
-  if (degrees) BLURRILY_HIP_TRY(hipMemcpyAsync(degrees, X.degrees.p, n * 4, hipMemcpyDeviceToHost, stream));
-  if (centres) BLURRILY_HIP_TRY(hipMemcpyAsync(centres, X.centres.p, n * 4, hipMemcpyDeviceToHost, stream));
-  if (attached) BLURRILY_HIP_TRY(hipMemcpyAsync(att.data(), X.attached.p, nu * 4, hipMemcpyDeviceToHost, stream));
-  BLURRILY_HIP_TRY(hipStreamSynchronize(stream));
-  if (totals.error) { errno = EIO; return -1; }
+  if (c.read_totals(&totals) < 0) return -1;
+  BLURRILY_HIP_TRY(hipMemcpyAsync(labels, c.d_labels, n * 4, hipMemcpyDeviceToHost, stream));
+  if (degrees) BLURRILY_HIP_TRY(hipMemcpyAsync(degrees, d_degrees, n * 4, hipMemcpyDeviceToHost, stream));
+  if (centres) BLURRILY_HIP_TRY(hipMemcpyAsync(centres, d_centres, n * 4, hipMemcpyDeviceToHost, stream));
+  if (attached) BLURRILY_HIP_TRY(hipMemcpyAsync(att.data(), d_attached, nu * 4, hipMemcpyDeviceToHost, stream));
+  if (c.wait(&totals) < 0) return -1;
   if (attached)
-    for (size_t i = 0; i < n; ++i) attached[i] = uint8_t(att[inv.empty() ? i : inv[i]]);
+    for (size_t i = 0; i < n; ++i) attached[i] = uint8_t(att[c.inv.empty() ? i : c.inv[i]]);
   if (n_clusters) *n_clusters = totals.clusters;
   if (n_edges) *n_edges = totals.edges;
   return 0;

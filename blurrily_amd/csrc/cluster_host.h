@@ -1,21 +1,18 @@
-// cluster_host.h -- what the clustering entries' translation units share on the host side (cluster.hip,
-// cluster_levels.hip, cluster_centres.hip, cluster_cores.hip, cluster_extend.hip): a call's launch chunk, its device scratch and the node numbering.
+// cluster_host.h -- the host-side call sequence the clustering entries share (cluster.hip, cluster_levels.hip,
+// cluster_centres.hip, cluster_cores.hip, cluster_extend.hip): the node numbering and
+// ClusterCall, which owns a call's device scratch, runs what every entry does in front of its sweeps, fills the sweeps'
+// common arguments per image and chunk, and reads the totals back.  The device code is each entry's own.
 #pragma once
 #include <algorithm>
 #include <vector>
 
+#include "cluster.h"
 #include "map_internal.h"
 
 namespace blurrily {
 namespace detail __attribute__((visibility("hidden"))) {
 
 constexpr size_t kClusterChunkNeedles = size_t(1) << 20;   // needles per sweep launch (nothing else bounds a chunk)
-
-// device scratch of one call, freed on the way out
-struct ClusterScratch {
-  DeviceBuffer refs, inv, node_of_pos, parent, labels, totals;
-  ~ClusterScratch() { for (DeviceBuffer* b : {&refs, &inv, &node_of_pos, &parent, &labels, &totals}) b->release(); }
-};
 
 // The caller's references ascending without repeats (the node numbering), and each element's number.  A list that is
 // strictly ascending already is its own numbering: inv stays empty.
@@ -33,6 +30,78 @@ inline void number_nodes(const uint32_t* references, size_t n, std::vector<uint3
     inv[uint32_t(keyed[i])] = uint32_t(uniq.size() - 1);
   }
 }
+
+// One call of a clustering entry, from the entry's checks to its return.
+struct ClusterCall {
+  ClusterCall(trigram_map m, hipStream_t stream) : m(m), stream(stream) {}
+  ~ClusterCall();                                            // frees every buffer of the call
+  ClusterCall(const ClusterCall&) = delete;
+  ClusterCall& operator=(const ClusterCall&) = delete;
+
+  // One more device buffer of the call's, one allocation each, zeroed on the stream if asked (no bytes: p = nullptr).
+  template <class T>
+  int more(T*& p, size_t bytes, bool zeroed = false) {
+    void* v = nullptr;
+    if (alloc(&v, bytes, zeroed) < 0) return -1;
+    p = static_cast<T*>(v);
+    return 0;
+  }
+
+  // The beginning: the numbering of `references` (n >= 1), the call's buffers -- `forests` parent arrays of nu words,
+  // as many rows of n labels, totals_bytes of zeroed totals -- the uploads, the extraction, the images with their
+  // per-rank tables, and the node tables: node_of_pos once, parent + k * nu per forest.
+  int begin(const uint32_t* references, size_t n, uint32_t forests, size_t totals_bytes);
+
+  // `needles` needles (of the numbering, or of an entry's own list) over every image, in chunks: the sweep arguments
+  // all entries share, handed to launch(const ClusterSweepArgs&), which adds the entry's own and launches.
+  template <class Launch>
+  int sweep(size_t needles, uint32_t min_permille, ClusterTotals* totals, Launch&& launch) const {
+    for (uint32_t i = 0; i < images.n; ++i) {
+      const DeviceIndex& ix = *images.img[i];
+      for (size_t s = 0; s < needles; s += kClusterChunkNeedles) {
+        const size_t nc = std::min(kClusterChunkNeedles, needles - s);
+        ClusterSweepArgs a{};
+        a.slice_se = ix.d_slice_se; a.ent = ix.d_ent; a.win_max_tri = ix.d_win_max_tri; a.win_min_tri = tab[i].win_min_tri;
+        a.ntri_of_rank = tab[i].ntri_of_rank; a.n_windows = ix.n_windows; a.n_refs = ix.n_refs; a.dense_min8 = ix.dense_min8;
+        a.per = windows_per_workgroup(m, ix, nc); a.win0 = i ? x.win0_delta : 0u;
+        a.qcodes = x.needles.codes; a.qoff = x.needles.qoff; a.q_ntri = x.needles.ntri; a.loc = x.loc;
+        a.q_base = uint32_t(s); a.n = uint32_t(nc); a.n_nodes = uint32_t(nu); a.min_permille = min_permille;
+        a.node_of_pos = d_node_of_pos; a.parent = d_parent; a.totals = totals;
+        if (launch(a) < 0) return -1;
+      }
+    }
+    return 0;
+  }
+
+  // The ending: cluster_label_kernel's arguments for forest k (its row of labels, its ClusterTotals) ...
+  ClusterLabelArgs label_args(uint32_t k = 0) const;
+  // ... the totals on their way to the host, and, after whatever else the entry reads back, the wait for the stream:
+  // EIO if one of the forests' totals, t[0 .. forests), reports that a bounded loop ran out.
+  int read_totals(void* host);
+  int wait(const ClusterTotals* t);
+
+  trigram_map m;
+  hipStream_t stream;
+  size_t      n = 0, nu = 0;                                  // the caller's elements, the numbers
+  std::vector<uint32_t> inv;                                 // element i's number (empty: i itself)
+  RefExtract  x{};                                           // the by-reference front end's (section 11), over every number
+  uint32_t*   d_refs = nullptr;                              // [nu] ascending
+  const uint32_t* d_inv = nullptr;                           // [n] (nullptr: inv is empty)
+  uint32_t*   d_node_of_pos = nullptr;
+  uint32_t*   d_parent = nullptr;                            // forest k: words [k * nu, k * nu + nu)
+  uint32_t*   d_labels = nullptr;                            // forest k: words [k * n, k * n + n), as the caller's
+  void*       d_totals = nullptr;                            // totals_bytes, as the entry's kernels type them
+
+ private:
+  int alloc(void** p, size_t bytes, bool zeroed);
+  uint32_t  forests = 0;
+  size_t    totals_bytes = 0;
+  MapImages images{};                                        // (the images the extraction looked the references up in)
+  SimilarTables tables;
+  SimilarTable  tab[2];
+  std::vector<uint32_t> uniq;                                // the numbering's references (the upload's source: kept to the end)
+  std::vector<void*> buffers;
+};
 
 }  // namespace detail
 }  // namespace blurrily
