@@ -12,9 +12,9 @@ import workloads as W
 from blurrily_amd import Map, RawMap, _native
 from blurrily_amd.map import _pack
 from helpers import Oracle
+from scope_truth import NUM_CODES, Truth    # noqa: F401
 
 pytestmark = pytest.mark.gpu
-NUM_CODES = 28 * 28 * 28
 STRATEGIES = (0, 1, 2)                # auto, mask, direct
 EXACT = (16, 64, 65, 127, 128)       # distinct trigram counts at the find path's class boundaries
 
@@ -24,44 +24,6 @@ def _exact(rng, letters, t):
         s = bytes(rng.choice(letters, size=t - 1).tolist())
         if len(Oracle.tokenise(s)) == t:
             return s
-
-
-class Truth:
-    """The map's contents (reference -> (string, weight)) and the scoped find restated in numpy: a member's matches are
-    the needle's distinct codes among its own; rows by (matches desc, weight asc, reference asc), matches >= 1."""
-
-    def __init__(self):
-        self.entries = {}
-
-    def put(self, s, ref, weight):
-        if ref not in self.entries:
-            self.entries[ref] = (s, weight if weight else len(s))
-
-    def delete(self, ref):
-        self.entries.pop(ref, None)
-
-    def members(self, scope):
-        refs = sorted({int(r) for r in scope if int(r) in self.entries})
-        codes = [Oracle.tokenise(self.entries[r][0]) for r in refs]
-        lens = np.array([len(c) for c in codes], dtype=np.int64)
-        flat = np.array([c for cs in codes for c in cs], dtype=np.int64)
-        starts = np.zeros(len(refs), dtype=np.int64)
-        if len(refs):
-            starts[1:] = np.cumsum(lens)[:-1]
-        return (np.array(refs, dtype=np.int64), np.array([self.entries[r][1] for r in refs], dtype=np.int64),
-                flat, starts)
-
-    @staticmethod
-    def rows(mem, needle, limit):
-        refs, weights, flat, starts = mem
-        if len(refs) == 0 or limit == 0:
-            return []
-        mask = np.zeros(NUM_CODES, dtype=bool)
-        mask[Oracle.tokenise(needle)] = True
-        matches = np.add.reduceat(mask[flat].astype(np.int64), starts)
-        keep = np.nonzero(matches >= 1)[0]
-        order = keep[np.lexsort((refs[keep], weights[keep], -matches[keep]))][:limit]
-        return [[int(refs[i]), int(matches[i]), int(weights[i])] for i in order]
 
 
 def _put(m, t, strings, refs, weights):
