@@ -120,6 +120,17 @@ _ENTRIES = {
     "blurrily_storage_find_references_similar_each_in": (C.c_int, [_vp, C.c_void_p, C.c_size_t, C.c_void_p,
                                                                    C.c_void_p, C.c_size_t, C.c_uint16, C.c_uint32,
                                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # scoped threshold find: the threshold find among a scope's members, one scope or a scope per needle
+    "blurrily_storage_find_batch_above_in": (C.c_int, [_vp, _vp, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32,
+                                                       C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "blurrily_storage_find_above_in": (C.c_int, [_vp, _vp, C.c_char_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64,
+                                                 C.POINTER(C.c_uint64)]),
+    "blurrily_storage_find_batch_above_each_in": (C.c_int, [_vp, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                                            C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32,
+                                                            C.c_void_p, C.c_uint64, C.c_void_p]),
+    "blurrily_storage_find_references_above_each_in": (C.c_int, [_vp, C.c_void_p, C.c_size_t, C.c_void_p,
+                                                                 C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32,
+                                                                 C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     # clusters: connected components of the similarity self-join, one label per reference
     "blurrily_storage_cluster": (C.c_int, [_vp, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p,
                                            C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),

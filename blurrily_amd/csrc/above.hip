@@ -1,64 +1,70 @@
 // above.hip -- the threshold find's entry points (include/blurrily_storage.h).  They drive the
 // map's internals (map_internal.h: the mutation log, the device images, the string and by-reference front ends);
-// the kernels are above_kernels.hip's.
+// the kernels are above_kernels.hip's.  The find runs in two steps, above_count and above_emit (map_internal.h), which
+// the scoped threshold find (scope.hip; section 27) runs apart, with a scope's masks.
 #include "above.h"
 #include "map_internal.h"
 
 using namespace blurrily;
 using namespace blurrily::detail;
 
+namespace blurrily {
+namespace detail {
+
 namespace {
 
-constexpr size_t   kAboveChunkNeedles = size_t(1) << 20;   // needles per sweep launch
-constexpr uint64_t kAboveChunkRows    = uint64_t(1) << 24; // rows per emit chunk (keys, sorted keys, rows: 28 B each)
+// one image's launch arguments for needles [s, s + nc) of the call
+AboveArgs above_args(trigram_map m, const MapImages& I, const ScopeMasks* sm, uint32_t i, const NeedleView& N, size_t s,
+                     size_t nc, uint32_t min_matches, uint32_t min_permille) {
+  const DeviceIndex& ix = *I.img[i];
+  AboveArgs a{};
+  a.slice_se = ix.d_slice_se; a.ent = ix.d_ent; a.win_max_tri = ix.d_win_max_tri;
+  a.tomb = sm ? (i ? sm->delta : sm->base) : I.tomb[i];
+  a.n_windows = ix.n_windows; a.n_refs = ix.n_refs; a.dense_min8 = ix.dense_min8; a.per = windows_per_workgroup(m, ix, nc);
+  a.qcodes = N.codes; a.qoff = N.qoff + s; a.q_ntri = N.ntri + s; a.q_base = uint32_t(s); a.n = uint32_t(nc);
+  a.min_matches = min_matches; a.min_permille = min_permille;
+  return a;
+}
 
-// device scratch of one call, freed on the way out
-struct AboveScratch {
-  DeviceBuffer b[8];
-  ~AboveScratch() { for (auto& x : b) x.release(); }
-};
+}  // namespace
 
-// Count (and, when results is given, write) the rows of n needles over the map as it is now.  row_off: n + 1 offsets.
-int above_run(trigram_map m, size_t n, const NeedleView& N, uint32_t min_matches, uint32_t min_permille,
-              trigram_match results, uint64_t capacity, uint64_t* row_off, hipStream_t stream, AboveScratch& S) {
+int above_count(trigram_map m, size_t n, const NeedleView& N, uint32_t min_matches, uint32_t min_permille,
+                hipStream_t stream, const ScopeMasks* sm, AboveCounted* C) {
   const MapImages I = map_images(m);
   const uint32_t n_img = I.n;
-  const bool with_delta = n_img > 1;
-  DeviceIndex* const* img = I.img;
-  const uint32_t* const* tomb = I.tomb;
-  auto args_of = [&](uint32_t i, size_t s, size_t nc) {
-    const DeviceIndex& ix = *img[i];
-    AboveArgs a{};
-    a.slice_se = ix.d_slice_se; a.ent = ix.d_ent; a.win_max_tri = ix.d_win_max_tri; a.tomb = tomb[i];
-    a.n_windows = ix.n_windows; a.n_refs = ix.n_refs; a.dense_min8 = ix.dense_min8; a.per = windows_per_workgroup(m, ix, nc);
-    a.qcodes = N.codes; a.qoff = N.qoff + s; a.q_ntri = N.ntri + s; a.q_base = uint32_t(s); a.n = uint32_t(nc);
-    a.min_matches = min_matches; a.min_permille = min_permille;
-    return a;
-  };
-
-  // 1. count
-  if (S.b[0].reserve(std::max<size_t>(size_t(n_img) * n * 4, 16), stream) < 0) return -1;
-  uint32_t* d_counts = static_cast<uint32_t*>(S.b[0].p);
+  C->n = n;
+  C->n_img = n_img;
+  if (C->d_counts.reserve(std::max<size_t>(size_t(n_img) * n * 4, 16), stream) < 0) return -1;
+  uint32_t* d_counts = static_cast<uint32_t*>(C->d_counts.p);
   BLURRILY_HIP_TRY(hipMemsetAsync(d_counts, 0, size_t(n_img) * n * 4, stream));
   for (uint32_t i = 0; i < n_img; ++i)
     for (size_t s = 0; s < n; s += kAboveChunkNeedles) {
-      AboveArgs a = args_of(i, s, std::min(kAboveChunkNeedles, n - s));
+      AboveArgs a = above_args(m, I, sm, i, N, s, std::min(kAboveChunkNeedles, n - s), min_matches, min_permille);
       a.counts = d_counts + size_t(i) * n + s;
       if (launch_above_sweep(a, stream) < 0) return -1;
     }
-  std::vector<uint32_t> cnt(size_t(n_img) * n);
-  BLURRILY_HIP_TRY(hipMemcpyAsync(cnt.data(), d_counts, cnt.size() * 4, hipMemcpyDeviceToHost, stream));
+  C->cnt.resize(size_t(n_img) * n);
+  BLURRILY_HIP_TRY(hipMemcpyAsync(C->cnt.data(), d_counts, C->cnt.size() * 4, hipMemcpyDeviceToHost, stream));
   BLURRILY_HIP_TRY(hipStreamSynchronize(stream));
-  row_off[0] = 0;
-  for (size_t q = 0; q < n; ++q) row_off[q + 1] = row_off[q] + cnt[q] + (with_delta ? cnt[n + q] : 0u);
-  if (!results) return 0;
-  if (capacity < row_off[n]) { errno = ERANGE; return -1; }
+  return 0;
+}
 
-  // 2. emit, sort and write, in chunks of needles whose rows fit the chunk's scratch
+int above_emit(trigram_map m, const NeedleView& N, uint32_t min_matches, uint32_t min_permille, const AboveCounted& C,
+               const uint64_t* row_off, trigram_match results, hipStream_t stream, AboveScratch& S,
+               const ScopeMasks* sm) {
+  const MapImages I = map_images(m);
+  const size_t n = C.n;
+  const uint32_t n_img = C.n_img;
+  DeviceIndex* const* img = I.img;
+  const std::vector<uint32_t>& cnt = C.cnt;
+  uint32_t* d_counts = static_cast<uint32_t*>(C.d_counts.p);
+  auto args_of = [&](uint32_t i, size_t s, size_t nc) {
+    return above_args(m, I, sm, i, N, s, nc, min_matches, min_permille);
+  };
+  // emit, sort and write, in chunks of needles whose rows fit the chunk's scratch
   size_t s = 0;
   while (s < n) {
-    size_t e = s + 1;
-    while (e < n && e - s < kAboveChunkNeedles && row_off[e + 1] - row_off[s] <= kAboveChunkRows) ++e;
+    const size_t e = above_chunk_end(row_off, n, s);
     const size_t nc = e - s;
     const uint64_t rows = row_off[e] - row_off[s];
     if (rows == 0) { s = e; continue; }
@@ -109,6 +115,23 @@ int above_run(trigram_map m, size_t n, const NeedleView& N, uint32_t min_matches
     s = e;
   }
   return 0;
+}
+
+}  // namespace detail
+}  // namespace blurrily
+
+namespace {
+
+// Count (and, when results is given, write) the rows of n needles over the map as it is now.  row_off: n + 1 offsets.
+int above_run(trigram_map m, size_t n, const NeedleView& N, uint32_t min_matches, uint32_t min_permille,
+              trigram_match results, uint64_t capacity, uint64_t* row_off, hipStream_t stream, AboveScratch& S) {
+  AboveCounted C;
+  if (above_count(m, n, N, min_matches, min_permille, stream, nullptr, &C) < 0) return -1;
+  row_off[0] = 0;
+  for (size_t q = 0; q < n; ++q) row_off[q + 1] = row_off[q] + C.rows(q);
+  if (!results) return 0;
+  if (capacity < row_off[n]) { errno = ERANGE; return -1; }
+  return above_emit(m, N, min_matches, min_permille, C, row_off, results, stream, S, nullptr);
 }
 
 }  // namespace

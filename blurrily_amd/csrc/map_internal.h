@@ -8,7 +8,7 @@
 //   host_batch.hip   host-buffer batches: needle_len, longest_needle, BatchBlocks; the chunked pipeline,
 //                    find_batch_host, find_few
 //   refs.hip         by reference: refs_extract, ExtractionOnHost, stage_reference_needles, get / find_references entries
-//   scope.hip        scoped find, a scope per needle, the scoped similarity find
+//   scope.hip        scoped find, a scope per needle, the scoped similarity and threshold finds
 //   above.hip, similar.hip   the threshold and similarity finds (their shared sort: segsort.h)
 //   cluster.hip      connected components of the similarity self-join (similar.hip's per-rank trigram table)
 #pragma once
@@ -335,6 +335,42 @@ struct ExtractionOnHost {
   // (on the device reference i's codes sit at codes + qoff[i] + i, as a needle's do; `all` starts behind the pad)
   const uint16_t* codes_of(size_t i) const { return all.data() + (qoff[i] + i - n); }
 };
+
+// ---- above.hip -------------------------------------------------------------------------------------------------------
+constexpr size_t   kAboveChunkNeedles = size_t(1) << 20;   // needles per sweep launch
+constexpr uint64_t kAboveChunkRows    = uint64_t(1) << 24; // rows per emit chunk (keys, sorted keys, rows: 28 B each)
+// The needles [s, e) of one emit chunk: as many as the bounds allow, one at least.  row_off: the call's n + 1 offsets.
+inline size_t above_chunk_end(const uint64_t* row_off, size_t n, size_t s) {
+  size_t e = s + 1;
+  while (e < n && e - s < kAboveChunkNeedles && row_off[e + 1] - row_off[s] <= kAboveChunkRows) ++e;
+  return e;
+}
+// device scratch of one threshold call, freed on the way out (b[8], b[9]: the scoped calls' own)
+struct AboveScratch {
+  DeviceBuffer b[10];
+  ~AboveScratch() { for (auto& x : b) x.release(); }
+};
+// What the count step found, kept for the emit step: per image and needle, on the device and on the host.
+struct AboveCounted {
+  DeviceBuffer          d_counts;      // [n_img * n]
+  std::vector<uint32_t> cnt;           // the same, read back
+  size_t                n = 0;
+  uint32_t              n_img = 0;
+  AboveCounted() = default;
+  AboveCounted(const AboveCounted&) = delete;
+  AboveCounted& operator=(const AboveCounted&) = delete;
+  ~AboveCounted() { d_counts.release(); }
+  uint64_t rows(size_t q) const { return uint64_t(cnt[q]) + (n_img > 1 ? cnt[n + q] : 0u); }
+};
+// The threshold find in its two steps.  above_count: the rows of each of n needles over the map as it is now (waits for
+// the stream).  above_emit: their rows to host memory, needle q's at results + row_off[q] (row_off: n + 1 offsets that
+// add up C.rows), in chunks of needles bounded by kAboveChunkNeedles and kAboveChunkRows.  The same needles, bar and
+// masks go to both.  sm: a scoped call's masks, in the tombstone bitmaps' place.
+int above_count(trigram_map m, size_t n, const NeedleView& N, uint32_t min_matches, uint32_t min_permille,
+                hipStream_t stream, const ScopeMasks* sm, AboveCounted* C);
+int above_emit(trigram_map m, const NeedleView& N, uint32_t min_matches, uint32_t min_permille, const AboveCounted& C,
+               const uint64_t* row_off, trigram_match results, hipStream_t stream, AboveScratch& S,
+               const ScopeMasks* sm);
 
 // ---- similar.hip ------------------------------------------------------------------------------------------------------
 // An image's per-rank trigram counts (similar.h: SimilarTable), built at the first call that needs them and kept in a

@@ -610,6 +610,76 @@ class RawMap:
         held = np.nonzero(ntri)[0]
         return refs[held], which[held], _lists(rows[held], counts[held], rntri[held])
 
+    # -- scoped threshold find: the threshold find among a scope's members -----------------------
+    def find_batch_above_in_packed(self, scope, packed, offsets, min_matches=0, min_permille=0):
+        """``find_batch_above_packed`` among the scope's members only (a ``Scope`` or an iterable of references).
+        Returns (rows[R, 3] uint32, row_off[n + 1] uint64)."""
+        self._check_open()
+        mm, mp = self._bar(min_matches, min_permille)
+        if not isinstance(scope, Scope):
+            with self.scope(scope) as one_shot:
+                return RawMap.find_batch_above_in_packed(self, one_shot, packed, offsets, mm, mp)
+        sc = self._own(scope)
+        data, offsets, n = _needles(packed, offsets)
+        return self._above(lambda rows, cap, off: self._lib.blurrily_storage_find_batch_above_in(
+            self._h, sc._h, data, offsets.ctypes.data, n, mm, mp, rows, cap, off), n)
+
+    def find_above_in(self, scope, needle, min_matches=0, min_permille=0):
+        """``find_above`` among the scope's members only: a list of ``[ref, matches, weight]``."""
+        self._check_open()
+        mm, mp = self._bar(min_matches, min_permille)
+        if not isinstance(scope, Scope):
+            with self.scope(scope) as one_shot:
+                return RawMap.find_above_in(self, one_shot, needle, mm, mp)
+        sc = self._own(scope)
+        s = _as_bytes(needle)
+        total = C.c_uint64(0)
+        rows = _call_growing(lambda rows, cap: self._lib.blurrily_storage_find_above_in(
+            self._h, sc._h, s, mm, mp, rows, cap, C.byref(total)), 1024, lambda: total.value, row=(3,))
+        return rows[:total.value].tolist()
+
+    def find_batch_above_each_in(self, scopes, which, packed, offsets, min_matches=0, min_permille=0):
+        """``find_batch_above_packed`` with a scope per needle: needle i among ``scopes[which[i]]`` only, or the whole
+        map when ``which[i]`` is None.  Returns (rows[R, 3] uint32, row_off[n + 1] uint64)."""
+        self._check_open()
+        mm, mp = self._bar(min_matches, min_permille)
+        which = self._which(which, len(offsets) - 1)
+        with self._scopes_of(scopes) as scs:
+            data, offsets, n = _needles(packed, offsets)
+            return self._above(lambda rows, cap, off: self._lib.blurrily_storage_find_batch_above_each_in(
+                self._h, self._handles(scs), len(scs), which.ctypes.data if n else None, data, offsets.ctypes.data, n,
+                mm, mp, rows, cap, off), n)
+
+    def find_batch_by_reference_above_each_in(self, scopes, which, references, min_matches=0, min_permille=0):
+        """``find_batch_by_reference_above`` with a scope per reference.  Returns (rows[R, 3] uint32,
+        row_off[n + 1] uint64, nb_trigrams[n] uint32)."""
+        self._check_open()
+        mm, mp = self._bar(min_matches, min_permille)
+        refs = self._refs(references)
+        n = len(refs)
+        which = self._which(which, n)
+        ntri = np.zeros(n, dtype=np.uint32)
+        with self._scopes_of(scopes) as scs:
+            rows, row_off = self._above(lambda rows, cap, off: self._lib.blurrily_storage_find_references_above_each_in(
+                self._h, self._handles(scs), len(scs), which.ctypes.data if n else None,
+                refs.ctypes.data if n else None, n, mm, mp, rows, cap, off, ntri.ctypes.data), n)
+        return rows, row_off, ntri
+
+    def join_above_within(self, scopes, min_matches=0, min_permille=0):
+        """The blocked threshold self-join: every member of every scope with all the members of its own scope at or above
+        its bar, in one GPU batch.  Returns (refs[k] uint32, which[k] uint32: the scope of each, row_off[k + 1] uint64,
+        rows[R, 3] uint32) over the members the map holds, scope after scope."""
+        self._check_open()
+        with self._scopes_of(scopes) as scs:
+            parts = [sc._refs if sc._refs is not None else np.zeros(0, np.uint32) for sc in scs]
+            refs = np.concatenate(parts).astype(np.uint32) if parts else np.zeros(0, np.uint32)
+            which = np.repeat(np.arange(len(parts), dtype=np.uint32), [len(p) for p in parts])
+            rows, row_off, ntri = self.find_batch_by_reference_above_each_in(scs, which, refs, min_matches, min_permille)
+        held = np.nonzero(ntri)[0]                       # (a reference the map does not hold has no rows: nothing to cut)
+        off = np.zeros(len(held) + 1, dtype=np.uint64)
+        off[1:] = np.cumsum(np.diff(row_off.astype(np.int64))[held])
+        return refs[held], which[held], off, rows
+
     # -- clusters (no reference counterpart): connected components of the similarity self-join ----------------------
     def cluster(self, references, min_permille):
         """Single-linkage clusters of the stored references under "J >= min_permille / 1000" (blurrily_storage_cluster).
@@ -1000,6 +1070,25 @@ class Map(RawMap):
         """``[self.find_above(s, min_matches, min_permille) for s in needles]`` in one GPU batch."""
         rows, row_off = super().find_batch_above_packed(*_normalised(needles), min_matches, min_permille)
         return [rows[lo:hi].tolist() for lo, hi in zip(row_off[:-1].tolist(), row_off[1:].tolist())]
+
+    def find_above_in(self, scope, needle, min_matches=0, min_permille=0):
+        """``find_above`` among the references of `scope` (a ``Scope`` or an iterable of references) only."""
+        return super().find_above_in(scope, normalize_string(needle), min_matches, min_permille)
+
+    def find_batch_above_in(self, scope, needles, min_matches=0, min_permille=0):
+        """``[self.find_above_in(scope, s, min_matches, min_permille) for s in needles]`` in one GPU batch."""
+        rows, row_off = super().find_batch_above_in_packed(scope, *_normalised(needles), min_matches, min_permille)
+        return [rows[lo:hi].tolist() for lo, hi in zip(row_off[:-1].tolist(), row_off[1:].tolist())]
+
+    def find_batch_above_each_in(self, scopes, which, needles, min_matches=0, min_permille=0):
+        """``[self.find_above_in(scopes[w], s, ...) if w is not None else self.find_above(s, ...) for s, w in
+        zip(needles, which)]`` in one GPU batch."""
+        rows, row_off = super().find_batch_above_each_in(scopes, which, *_normalised(needles), min_matches,
+                                                         min_permille)
+        return [rows[lo:hi].tolist() for lo, hi in zip(row_off[:-1].tolist(), row_off[1:].tolist())]
+
+    def join_above_within(self, scopes, min_matches=0, min_permille=0):
+        return super().join_above_within(scopes, min_matches, min_permille)
 
     def find_similar(self, needle, limit=LIMIT_DEFAULT, min_permille=0):
         """The best rows of the normalised needle by trigram Jaccard similarity (``RawMap.find_similar``): a list of

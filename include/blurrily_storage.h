@@ -369,6 +369,43 @@ int blurrily_storage_find_references_similar_each_in(trigram_map haystack, const
                                                      uint32_t min_permille, trigram_match results, uint32_t* counts,
                                                      uint32_t* row_ntri, uint32_t* nb_trigrams);
 
+/* Scoped threshold find: the threshold find among a scope's members only.  A needle's rows are
+ * exactly the rows blurrily_storage_find_batch_above gives for it with the same min_matches and min_permille, in the
+ * same order, with every row removed whose reference is not a held member of the scope (a threshold find has no cut, so
+ * this is the unscoped call filtered -- without sweeping the map or moving its rows).  T, the bar t and the order are
+ * the threshold find's; membership is the scoped find's, read against the map as it is at each call (a deleted member is
+ * not found; one put after the scope was made is, pending or folded; one deleted and put again is found with its new
+ * trigrams; an empty scope, or one with no held member, gives no rows).  T == 0 or t > T: no rows.  results, capacity
+ * and row_off follow blurrily_storage_find_batch_above's protocol: row_off[n + 1] is filled on success and on ERANGE;
+ * results == NULL counts only; capacity < row_off[n] is -1 / ERANGE with results untouched.  With "devices" > 1 the
+ * primary device alone serves the call.
+ * 0, or -1 with errno.  EINVAL, before anything needs a GPU and with nothing written: a NULL map, a NULL scope or a
+ * scope of another map, which[i] >= n_scopes (other than BLURRILY_NO_SCOPE), n_scopes > 0 with scopes NULL, row_off
+ * NULL, needles (or which, or references) NULL with n > 0, n above the batch's cap, min_permille > 1000.  Valid
+ * arguments without a usable GPU: ENODEV. */
+int blurrily_storage_find_batch_above_in(trigram_map haystack, blurrily_scope scope, const char* packed,
+                                         const uint64_t* offsets, size_t n, uint32_t min_matches,
+                                         uint32_t min_permille, trigram_match results, uint64_t capacity,
+                                         uint64_t* row_off);
+/* One needle: the same with n == 1; *total (optional) = its row count, also on ERANGE. */
+int blurrily_storage_find_above_in(trigram_map haystack, blurrily_scope scope, const char* needle,
+                                   uint32_t min_matches, uint32_t min_permille, trigram_match results,
+                                   uint64_t capacity, uint64_t* total);
+/* A scope per needle: element i is the single-scope call on scopes[which[i]], or blurrily_storage_find_batch_above
+ * when which[i] == BLURRILY_NO_SCOPE. */
+int blurrily_storage_find_batch_above_each_in(trigram_map haystack, const blurrily_scope* scopes, size_t n_scopes,
+                                              const uint32_t* which, const char* packed, const uint64_t* offsets,
+                                              size_t n, uint32_t min_matches, uint32_t min_permille,
+                                              trigram_match results, uint64_t capacity, uint64_t* row_off);
+/* blurrily_storage_find_references_above with a scope per reference: an absent reference gets no rows and
+ * nb_trigrams[i] == 0 (nb_trigrams may be NULL); a held one that is a member of its own scope is among its own rows
+ * with matches == T. */
+int blurrily_storage_find_references_above_each_in(trigram_map haystack, const blurrily_scope* scopes,
+                                                   size_t n_scopes, const uint32_t* which,
+                                                   const uint32_t* references, size_t n, uint32_t min_matches,
+                                                   uint32_t min_permille, trigram_match results, uint64_t capacity,
+                                                   uint64_t* row_off, uint32_t* nb_trigrams);
+
 /* Clusters: connected components of the similarity self-join, computed on the device.  T, R, m
  * and J = m / (T + R - m) as for the similarity find; the map is read as find reads it.
  *   Nodes: the distinct references of the list that the map holds (a reference listed twice is one node).
