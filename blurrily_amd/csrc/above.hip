@@ -1,7 +1,7 @@
 // above.hip -- the threshold find's entry points (include/blurrily_storage.h).  They drive the
 // map's internals (map_internal.h: the mutation log, the device images, the string and by-reference front ends);
 // the kernels are above_kernels.hip's.  The find runs in two steps, above_count and above_emit (map_internal.h), which
-// the scoped threshold find (scope.hip; section 27) runs apart, with a scope's masks.
+// the scoped threshold find (scope_above.hip; section 27) runs apart, with a scope's masks.
 #include "above.h"
 #include "map_internal.h"
 
@@ -127,10 +127,8 @@ int above_run(trigram_map m, size_t n, const NeedleView& N, uint32_t min_matches
               trigram_match results, uint64_t capacity, uint64_t* row_off, hipStream_t stream, AboveScratch& S) {
   AboveCounted C;
   if (above_count(m, n, N, min_matches, min_permille, stream, nullptr, &C) < 0) return -1;
-  row_off[0] = 0;
-  for (size_t q = 0; q < n; ++q) row_off[q + 1] = row_off[q] + C.rows(q);
-  if (!results) return 0;
-  if (capacity < row_off[n]) { errno = ERANGE; return -1; }
+  const int go = above_row_off(n, [&](size_t q) { return C.rows(q); }, results, capacity, row_off);
+  if (go <= 0) return go;
   return above_emit(m, N, min_matches, min_permille, C, row_off, results, stream, S, nullptr);
 }
 

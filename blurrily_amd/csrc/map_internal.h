@@ -8,7 +8,8 @@
 //   host_batch.hip   host-buffer batches: needle_len, longest_needle, BatchBlocks; the chunked pipeline,
 //                    find_batch_host, find_few
 //   refs.hip         by reference: refs_extract, ExtractionOnHost, stage_reference_needles, get / find_references entries
-//   scope.hip        scoped find, a scope per needle, the scoped similarity and threshold finds
+//   scope.hip        scoped find, a scope per needle; behind scope_internal.h with scope_similar.hip and scope_above.hip,
+//                    the scoped similarity and threshold finds
 //   above.hip, similar.hip   the threshold and similarity finds (their shared sort: segsort.h)
 //   cluster.hip      connected components of the similarity self-join (similar.hip's per-rank trigram table)
 #pragma once
@@ -344,6 +345,19 @@ inline size_t above_chunk_end(const uint64_t* row_off, size_t n, size_t s) {
   size_t e = s + 1;
   while (e < n && e - s < kAboveChunkNeedles && row_off[e + 1] - row_off[s] <= kAboveChunkRows) ++e;
   return e;
+}
+// Offsets that add up each of n needles' (or jobs') rows: off[0 .. n].
+template <class Rows> void rows_to_offsets(size_t n, Rows rows, uint64_t* off) {
+  off[0] = 0;
+  for (size_t q = 0; q < n; ++q) off[q + 1] = off[q] + rows(q);
+}
+// Between a threshold call's two steps: row_off from each needle's counted rows, then whether it emits: 1, or 0 (no
+// results wanted: the counts were the call) or -1 (ERANGE: they do not fit the capacity; row_off stays laid out).
+template <class Rows> int above_row_off(size_t n, Rows rows, const void* results, uint64_t capacity, uint64_t* row_off) {
+  rows_to_offsets(n, rows, row_off);
+  if (!results) return 0;
+  if (capacity < row_off[n]) { errno = ERANGE; return -1; }
+  return 1;
 }
 // device scratch of one threshold call, freed on the way out (b[8], b[9]: the scoped calls' own)
 struct AboveScratch {

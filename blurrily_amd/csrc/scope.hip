@@ -1,39 +1,12 @@
 // scope.hip -- scoped find and a scope per needle (blurrily_scope_*, blurrily_storage_find_in / _find_batch_in[_device],
-// _find_batch_each_in[_device], _find_references_each_in; DESIGN.md sections 12 and 13) and the scoped similarity find
-// (blurrily_storage_find_batch_similar_in, _find_similar_in, _find_batch_similar_each_in,
-// _find_references_similar_each_in; section 24) and the scoped threshold find (blurrily_storage_find_batch_above_in,
-// _find_above_in, _find_batch_above_each_in, _find_references_above_each_in; section 27).
-#include "map_internal.h"
-#include "scope_above.h"
-#include "scope_similar.h"
+// _find_batch_each_in[_device], _find_references_each_in; DESIGN.md sections 12 and 13), and what the scoped similarity
+// and threshold finds (scope_similar.hip, scope_above.hip) share with them (scope_internal.h).
+#include "scope_internal.h"
 
 using namespace blurrily;
 using namespace blurrily::detail;
 
 // ---- scoped find (blurrily_scope_* / blurrily_storage_find_in / _find_batch_in[_device]) ---------
-// A scope keeps its references sorted and distinct.  Its device state is made at the first scoped find and whenever
-// the map has changed since (base_builds, log_version): the members are looked up and extracted as by reference
-// (refs_extract), a mask per image excludes every rank but the members held now, and -- for scopes the direct strategy
-// may serve -- the held members' codes, weights and references in (weight, reference) order are copied into the
-// scope's own buffers (ws_refs is every later by-reference call's).
-struct blurrily_scope_t {
-  trigram_map           map = nullptr;
-  std::vector<uint32_t> refs;           // sorted, distinct
-  bool         ready = false;
-  bool         mask_ready = false;       // (a scope prepared with others, by a scope-per-needle call, has no masks yet)
-  uint64_t     built_base = 0, built_log = 0;
-  uint32_t     n_held = 0;               // members held at the last preparation
-  DeviceBuffer d_refs, d_mask[2];        // masks: base image, delta image (pending puts)
-  bool         has_delta = false;
-  // direct form (n_direct members: m_off [n_direct + 1] | m_ref | m_weight | m_codes)
-  bool         direct = false;
-  uint32_t     n_direct = 0;
-  uint64_t     direct_codes = 0;
-  DeviceBuffer d_direct;
-  const uint32_t *m_off = nullptr, *m_ref = nullptr, *m_weight = nullptr;
-  const uint16_t* m_codes = nullptr;
-};
-
 namespace {
 
 constexpr size_t kScopePageBytes = size_t(1) << 16;   // small direct batches: needles in, rows out, through mapped memory
@@ -96,9 +69,38 @@ int scope_from_extraction(trigram_map m, blurrily_scope sc, ExtractionOnHost& R,
   return 0;
 }
 
-// The scope's device state for the map as it is now (the image brought up to date and tombstones applied first): the
-// direct form of this one scope, if it is stale, and its masks.
-int scope_prepare(trigram_map m, blurrily_scope sc, hipStream_t stream) {
+// The direct form and the held count of every scope in `stale` for the map as it is now: their members uploaded and
+// extracted as one list, read back once.  No masks: mask_ready stays false until scope_prepare builds them.
+int scopes_prepare_direct(trigram_map m, const std::vector<blurrily_scope>& stale, hipStream_t stream) {
+  if (stale.empty()) return 0;
+  size_t n = 0;
+  for (blurrily_scope sc : stale) {
+    n += sc->refs.size();
+    sc->ready = false; sc->mask_ready = false; sc->direct = false; sc->n_held = 0;
+  }
+  if (n > kMaxBatchNeedles) { errno = EINVAL; return -1; }
+  ExtractionOnHost R(n);
+  if (n) {
+    std::vector<uint32_t> refs;
+    refs.reserve(n);
+    for (blurrily_scope sc : stale) refs.insert(refs.end(), sc->refs.begin(), sc->refs.end());
+    if (m->ws_each.reserve(n * sizeof(uint32_t), stream) < 0) return -1;
+    BLURRILY_HIP_TRY(hipMemcpyAsync(m->ws_each.p, refs.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    RefExtract x;
+    if (refs_extract(m, static_cast<const uint32_t*>(m->ws_each.p), n, stream, &x) < 0) return -1;
+    if (R.enqueue_counts(x, stream) < 0 || R.read_codes(stream) < 0) return -1;   // (one readback, whatever the scopes hold)
+  }
+  size_t at = 0;
+  for (blurrily_scope sc : stale) {
+    if (scope_from_extraction(m, sc, R, at, stream) < 0) return -1;
+    at += sc->refs.size();
+  }
+  return 0;
+}
+
+}  // namespace
+
+int blurrily::detail::scope_prepare(trigram_map m, blurrily_scope sc, hipStream_t stream) {
   if (map_ready(m, stream) < 0) return -1;
   if (sc->ready && sc->mask_ready && sc->built_base == m->base_builds && sc->built_log == log_of(m)->log_version)
     return 0;
@@ -136,13 +138,12 @@ int scope_prepare(trigram_map m, blurrily_scope sc, hipStream_t stream) {
   return 0;
 }
 
-// Which strategy serves a scoped find of `limit` (the scope prepared): the direct one declines limits above its pool and
-// scopes without a direct form (above kScopeMaxMembers held members, or a member of more than 255 distinct trigrams);
-// auto takes it for scopes of at most "scope_direct_max" member codes.
-bool scope_takes_direct(const trigram_map_t* m, const blurrily_scope_t* sc, uint16_t limit) {
+bool blurrily::detail::scope_takes_direct(const trigram_map_t* m, const blurrily_scope_t* sc, uint16_t limit) {
   if (m->scope_strategy == 1 || !sc->direct || limit == 0 || limit > kScopeMaxKeep) return false;
   return m->scope_strategy == 2 || sc->direct_codes <= m->scope_direct_max;
 }
+
+namespace {
 
 // Enqueue a scoped find of n device-resident needles on the prepared scope: rows of only its members.
 int scope_run(trigram_map m, blurrily_scope sc, const char* d_packed, size_t packed_bytes, const uint64_t* d_offsets,
@@ -159,16 +160,13 @@ int scope_run(trigram_map m, blurrily_scope sc, const char* d_packed, size_t pac
       BLURRILY_HIP_TRY(hipMemsetAsync(d_counts, 0, n * sizeof(uint32_t), stream));
       return 0;
     }
-    ScopeFindArgs a{};
-    a.packed = d_packed; a.offsets = d_offsets; a.n = uint32_t(n);
-    a.m_off = sc->m_off; a.m_codes = sc->m_codes; a.m_ref = sc->m_ref; a.m_weight = sc->m_weight;
-    a.n_members = sc->n_direct; a.limit = limit; a.results = d_results; a.counts = d_counts;
+    const ScopeDirect d = direct_of(sc);
+    const ScopeFindArgs a{d_packed, d_offsets, uint32_t(n), d.m_off, d.m_codes, d.m_ref, d.m_weight, d.n_members, limit,
+                          d_results, d_counts};
     return launch_scope_find(a, stream);
   }
-  const ScopeMasks sm{static_cast<const uint32_t*>(sc->d_mask[0].p),
-                      sc->has_delta ? static_cast<const uint32_t*>(sc->d_mask[1].p) : nullptr};
   return run_find(m, d_packed, packed_bytes, d_offsets, n, limit, d_results, d_counts, nullptr, maybe_long, maybe_mid,
-                  stream, nullptr, &sm);
+                  stream, nullptr, masks_of(sc).ptr());
 }
 
 // The pinned page small direct batches go through (m->h_scope, mapped at m->d_scope), made at first use.
@@ -184,11 +182,6 @@ int scope_page(trigram_map m) {
     return -1;
   }
   m->h_scope = h; m->d_scope = d;
-  return 0;
-}
-
-int scope_check(trigram_map m, blurrily_scope sc) {
-  if (!m || !sc || sc->map != m) { errno = EINVAL; return -1; }
   return 0;
 }
 
@@ -295,65 +288,8 @@ int blurrily_storage_find_in(trigram_map m, blurrily_scope sc, const char* needl
 // group (unscoped); a scatter puts their rows back in the caller's order.  The stale scopes of a call are prepared
 // together (scopes_prepare_direct: one extraction of all their members, one readback); a scope's masks are built only
 // when a call serves it through them (scope_prepare).
-namespace {
-
-int each_check(trigram_map m, const blurrily_scope* scopes, size_t n_scopes) {
-  if (!m || (n_scopes && !scopes)) { errno = EINVAL; return -1; }
-  for (size_t j = 0; j < n_scopes; ++j)
-    if (!scopes[j] || scopes[j]->map != m) { errno = EINVAL; return -1; }
-  return 0;
-}
-
-int each_check_which(const uint32_t* which, size_t n, size_t n_scopes) {
-  for (size_t i = 0; i < n; ++i)
-    if (which[i] != BLURRILY_NO_SCOPE && which[i] >= n_scopes) { errno = EINVAL; return -1; }
-  return 0;
-}
-
-// The direct form and the held count of every scope in `stale` for the map as it is now: their members uploaded and
-// extracted as one list, read back once.  No masks: mask_ready stays false until scope_prepare builds them.
-int scopes_prepare_direct(trigram_map m, const std::vector<blurrily_scope>& stale, hipStream_t stream) {
-  if (stale.empty()) return 0;
-  size_t n = 0;
-  for (blurrily_scope sc : stale) {
-    n += sc->refs.size();
-    sc->ready = false; sc->mask_ready = false; sc->direct = false; sc->n_held = 0;
-  }
-  if (n > kMaxBatchNeedles) { errno = EINVAL; return -1; }
-  ExtractionOnHost R(n);
-  if (n) {
-    std::vector<uint32_t> refs;
-    refs.reserve(n);
-    for (blurrily_scope sc : stale) refs.insert(refs.end(), sc->refs.begin(), sc->refs.end());
-    if (m->ws_each.reserve(n * sizeof(uint32_t), stream) < 0) return -1;
-    BLURRILY_HIP_TRY(hipMemcpyAsync(m->ws_each.p, refs.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-    RefExtract x;
-    if (refs_extract(m, static_cast<const uint32_t*>(m->ws_each.p), n, stream, &x) < 0) return -1;
-    if (R.enqueue_counts(x, stream) < 0 || R.read_codes(stream) < 0) return -1;   // (one readback, whatever the scopes hold)
-  }
-  size_t at = 0;
-  for (blurrily_scope sc : stale) {
-    if (scope_from_extraction(m, sc, R, at, stream) < 0) return -1;
-    at += sc->refs.size();
-  }
-  return 0;
-}
-
-// Which launch serves each needle of a call.
-struct EachPlan {
-  std::vector<ScopeDirect>    table;         // the direct scopes' forms
-  std::vector<uint2>          order;         // the direct needles {needle, table slot}: largest scopes first
-  uint32_t                    max_members = 0;
-  std::vector<uint32_t>       idx;           // the swept groups' needles, group after group
-  std::vector<size_t>         group_start;   // [groups + 1]
-  std::vector<blurrily_scope> group_scope;   // nullptr: the NO_SCOPE group
-  bool                        any_empty = false;   // needles of a scope without rows (no held member, limit 0)
-};
-
-// Group the needles and prepare what serves them: the stale scopes together, then the masks of the scopes the mask
-// serves.  (Every extraction of the call happens here, before the by-reference needles take ws_refs.)
-int each_plan(trigram_map m, const blurrily_scope* scopes, size_t n_scopes, const uint32_t* which, size_t n,
-              uint16_t limit, hipStream_t stream, EachPlan* P) {
+int blurrily::detail::each_plan(trigram_map m, const blurrily_scope* scopes, size_t n_scopes, const uint32_t* which,
+                                size_t n, uint16_t limit, hipStream_t stream, EachPlan* P) {
   std::unordered_map<blurrily_scope, uint32_t> slot_of;    // the distinct scopes (a handle given twice is one)
   std::vector<blurrily_scope> uniq;
   std::vector<uint32_t> slot(n_scopes);
@@ -394,7 +330,7 @@ int each_plan(trigram_map m, const blurrily_scope* scopes, size_t n_scopes, cons
   for (uint32_t u : direct_u) {
     const blurrily_scope sc = uniq[u];
     dslot[u] = uint32_t(P->table.size());
-    P->table.push_back(ScopeDirect{sc->m_off, sc->m_codes, sc->m_ref, sc->m_weight, sc->n_direct, 0u});
+    P->table.push_back(direct_of(sc));
     P->max_members = std::max(P->max_members, sc->n_direct);
     cursor[u] = nd;
     nd += per[u];
@@ -417,20 +353,37 @@ int each_plan(trigram_map m, const blurrily_scope* scopes, size_t n_scopes, cons
   return 0;
 }
 
-// The needles of a call: strings on the device (h_offsets: the caller's offsets on the host, or nullptr: read back if
-// a swept group needs them) or references extracted by refs_extract (rn).
-struct EachNeedles {
-  const char*       d_packed = nullptr;
-  const uint64_t*   d_offsets = nullptr;
-  const uint64_t*   h_offsets = nullptr;
-  const RefNeedles* rn = nullptr;
-};
+int EachOnDevice::upload(trigram_map m, const EachPlan& P, const std::vector<uint64_t>* goff, size_t gpk_bytes,
+                         size_t n_desc, bool weights, hipStream_t stream) {
+  const size_t nd = P.order.size(), ng = P.idx.size();
+  size_t at = 0;
+  auto take = [&](size_t bytes) { const size_t here = at; at += align_up(std::max<size_t>(bytes, 8), 256); return here; };
+  const size_t o_tab = take(P.table.size() * sizeof(ScopeDirect)), o_ord = take(nd * sizeof(uint2));
+  const size_t o_idx = take(ng * 4), o_goff = goff ? take(goff->size() * 8) : 0, up = at;
+  const size_t o_gpk = goff ? take(gpk_bytes) : 0, o_gq = take(n_desc * 8), o_gn = take(n_desc * 4);
+  const size_t o_gw = weights ? take(n_desc * 4) : 0;
+  m->h_each.assign(up, 0);                               // (kept: the copy reads it after this returns)
+  unsigned char* h = m->h_each.data();
+  if (!P.table.empty()) std::memcpy(h + o_tab, P.table.data(), P.table.size() * sizeof(ScopeDirect));
+  if (nd) std::memcpy(h + o_ord, P.order.data(), nd * sizeof(uint2));
+  if (ng) std::memcpy(h + o_idx, P.idx.data(), ng * 4);
+  if (goff && !goff->empty()) std::memcpy(h + o_goff, goff->data(), goff->size() * 8);
+  if (m->ws_each.reserve(at, stream) < 0) return -1;
+  unsigned char* d = static_cast<unsigned char*>(m->ws_each.p);
+  BLURRILY_HIP_TRY(hipMemcpyAsync(d, h, up, hipMemcpyHostToDevice, stream));
+  d_table = reinterpret_cast<const ScopeDirect*>(d + o_tab); d_order = reinterpret_cast<const uint2*>(d + o_ord);
+  d_idx = reinterpret_cast<const uint32_t*>(d + o_idx); d_goff = reinterpret_cast<const uint64_t*>(d + o_goff);
+  d_gpk = reinterpret_cast<char*>(d + o_gpk); gq = reinterpret_cast<uint64_t*>(d + o_gq);
+  gn = reinterpret_cast<uint32_t*>(d + o_gn); gw = reinterpret_cast<uint32_t*>(d + o_gw);
+  return 0;
+}
+
+namespace {
 
 int each_launch_direct(const EachPlan& P, const EachNeedles& N, const ScopeDirect* d_table, const uint2* d_order,
                        uint16_t limit, trigram_match d_results, uint32_t* d_counts, hipStream_t stream) {
   ScopeEachArgs a{};
-  if (N.rn) { a.codes = N.rn->codes; a.qoff = N.rn->qoff; a.ntri = N.rn->ntri; }
-  else { a.packed = N.d_packed; a.offsets = N.d_offsets; }
+  N.into(a);
   a.order = d_order; a.n = uint32_t(P.order.size()); a.scopes = d_table; a.max_members = P.max_members;
   a.limit = limit; a.results = d_results; a.counts = d_counts;
   return launch_scope_each(a, stream);
@@ -458,54 +411,32 @@ int each_run(trigram_map m, const EachPlan& P, const EachNeedles& N, size_t n, u
     for (size_t k = 0; k < ng; ++k) goff[k + 1] = goff[k] + (off[P.idx[k] + 1] - off[P.idx[k]]);
   }
   // one upload (table | order | idx | compacted offsets), then the device's own: compacted strings or descriptors
-  size_t at = 0;
-  auto take = [&](size_t bytes) { const size_t here = at; at += align_up(std::max<size_t>(bytes, 8), 256); return here; };
-  const size_t o_tab = take(P.table.size() * sizeof(ScopeDirect)), o_ord = take(nd * sizeof(uint2));
-  const size_t o_idx = take(ng * 4), o_goff = take(goff.size() * 8), up = at;
-  const size_t o_gpk = take(goff.empty() ? 0 : goff[ng]), o_gq = take(N.rn ? ng * 8 : 0);
-  const size_t o_gn = take(N.rn ? ng * 4 : 0), o_gw = take(N.rn ? ng * 4 : 0);
-  m->h_each.assign(up, 0);
-  unsigned char* h = m->h_each.data();
-  if (!P.table.empty()) std::memcpy(h + o_tab, P.table.data(), P.table.size() * sizeof(ScopeDirect));
-  if (nd) std::memcpy(h + o_ord, P.order.data(), nd * sizeof(uint2));
-  if (ng) std::memcpy(h + o_idx, P.idx.data(), ng * 4);
-  if (!goff.empty()) std::memcpy(h + o_goff, goff.data(), goff.size() * 8);
-  if (m->ws_each.reserve(at, stream) < 0) return -1;
-  unsigned char* d = static_cast<unsigned char*>(m->ws_each.p);
-  BLURRILY_HIP_TRY(hipMemcpyAsync(d, h, up, hipMemcpyHostToDevice, stream));
+  EachOnDevice D;
+  if (D.upload(m, P, &goff, goff.empty() ? 0 : goff[ng], N.rn ? ng : 0, true, stream) < 0) return -1;
   // every needle served directly: one launch
   if (nd) {
     NameScope name_scope(&names);
-    if (each_launch_direct(P, N, reinterpret_cast<const ScopeDirect*>(d + o_tab), reinterpret_cast<const uint2*>(d + o_ord),
-                           limit, d_results, d_counts, stream) < 0)
-      return -1;
+    if (each_launch_direct(P, N, D.d_table, D.d_order, limit, d_results, d_counts, stream) < 0) return -1;
   }
   if (ng) {
-    const uint32_t* d_idx = reinterpret_cast<const uint32_t*>(d + o_idx);
     const size_t row_bytes = align_up(std::max<size_t>(ng * size_t(limit) * sizeof(trigram_match_t), 16), 256);
     if (m->ws_each_rows.reserve(row_bytes + ng * 4, stream) < 0) return -1;
     trigram_match g_rows = static_cast<trigram_match>(m->ws_each_rows.p);
     uint32_t* g_counts = reinterpret_cast<uint32_t*>(static_cast<unsigned char*>(m->ws_each_rows.p) + row_bytes);
-    const uint64_t* d_goff = reinterpret_cast<const uint64_t*>(d + o_goff);
-    char* d_gpk = reinterpret_cast<char*>(d + o_gpk);
-    if (!N.rn && launch_scope_gather_strings(N.d_packed, N.d_offsets, d_idx, d_goff, uint32_t(ng), d_gpk, stream) < 0)
+    if (!N.rn && launch_scope_gather_strings(N.d_packed, N.d_offsets, D.d_idx, D.d_goff, uint32_t(ng), D.d_gpk, stream) < 0)
       return -1;
-    for (size_t g = 0; g + 1 < P.group_start.size(); ++g) {
+    for (size_t g = 0; g < P.group_scope.size(); ++g) {
       const size_t k0 = P.group_start[g], cnt = P.group_start[g + 1] - k0;
-      const blurrily_scope sc = P.group_scope[g];
-      const ScopeMasks sm{sc ? static_cast<const uint32_t*>(sc->d_mask[0].p) : nullptr,
-                          sc && sc->has_delta ? static_cast<const uint32_t*>(sc->d_mask[1].p) : nullptr};
+      const ScopeMasksOf sm = masks_of(P.group_scope[g]);
       RefNeedles rg{};
       if (N.rn) {
-        uint64_t* gq = reinterpret_cast<uint64_t*>(d + o_gq) + k0;
-        uint32_t* gn = reinterpret_cast<uint32_t*>(d + o_gn) + k0;
-        uint32_t* gw = reinterpret_cast<uint32_t*>(d + o_gw) + k0;
-        if (launch_scope_gather_refs(*N.rn, d_idx + k0, uint32_t(cnt), gq, gn, gw, stream) < 0) return -1;
-        rg = RefNeedles{N.rn->codes, gq, gn, gw, uint32_t(cnt), N.rn->code_slots};
+        if (launch_scope_gather_refs(*N.rn, D.d_idx + k0, uint32_t(cnt), D.gq + k0, D.gn + k0, D.gw + k0, stream) < 0)
+          return -1;
+        rg = RefNeedles{N.rn->codes, D.gq + k0, D.gn + k0, D.gw + k0, uint32_t(cnt), N.rn->code_slots};
       }
-      if (run_find(m, N.rn ? nullptr : d_gpk, N.rn ? 0 : size_t(goff[ng]), N.rn ? nullptr : d_goff + k0, cnt, limit,
+      if (run_find(m, N.rn ? nullptr : D.d_gpk, N.rn ? 0 : size_t(goff[ng]), N.rn ? nullptr : D.d_goff + k0, cnt, limit,
                    g_rows + k0 * limit, g_counts + k0, nullptr, maybe_long, maybe_mid, stream, N.rn ? &rg : nullptr,
-                   sc ? &sm : nullptr) < 0)
+                   sm.ptr()) < 0)
         return -1;
       NameScope name_scope(&names);                      // (what that run noted in last_kernels, in launch order)
       for (size_t b = 0, e; b < m->last_kernels.size(); b = e + 1) {
@@ -514,7 +445,7 @@ int each_run(trigram_map m, const EachPlan& P, const EachNeedles& N, size_t n, u
         note_launch(m->last_kernels.substr(b, e - b).c_str());
       }
     }
-    if (launch_scope_scatter(g_rows, g_counts, d_idx, uint32_t(ng), limit, d_results, d_counts, stream) < 0) return -1;
+    if (launch_scope_scatter(g_rows, g_counts, D.d_idx, uint32_t(ng), limit, d_results, d_counts, stream) < 0) return -1;
   }
   m->last_kernels = names;
   return 0;
@@ -620,493 +551,9 @@ int blurrily_storage_find_references_each_in(trigram_map m, const blurrily_scope
   RefExtract x;                                          // (after every scope's preparation: both use ws_refs)
   if (refs_extract(m, static_cast<const uint32_t*>(m->ws_io_in.p), n, stream, &x) < 0) return -1;
   EachNeedles N;
-  N.rn = &x.needles;
+  N.rn = &x.needles; N.V = NeedleView{x.needles.codes, x.needles.qoff, x.needles.ntri};
   if (each_run(m, P, N, n, limit, out.rows, out.counts, true, true, stream) < 0) return -1;
   return B.copy_out(out.counts, x.needles.ntri, out.rows, counts, nb_trigrams, results, stream);   // (the counts of trigrams: the extraction's own)
-}
-
-}  // extern "C"
-
-// ---- scoped similarity find (blurrily_storage_find_batch_similar_in / _find_similar_in / _find_batch_similar_each_in /
-// _find_references_similar_each_in) ---------------------------------------------------------------
-// The similarity find's rows (section 15) among a scope's members only, the strategies chosen as the scoped find
-// chooses them: the similarity sweep with the scope's masks in the tombstone bitmaps' place (any scope, any limit), or
-// the members scored directly (scope_similar_kernels.hip).  The each-in entries group their needles with each_plan: the
-// direct ones in one launch, a sweep per masked scope and one for the NO_SCOPE group over their compacted needles; the
-// rows come back to the host per group and are put in the caller's order there.
-namespace {
-
-int similar_check(const uint32_t* counts, uint32_t min_permille, size_t n, uint16_t limit, const void* results,
-                  bool needles) {
-  if (!counts || min_permille > 1000 || (n && limit && !results) || (n && !needles) || n > kMaxBatchNeedles) {
-    errno = EINVAL;
-    return -1;
-  }
-  return 0;
-}
-
-// The direct launch's device output for nd workgroups (zeroed: a needle's rows past its count read 0, as the sweep's do).
-struct DirectOut {
-  trigram_match rows;
-  uint32_t *rntri, *counts;
-  size_t rows_bytes, rn_bytes;
-  int reserve(DeviceBuffer& b, size_t nd, uint16_t limit, hipStream_t stream) {
-    rows_bytes = align_up(std::max<size_t>(nd * limit * sizeof(trigram_match_t), 16), 256);
-    rn_bytes = align_up(std::max<size_t>(nd * limit * 4, 16), 256);
-    const size_t bytes = rows_bytes + rn_bytes + align_up(nd * 4, 256);
-    if (b.reserve(bytes, stream) < 0) return -1;
-    unsigned char* p = static_cast<unsigned char*>(b.p);
-    rows = reinterpret_cast<trigram_match>(p);
-    rntri = reinterpret_cast<uint32_t*>(p + rows_bytes);
-    counts = reinterpret_cast<uint32_t*>(p + rows_bytes + rn_bytes);
-    BLURRILY_HIP_TRY(hipMemsetAsync(p, 0, bytes, stream));
-    return 0;
-  }
-  // to host arrays of nd needles (waits for the stream)
-  int read(size_t nd, uint16_t limit, trigram_match h_rows, uint32_t* h_counts, uint32_t* h_rntri, hipStream_t stream) const {
-    BLURRILY_HIP_TRY(hipMemcpyAsync(h_counts, counts, nd * 4, hipMemcpyDeviceToHost, stream));
-    BLURRILY_HIP_TRY(hipMemcpyAsync(h_rows, rows, nd * limit * sizeof(trigram_match_t), hipMemcpyDeviceToHost, stream));
-    if (h_rntri) BLURRILY_HIP_TRY(hipMemcpyAsync(h_rntri, rntri, nd * limit * 4, hipMemcpyDeviceToHost, stream));
-    BLURRILY_HIP_TRY(hipStreamSynchronize(stream));
-    return 0;
-  }
-};
-
-// The planned each-in call.  strings: the needles on the device as strings (null for references); V: as code lists
-// (references always; strings when a group is swept).
-int similar_each_run(trigram_map m, const EachPlan& P, const char* d_packed, const uint64_t* d_offsets,
-                     const NeedleView* V, size_t n, uint16_t limit, uint32_t min_permille, trigram_match results,
-                     uint32_t* counts, uint32_t* row_ntri, SimilarScratch& S, hipStream_t stream) {
-  const size_t nd = P.order.size(), ng = P.idx.size();
-  if (P.any_empty) std::memset(counts, 0, n * 4);
-  std::vector<trigram_match_t> h_rows;
-  std::vector<uint32_t> h_counts, h_rntri;
-  auto put_back = [&](size_t k, uint32_t q) {           // group-local needle k is the caller's q
-    counts[q] = h_counts[k];
-    std::memcpy(results + size_t(q) * limit, h_rows.data() + k * limit, size_t(limit) * sizeof(trigram_match_t));
-    if (row_ntri) std::memcpy(row_ntri + size_t(q) * limit, h_rntri.data() + k * limit, size_t(limit) * 4);
-  };
-  auto host_room = [&](size_t k) {
-    h_rows.resize(k * limit); h_counts.resize(k);
-    if (row_ntri) h_rntri.resize(k * limit);
-  };
-  // one upload: scope table | order | idx
-  size_t at = 0;
-  auto take = [&](size_t bytes) { const size_t here = at; at += align_up(std::max<size_t>(bytes, 8), 256); return here; };
-  const size_t o_tab = take(P.table.size() * sizeof(ScopeDirect)), o_ord = take(nd * sizeof(uint2)), o_idx = take(ng * 4);
-  const size_t up = at, o_gq = take(ng * 8), o_gn = take(ng * 4);
-  m->h_each.assign(up, 0);
-  unsigned char* h = m->h_each.data();
-  if (!P.table.empty()) std::memcpy(h + o_tab, P.table.data(), P.table.size() * sizeof(ScopeDirect));
-  if (nd) std::memcpy(h + o_ord, P.order.data(), nd * sizeof(uint2));
-  if (ng) std::memcpy(h + o_idx, P.idx.data(), ng * 4);
-  if (m->ws_each.reserve(at, stream) < 0) return -1;
-  unsigned char* d = static_cast<unsigned char*>(m->ws_each.p);
-  BLURRILY_HIP_TRY(hipMemcpyAsync(d, h, up, hipMemcpyHostToDevice, stream));
-  // every needle served directly: one launch
-  if (nd) {
-    DirectOut out;
-    if (out.reserve(S.b[9], nd, limit, stream) < 0) return -1;
-    ScopeSimilarArgs a{};
-    if (d_packed) { a.packed = d_packed; a.offsets = d_offsets; }
-    else { a.codes = V->codes; a.qoff = V->qoff; a.ntri = V->ntri; }
-    a.order = reinterpret_cast<const uint2*>(d + o_ord); a.scopes = reinterpret_cast<const ScopeDirect*>(d + o_tab);
-    a.n = uint32_t(nd); a.max_members = P.max_members; a.limit = limit; a.min_permille = min_permille;
-    a.rows = out.rows; a.row_ntri = row_ntri ? out.rntri : nullptr; a.counts = out.counts;
-    if (launch_scope_similar(a, stream) < 0) return -1;
-    host_room(nd);
-    if (out.read(nd, limit, h_rows.data(), h_counts.data(), row_ntri ? h_rntri.data() : nullptr, stream) < 0) return -1;
-    for (size_t b = 0; b < nd; ++b) put_back(b, P.order[b].x);
-  }
-  // a sweep per group over its needles, compacted
-  const uint32_t* d_idx = reinterpret_cast<const uint32_t*>(d + o_idx);
-  for (size_t g = 0; g + 1 < P.group_start.size(); ++g) {
-    const size_t k0 = P.group_start[g], cnt = P.group_start[g + 1] - k0;
-    const blurrily_scope sc = P.group_scope[g];
-    const ScopeMasks sm{sc ? static_cast<const uint32_t*>(sc->d_mask[0].p) : nullptr,
-                        sc && sc->has_delta ? static_cast<const uint32_t*>(sc->d_mask[1].p) : nullptr};
-    uint64_t* gq = reinterpret_cast<uint64_t*>(d + o_gq) + k0;
-    uint32_t* gn = reinterpret_cast<uint32_t*>(d + o_gn) + k0;
-    if (launch_scope_similar_gather(V->qoff, V->ntri, d_idx + k0, uint32_t(cnt), gq, gn, stream) < 0) return -1;
-    host_room(cnt);
-    if (similar_run(m, cnt, NeedleView{V->codes, gq, gn}, limit, min_permille, h_rows.data(), h_counts.data(),
-                    row_ntri ? h_rntri.data() : nullptr, stream, S, sc ? &sm : nullptr) < 0)
-      return -1;
-    for (size_t k = 0; k < cnt; ++k) put_back(k, P.idx[k0 + k]);
-  }
-  return 0;
-}
-
-}  // namespace
-
-extern "C" {
-
-int blurrily_storage_find_batch_similar_in(trigram_map m, blurrily_scope sc, const char* packed, const uint64_t* offsets,
-                                           size_t n, uint16_t limit, uint32_t min_permille, trigram_match results,
-                                           uint32_t* counts, uint32_t* row_ntri) {
-  if (scope_check(m, sc) < 0 || similar_check(counts, min_permille, n, limit, results, packed && offsets) < 0) return -1;
-  DeviceScope scope(m->dev.device);
-  hipStream_t stream = nullptr;
-  if (scope_prepare(m, sc, stream) < 0) return -1;     // (without a GPU this is what fails, with ENODEV)
-  if (n == 0) return 0;
-  NameScope names(&m->last_kernels);
-  m->last_kernels.clear();
-  if (limit == 0 || sc->n_held == 0) { std::memset(counts, 0, n * 4); return 0; }
-  SimilarScratch S;
-  if (scope_takes_direct(m, sc, limit)) {
-    const BatchBlocks B(n, size_t(offsets[n]), 0, false);
-    if (S.b[8].reserve(B.in_bytes, stream) < 0) return -1;
-    unsigned char* d_in = static_cast<unsigned char*>(S.b[8].p);
-    if (B.copy_in(d_in, packed, offsets, stream) < 0) return -1;
-    DirectOut out;
-    if (out.reserve(S.b[9], n, limit, stream) < 0) return -1;
-    ScopeSimilarArgs a{};
-    a.packed = B.in(d_in).packed; a.offsets = B.in(d_in).offsets;
-    a.one = ScopeDirect{sc->m_off, sc->m_codes, sc->m_ref, sc->m_weight, sc->n_direct, 0u};
-    a.n = uint32_t(n); a.max_members = sc->n_direct; a.limit = limit; a.min_permille = min_permille;
-    a.rows = out.rows; a.row_ntri = row_ntri ? out.rntri : nullptr; a.counts = out.counts;
-    if (launch_scope_similar(a, stream) < 0) return -1;
-    return out.read(n, limit, results, counts, row_ntri, stream);
-  }
-  const ScopeMasks sm{static_cast<const uint32_t*>(sc->d_mask[0].p),
-                      sc->has_delta ? static_cast<const uint32_t*>(sc->d_mask[1].p) : nullptr};
-  NeedleView N;
-  if (stage_string_needles(m, packed, offsets, n, S.b[6], stream, &N) < 0) return -1;
-  return similar_run(m, n, N, limit, min_permille, results, counts, row_ntri, stream, S, &sm);
-}
-
-int blurrily_storage_find_similar_in(trigram_map m, blurrily_scope sc, const char* needle, uint16_t limit,
-                                     uint32_t min_permille, trigram_match results, uint32_t* row_ntri) {
-  if (!needle) { errno = EINVAL; return -1; }
-  const uint64_t offsets[2] = {0, std::strlen(needle)};
-  uint32_t count = 0;
-  if (blurrily_storage_find_batch_similar_in(m, sc, needle, offsets, 1, limit, min_permille, results, &count, row_ntri) < 0)
-    return -1;
-  return int(count);
-}
-
-int blurrily_storage_find_batch_similar_each_in(trigram_map m, const blurrily_scope* scopes, size_t n_scopes,
-                                                const uint32_t* which, const char* packed, const uint64_t* offsets,
-                                                size_t n, uint16_t limit, uint32_t min_permille, trigram_match results,
-                                                uint32_t* counts, uint32_t* row_ntri) {
-  if (each_check(m, scopes, n_scopes) < 0 ||
-      similar_check(counts, min_permille, n, limit, results, which && packed && offsets) < 0 ||
-      each_check_which(which, n, n_scopes) < 0)
-    return -1;
-  DeviceScope scope(m->dev.device);
-  hipStream_t stream = nullptr;
-  if (map_ready(m, stream) < 0) return -1;
-  if (n == 0) return 0;
-  m->last_kernels.clear();
-  if (limit == 0) { std::memset(counts, 0, n * 4); return 0; }
-  EachPlan P;
-  if (each_plan(m, scopes, n_scopes, which, n, limit, stream, &P) < 0) return -1;
-  NameScope names(&m->last_kernels);                     // (the scopes' preparation is no part of the find)
-  SimilarScratch S;
-  NeedleView V{};
-  const BatchBlocks B(n, size_t(offsets[n]), 0, false);
-  unsigned char* d_in = nullptr;
-  if (!P.idx.empty()) {                                  // a swept group: tokenised, the strings in front of the codes
-    if (stage_string_needles(m, packed, offsets, n, S.b[6], stream, &V) < 0) return -1;
-    d_in = static_cast<unsigned char*>(S.b[6].p);
-  } else if (!P.order.empty()) {
-    if (S.b[8].reserve(B.in_bytes, stream) < 0) return -1;
-    d_in = static_cast<unsigned char*>(S.b[8].p);
-    if (B.copy_in(d_in, packed, offsets, stream) < 0) return -1;
-  } else {
-    std::memset(counts, 0, n * 4);
-    return 0;
-  }
-  return similar_each_run(m, P, B.in(d_in).packed, B.in(d_in).offsets, &V, n, limit, min_permille, results, counts,
-                          row_ntri, S, stream);
-}
-
-int blurrily_storage_find_references_similar_each_in(trigram_map m, const blurrily_scope* scopes, size_t n_scopes,
-                                                     const uint32_t* which, const uint32_t* references, size_t n,
-                                                     uint16_t limit, uint32_t min_permille, trigram_match results,
-                                                     uint32_t* counts, uint32_t* row_ntri, uint32_t* nb_trigrams) {
-  if (each_check(m, scopes, n_scopes) < 0 ||
-      similar_check(counts, min_permille, n, limit, results, which && references) < 0 ||
-      each_check_which(which, n, n_scopes) < 0)
-    return -1;
-  DeviceScope scope(m->dev.device);
-  hipStream_t stream = nullptr;
-  if (map_ready(m, stream) < 0) return -1;
-  if (n == 0) return 0;
-  m->last_kernels.clear();
-  EachPlan P;
-  if (limit && each_plan(m, scopes, n_scopes, which, n, limit, stream, &P) < 0) return -1;
-  SimilarScratch S;
-  NeedleView V;                                          // (after every scope's preparation: both use ws_refs)
-  if (stage_reference_needles(m, references, n, S.b[6], stream, nb_trigrams, &V) < 0) return -1;
-  NameScope names(&m->last_kernels);                     // (the preparation and the extraction are no part of the find)
-  if (limit == 0 || (P.idx.empty() && P.order.empty())) { std::memset(counts, 0, n * 4); return 0; }
-  return similar_each_run(m, P, nullptr, nullptr, &V, n, limit, min_permille, results, counts, row_ntri, S, stream);
-}
-
-}  // extern "C"
-
-// ---- scoped threshold find (blurrily_storage_find_batch_above_in / _find_above_in / _find_batch_above_each_in /
-// _find_references_above_each_in) -----------------------------------------------------------------
-// The threshold find's rows (section 14) among a scope's members only, the strategies chosen as the scoped find chooses
-// them (there is no limit: scope_takes_direct and each_plan are asked with a limit of 1): the threshold sweep with the
-// scope's masks in the tombstone bitmaps' place (any scope), or the members scored directly and written in result order
-// by a counting sort (scope_above_kernels.hip).  Either way a call counts first -- every needle, whatever serves it --
-// lays out row_off in the caller's order, checks the capacity, and only then emits.  The each-in entries group their
-// needles with each_plan: the direct ones in one count launch and one emit launch a chunk, a sweep's count and emit per
-// masked scope and for the NO_SCOPE group over their compacted needles; the rows are put at the caller's row_off on the
-// host.
-namespace {
-
-int above_in_check(const uint64_t* row_off, uint32_t min_permille, size_t n, bool needles) {
-  if (!row_off || min_permille > 1000 || (n && !needles) || n > kMaxBatchNeedles) { errno = EINVAL; return -1; }
-  return 0;
-}
-
-// The direct launches' count step: cnt[j] = job j's rows (a.first, a.n, a.counts and a.seg are set here).
-int direct_above_count(ScopeAboveArgs a, size_t jobs, DeviceBuffer& d_counts, std::vector<uint32_t>& cnt, hipStream_t stream) {
-  if (d_counts.reserve(std::max<size_t>(jobs * 4, 16), stream) < 0) return -1;
-  a.counts = static_cast<uint32_t*>(d_counts.p);
-  a.seg = nullptr; a.rows = nullptr;
-  for (size_t s = 0; s < jobs; s += kAboveChunkNeedles) {
-    a.first = uint32_t(s); a.n = uint32_t(std::min(kAboveChunkNeedles, jobs - s));
-    if (launch_scope_above(a, stream) < 0) return -1;
-  }
-  cnt.resize(jobs);
-  BLURRILY_HIP_TRY(hipMemcpyAsync(cnt.data(), a.counts, jobs * 4, hipMemcpyDeviceToHost, stream));
-  BLURRILY_HIP_TRY(hipStreamSynchronize(stream));
-  return 0;
-}
-
-// ... and their emit step: job j's rows to results + off[j] (off: jobs + 1 offsets that add up cnt), in the threshold
-// find's chunks.  d_counts: what the count step left.
-int direct_above_emit(ScopeAboveArgs a, size_t jobs, const DeviceBuffer& d_counts, const std::vector<uint32_t>& cnt,
-                      const uint64_t* off, trigram_match results, AboveScratch& S, hipStream_t stream) {
-  a.counts = static_cast<uint32_t*>(d_counts.p);
-  std::vector<uint32_t> seg;
-  size_t s = 0;
-  while (s < jobs) {
-    const size_t e = above_chunk_end(off, jobs, s);
-    const size_t nc = e - s;
-    const uint64_t rows = off[e] - off[s];
-    if (rows == 0) { s = e; continue; }
-    if (rows > 0x7FFFFFFFull) { errno = ENOMEM; return -1; }
-    seg.resize(nc);
-    uint32_t at = 0;
-    for (size_t j = 0; j < nc; ++j) { seg[j] = at; at += cnt[s + j]; }
-    if (S.b[3].reserve(nc * 4, stream) < 0 || S.b[5].reserve(size_t(rows) * sizeof(trigram_match_t), stream) < 0) return -1;
-    BLURRILY_HIP_TRY(hipMemcpyAsync(S.b[3].p, seg.data(), nc * 4, hipMemcpyHostToDevice, stream));
-    a.first = uint32_t(s); a.n = uint32_t(nc);
-    a.seg = static_cast<const uint32_t*>(S.b[3].p);
-    a.rows = static_cast<trigram_match>(S.b[5].p);
-    if (launch_scope_above(a, stream) < 0) return -1;
-    BLURRILY_HIP_TRY(hipMemcpyAsync(results + off[s], a.rows, size_t(rows) * sizeof(trigram_match_t),
-                                    hipMemcpyDeviceToHost, stream));
-    BLURRILY_HIP_TRY(hipStreamSynchronize(stream));   // (seg and the rows' scratch are the next chunk's too)
-    s = e;
-  }
-  return 0;
-}
-
-void offsets_of(const std::vector<uint32_t>& cnt, std::vector<uint64_t>& off) {
-  off.resize(cnt.size() + 1);
-  off[0] = 0;
-  for (size_t j = 0; j < cnt.size(); ++j) off[j + 1] = off[j] + cnt[j];
-}
-
-// The planned each-in call.  d_packed / d_offsets: the needles on the device as strings (null for references); V: as
-// code lists (references always; strings when a group is swept).
-int above_each_run(trigram_map m, const EachPlan& P, const char* d_packed, const uint64_t* d_offsets, const NeedleView* V,
-                   size_t n, uint32_t min_matches, uint32_t min_permille, trigram_match results, uint64_t capacity,
-                   uint64_t* row_off, AboveScratch& S, hipStream_t stream) {
-  const size_t nd = P.order.size(), ng = P.idx.size(), groups = P.group_start.size() - 1;
-  // one upload: scope table | order | idx
-  size_t at = 0;
-  auto take = [&](size_t bytes) { const size_t here = at; at += align_up(std::max<size_t>(bytes, 8), 256); return here; };
-  const size_t o_tab = take(P.table.size() * sizeof(ScopeDirect)), o_ord = take(nd * sizeof(uint2)), o_idx = take(ng * 4);
-  const size_t up = at, o_gq = take(ng * 8), o_gn = take(ng * 4);
-  m->h_each.assign(up, 0);
-  unsigned char* h = m->h_each.data();
-  if (!P.table.empty()) std::memcpy(h + o_tab, P.table.data(), P.table.size() * sizeof(ScopeDirect));
-  if (nd) std::memcpy(h + o_ord, P.order.data(), nd * sizeof(uint2));
-  if (ng) std::memcpy(h + o_idx, P.idx.data(), ng * 4);
-  if (m->ws_each.reserve(at, stream) < 0) return -1;
-  unsigned char* d = static_cast<unsigned char*>(m->ws_each.p);
-  BLURRILY_HIP_TRY(hipMemcpyAsync(d, h, up, hipMemcpyHostToDevice, stream));
-
-  // 1. count: every needle served directly in one launch, a sweep per group over its needles, compacted
-  std::vector<uint64_t> rows_of(n, 0);
-  ScopeAboveArgs a{};
-  std::vector<uint32_t> d_cnt;
-  if (nd) {
-    if (d_packed) { a.packed = d_packed; a.offsets = d_offsets; }
-    else { a.codes = V->codes; a.qoff = V->qoff; a.ntri = V->ntri; }
-    a.order = reinterpret_cast<const uint2*>(d + o_ord); a.scopes = reinterpret_cast<const ScopeDirect*>(d + o_tab);
-    a.max_members = P.max_members; a.min_matches = min_matches; a.min_permille = min_permille;
-    if (direct_above_count(a, nd, S.b[8], d_cnt, stream) < 0) return -1;
-    for (size_t b = 0; b < nd; ++b) rows_of[P.order[b].x] = d_cnt[b];
-  }
-  const uint32_t* d_idx = reinterpret_cast<const uint32_t*>(d + o_idx);
-  std::vector<AboveCounted> C(groups);
-  std::vector<NeedleView> GV(groups);
-  for (size_t g = 0; g < groups; ++g) {
-    const size_t k0 = P.group_start[g], cnt = P.group_start[g + 1] - k0;
-    const blurrily_scope sc = P.group_scope[g];
-    const ScopeMasks sm{sc ? static_cast<const uint32_t*>(sc->d_mask[0].p) : nullptr,
-                        sc && sc->has_delta ? static_cast<const uint32_t*>(sc->d_mask[1].p) : nullptr};
-    uint64_t* gq = reinterpret_cast<uint64_t*>(d + o_gq) + k0;
-    uint32_t* gn = reinterpret_cast<uint32_t*>(d + o_gn) + k0;
-    if (launch_scope_similar_gather(V->qoff, V->ntri, d_idx + k0, uint32_t(cnt), gq, gn, stream) < 0) return -1;
-    GV[g] = NeedleView{V->codes, gq, gn};
-    if (above_count(m, cnt, GV[g], min_matches, min_permille, stream, sc ? &sm : nullptr, &C[g]) < 0) return -1;
-    for (size_t k = 0; k < cnt; ++k) rows_of[P.idx[k0 + k]] = C[g].rows(k);
-  }
-  row_off[0] = 0;
-  for (size_t q = 0; q < n; ++q) row_off[q + 1] = row_off[q] + rows_of[q];
-  if (!results) return 0;
-  if (capacity < row_off[n]) { errno = ERANGE; return -1; }
-
-  // 2. emit, launch by launch in its own order; each needle's rows then go where the caller's row_off has them
-  std::vector<trigram_match_t> part;
-  std::vector<uint64_t> off;
-  if (nd) {
-    offsets_of(d_cnt, off);
-    part.resize(size_t(off[nd]));
-    if (off[nd] && direct_above_emit(a, nd, S.b[8], d_cnt, off.data(), part.data(), S, stream) < 0) return -1;
-    for (size_t b = 0; b < nd; ++b)
-      if (d_cnt[b]) std::memcpy(results + row_off[P.order[b].x], part.data() + off[b], size_t(d_cnt[b]) * sizeof(trigram_match_t));
-  }
-  for (size_t g = 0; g < groups; ++g) {
-    const size_t k0 = P.group_start[g], cnt = P.group_start[g + 1] - k0;
-    const blurrily_scope sc = P.group_scope[g];
-    const ScopeMasks sm{sc ? static_cast<const uint32_t*>(sc->d_mask[0].p) : nullptr,
-                        sc && sc->has_delta ? static_cast<const uint32_t*>(sc->d_mask[1].p) : nullptr};
-    off.resize(cnt + 1);
-    off[0] = 0;
-    for (size_t k = 0; k < cnt; ++k) off[k + 1] = off[k] + C[g].rows(k);
-    if (off[cnt] == 0) continue;
-    part.resize(size_t(off[cnt]));
-    if (above_emit(m, GV[g], min_matches, min_permille, C[g], off.data(), part.data(), stream, S, sc ? &sm : nullptr) < 0)
-      return -1;
-    for (size_t k = 0; k < cnt; ++k)
-      if (off[k + 1] > off[k])
-        std::memcpy(results + row_off[P.idx[k0 + k]], part.data() + off[k], size_t(off[k + 1] - off[k]) * sizeof(trigram_match_t));
-  }
-  return 0;
-}
-
-}  // namespace
-
-extern "C" {
-
-int blurrily_storage_find_batch_above_in(trigram_map m, blurrily_scope sc, const char* packed, const uint64_t* offsets,
-                                         size_t n, uint32_t min_matches, uint32_t min_permille, trigram_match results,
-                                         uint64_t capacity, uint64_t* row_off) {
-  if (scope_check(m, sc) < 0 || above_in_check(row_off, min_permille, n, packed && offsets) < 0) return -1;
-  DeviceScope scope(m->dev.device);
-  hipStream_t stream = nullptr;
-  if (scope_prepare(m, sc, stream) < 0) return -1;     // (without a GPU this is what fails, with ENODEV)
-  NameScope names(&m->last_kernels);
-  m->last_kernels.clear();
-  row_off[0] = 0;
-  if (n == 0) return 0;
-  if (sc->n_held == 0) { std::fill(row_off, row_off + n + 1, uint64_t(0)); return 0; }
-  AboveScratch S;
-  if (scope_takes_direct(m, sc, 1)) {
-    const BatchBlocks B(n, size_t(offsets[n]), 0, false);
-    if (S.b[9].reserve(B.in_bytes, stream) < 0) return -1;
-    unsigned char* d_in = static_cast<unsigned char*>(S.b[9].p);
-    if (B.copy_in(d_in, packed, offsets, stream) < 0) return -1;
-    ScopeAboveArgs a{};
-    a.packed = B.in(d_in).packed; a.offsets = B.in(d_in).offsets;
-    a.one = ScopeDirect{sc->m_off, sc->m_codes, sc->m_ref, sc->m_weight, sc->n_direct, 0u};
-    a.max_members = sc->n_direct; a.min_matches = min_matches; a.min_permille = min_permille;
-    std::vector<uint32_t> cnt;
-    if (direct_above_count(a, n, S.b[8], cnt, stream) < 0) return -1;
-    for (size_t q = 0; q < n; ++q) row_off[q + 1] = row_off[q] + cnt[q];
-    if (!results) return 0;
-    if (capacity < row_off[n]) { errno = ERANGE; return -1; }
-    return direct_above_emit(a, n, S.b[8], cnt, row_off, results, S, stream);
-  }
-  const ScopeMasks sm{static_cast<const uint32_t*>(sc->d_mask[0].p),
-                      sc->has_delta ? static_cast<const uint32_t*>(sc->d_mask[1].p) : nullptr};
-  NeedleView N;
-  if (stage_string_needles(m, packed, offsets, n, S.b[6], stream, &N) < 0) return -1;
-  AboveCounted C;
-  if (above_count(m, n, N, min_matches, min_permille, stream, &sm, &C) < 0) return -1;
-  for (size_t q = 0; q < n; ++q) row_off[q + 1] = row_off[q] + C.rows(q);
-  if (!results) return 0;
-  if (capacity < row_off[n]) { errno = ERANGE; return -1; }
-  return above_emit(m, N, min_matches, min_permille, C, row_off, results, stream, S, &sm);
-}
-
-int blurrily_storage_find_above_in(trigram_map m, blurrily_scope sc, const char* needle, uint32_t min_matches,
-                                   uint32_t min_permille, trigram_match results, uint64_t capacity, uint64_t* total) {
-  if (!needle) { errno = EINVAL; return -1; }
-  const uint64_t offsets[2] = {0, std::strlen(needle)};
-  uint64_t row_off[2] = {0, 0};
-  const int res = blurrily_storage_find_batch_above_in(m, sc, needle, offsets, 1, min_matches, min_permille, results,
-                                                       capacity, row_off);
-  if (total && (res == 0 || errno == ERANGE)) *total = row_off[1];
-  return res;
-}
-
-int blurrily_storage_find_batch_above_each_in(trigram_map m, const blurrily_scope* scopes, size_t n_scopes,
-                                              const uint32_t* which, const char* packed, const uint64_t* offsets,
-                                              size_t n, uint32_t min_matches, uint32_t min_permille,
-                                              trigram_match results, uint64_t capacity, uint64_t* row_off) {
-  if (each_check(m, scopes, n_scopes) < 0 || above_in_check(row_off, min_permille, n, which && packed && offsets) < 0 ||
-      each_check_which(which, n, n_scopes) < 0)
-    return -1;
-  DeviceScope scope(m->dev.device);
-  hipStream_t stream = nullptr;
-  if (map_ready(m, stream) < 0) return -1;
-  m->last_kernels.clear();
-  row_off[0] = 0;
-  if (n == 0) return 0;
-  EachPlan P;
-  if (each_plan(m, scopes, n_scopes, which, n, 1, stream, &P) < 0) return -1;
-  NameScope names(&m->last_kernels);                     // (the scopes' preparation is no part of the find)
-  AboveScratch S;
-  NeedleView V{};
-  const BatchBlocks B(n, size_t(offsets[n]), 0, false);
-  unsigned char* d_in = nullptr;
-  if (!P.idx.empty()) {                                  // a swept group: tokenised, the strings in front of the codes
-    if (stage_string_needles(m, packed, offsets, n, S.b[6], stream, &V) < 0) return -1;
-    d_in = static_cast<unsigned char*>(S.b[6].p);
-  } else if (!P.order.empty()) {
-    if (S.b[9].reserve(B.in_bytes, stream) < 0) return -1;
-    d_in = static_cast<unsigned char*>(S.b[9].p);
-    if (B.copy_in(d_in, packed, offsets, stream) < 0) return -1;
-  } else {
-    std::fill(row_off, row_off + n + 1, uint64_t(0));
-    return 0;
-  }
-  return above_each_run(m, P, B.in(d_in).packed, B.in(d_in).offsets, &V, n, min_matches, min_permille, results, capacity,
-                        row_off, S, stream);
-}
-
-int blurrily_storage_find_references_above_each_in(trigram_map m, const blurrily_scope* scopes, size_t n_scopes,
-                                                   const uint32_t* which, const uint32_t* references, size_t n,
-                                                   uint32_t min_matches, uint32_t min_permille, trigram_match results,
-                                                   uint64_t capacity, uint64_t* row_off, uint32_t* nb_trigrams) {
-  if (each_check(m, scopes, n_scopes) < 0 || above_in_check(row_off, min_permille, n, which && references) < 0 ||
-      each_check_which(which, n, n_scopes) < 0)
-    return -1;
-  DeviceScope scope(m->dev.device);
-  hipStream_t stream = nullptr;
-  if (map_ready(m, stream) < 0) return -1;
-  m->last_kernels.clear();
-  row_off[0] = 0;
-  if (n == 0) return 0;
-  EachPlan P;
-  if (each_plan(m, scopes, n_scopes, which, n, 1, stream, &P) < 0) return -1;
-  AboveScratch S;
-  NeedleView V;                                          // (after every scope's preparation: both use ws_refs)
-  if (stage_reference_needles(m, references, n, S.b[6], stream, nb_trigrams, &V) < 0) return -1;
-  NameScope names(&m->last_kernels);                     // (the preparation and the extraction are no part of the find)
-  if (P.idx.empty() && P.order.empty()) { std::fill(row_off, row_off + n + 1, uint64_t(0)); return 0; }
-  return above_each_run(m, P, nullptr, nullptr, &V, n, min_matches, min_permille, results, capacity, row_off, S, stream);
 }
 
 }  // extern "C"

@@ -1,4 +1,5 @@
-// scope_above_kernels.hip -- the scoped threshold find's direct strategy (launch code: scope.hip).
+// scope_above_kernels.hip -- the scoped threshold find's direct strategy (launch code:
+// scope_above.hip).
 //
 // scope_above_kernel / scope_above_each_kernel: one workgroup of 256 lanes per needle over a scope's direct form (the
 // held members' code lists in (weight, reference) order).  The needle's code set goes into an LDS bitmap, from its

@@ -1,5 +1,5 @@
 // scope_similar_kernels.hip -- the scoped similarity find's direct strategy (launch code:
-// scope.hip).
+// scope_similar.hip).
 //
 // scope_similar_kernel / scope_similar_each_kernel: one workgroup of 256 lanes per needle over a scope's direct form
 // (the held members' code lists in (weight, reference) order).  The needle's code set goes into an LDS bitmap, from its

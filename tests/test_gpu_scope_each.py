@@ -311,6 +311,52 @@ def test_mutations_between_calls_prepare_stale_scopes_again():
     m.close()
 
 
+def test_a_small_plan_with_pending_puts_by_strings_and_by_reference_in_every_shape():
+    """ the each-in's plan upload and needle carrier with the delta masks live: 300 references and
+    five pending puts, a scope of three members, one holding a member of 256 trigrams (it declines direct), one of unheld
+    references, an unscoped needle -- as a plan of both kinds with the empty scope and NO_SCOPE in the call, of swept
+    groups only (the mask forced) and of direct needles only (24 needles at limit 256: past the pinned page)."""
+    rng = np.random.default_rng(71)
+    strings = W.unpack(*W.geonames(300, 60, 19)) + [_exact(rng, np.frombuffer(b"abcdefghijklmnopqrstuvwxyz", np.uint8), 256)]
+    n = len(strings)
+    m, t = RawMap(), Truth()
+    _put(m, t, strings, np.arange(1, n + 1, dtype=np.uint32), rng.integers(1, 50, size=n).astype(np.uint32))
+    m.sync_device()
+    family = [np.array([3, 4, n + 1], np.uint32), np.array([n, 10, 11, 12, n + 2], np.uint32),
+              np.arange(10 ** 6, 10 ** 6 + 4, dtype=np.uint32)]    # three members; the 256-trigram member; unheld
+    scopes = [m.scope(f) for f in family]
+    for k in range(5):                                     # pending: n + 1 in `three`, n + 2 in `wide`, three in neither
+        m.put(strings[k] + b" late", n + 1 + k, 2)
+        t.put(strings[k] + b" late", n + 1 + k, 2)
+    needles = [strings[0], strings[1], strings[2], strings[2], strings[3], strings[9], strings[n - 1], strings[2]] * 3
+    by = [3, n + 1, n, 10, n + 3, n + 3, 10 ** 6, 4] * 3
+    both, direct_only = [0, 1, 0, 1, NO, 1, 2, NO] * 3, [0] * 24
+    # (a pending put outside both scopes matches needles asked within them: only the delta mask keeps it out)
+    assert n + 3 in [r[0] for r in Truth.rows(t.members(None), strings[2], 256)]
+    packed, offsets = _pack(needles)
+    buf = np.frombuffer(packed, dtype=np.uint8)
+    try:
+        for strategy, which, each in ((0, both, True), (1, both, False), (0, direct_only, True)):
+            m.set_option("scope_strategy", strategy)
+            for limit in (10, 256):
+                got = _as_lists(*m.find_batch_each_in(scopes, which, buf, offsets, limit))
+                names = m.last_kernels()
+                assert names == ["scope_each_kernel"] if which is direct_only else \
+                    ("scope_each_kernel" in names) == each and len(names) > each, (strategy, names)
+                assert got == _expect(t, family, which, needles, limit), (strategy, limit)
+                rows, counts, ntri = m.find_batch_by_reference_each_in(scopes, which, by, limit)
+                codes = [Oracle.tokenise(t.entries[r][0]) if r in t.entries else None for r in by]
+                assert ntri.tolist() == [len(c) if c is not None else 0 for c in codes]
+                assert _as_lists(rows, counts) == [
+                    [] if c is None else Truth.rows(t.members(None if w is None else family[w]), b"", limit, c)
+                    for c, w in zip(codes, which)], (strategy, limit)
+    finally:
+        m.set_option("scope_strategy", 0)
+        for sc in scopes:
+            sc.close()
+        m.close()
+
+
 def test_the_device_form_equals_the_host_form_on_another_stream(geo):
     import torch
     m, t, strings, refs = geo

@@ -1,4 +1,4 @@
-"""Scoped similarity find on the GPU (scope.hip, scope_similar_kernels.hip: scope_similar_kernel /
+"""Scoped similarity find on the GPU (scope_similar.hip, scope_similar_kernels.hip: scope_similar_kernel /
 scope_similar_each_kernel; the mask strategy through similar.hip's sweep): rows, counts and row_ntri equal the
 restatement of tests/scope_similar_truth.py exactly -- every reference passing the row test, ranked, the rows outside
 the scope's live set removed, cut at the limit -- with each strategy forced, at the workgroup's stride and the
@@ -357,6 +357,49 @@ def test_a_scope_per_needle_equals_the_single_scope_calls_and_the_truth(case):
         m.set_option("scope_strategy", 0)
         for sc in scopes:
             sc.close()
+
+
+def test_a_small_plan_with_pending_puts_by_strings_and_by_reference_in_every_shape():
+    """ the each-in's plan upload, swept-group description and needle carrier with the delta
+    masks live: 300 references and five pending puts, a scope of three members, one holding a member of 256 trigrams
+    (it declines direct), one of unheld references, an unscoped needle -- as a plan of both kinds with the empty scope
+    and NO_SCOPE in the call, of swept groups only (the mask forced) and of direct needles only."""
+    rng = np.random.default_rng(71)
+    strings = W.unpack(*W.geonames(300, 60, 19)) + [_needle_of(rng, 256)]
+    n = len(strings)
+    m, t = RawMap(), ScopedTruth()
+    _put(m, t, strings, np.arange(1, n + 1, dtype=np.uint32), rng.integers(1, 50, size=n).astype(np.uint32))
+    m.sync_device()
+    family = [np.array([3, 4, n + 1], np.uint32), np.array([n, 10, 11, 12, n + 2], np.uint32),
+              np.arange(10 ** 6, 10 ** 6 + 4, dtype=np.uint32)]    # three members; the 256-trigram member; unheld
+    scopes = [m.scope(f) for f in family]
+    for k in range(5):                                     # pending: n + 1 in `three`, n + 2 in `wide`, three in neither
+        m.put(strings[k] + b" late", n + 1 + k, 2)
+        t.put(strings[k] + b" late", n + 1 + k, 2)
+    needles = [strings[0], strings[1], strings[2], strings[2], strings[3], strings[9], strings[n - 1], strings[2]]
+    by = [3, n + 1, n, 10, n + 3, n + 3, 10 ** 6, 4]
+    both, direct_only = [0, 1, 0, 1, None, 1, 2, None], [0] * 8
+    # (a pending put outside both scopes matches needles asked within them: only the delta mask keeps it out)
+    assert n + 3 in [r[0] for r in t.rows(strings[2], None, 1000, 0)] and n + 3 not in family[0] and n + 3 not in family[1]
+    try:
+        for strategy, which, each, sweep in ((0, both, True, True), (1, both, False, True), (0, direct_only, True, False)):
+            m.set_option("scope_strategy", strategy)
+            for limit, p in ((10, 0), (3, 300)):
+                got = _each(m, scopes, which, needles, limit, p)
+                names = m.last_kernels()
+                assert (EACH in names) == each and (SWEEP in names) == sweep, (strategy, names)
+                assert got == [t.rows(s, None if w is None else family[w], limit, p) for s, w in zip(needles, which)]
+                rows, counts, rntri, nb = m.find_batch_by_reference_similar_each_in(scopes, which, by, limit, p)
+                names = m.last_kernels()
+                assert (EACH in names) == each and (SWEEP in names) == sweep, (strategy, names)
+                assert _got(rows, counts, rntri) == [t.by_reference(r, None if w is None else family[w], limit, p)
+                                                     for r, w in zip(by, which)], (strategy, limit, p)
+                assert nb.tolist() == [len(Oracle.tokenise(t.entries[r][0])) if r in t.entries else 0 for r in by]
+    finally:
+        m.set_option("scope_strategy", 0)
+        for sc in scopes:
+            sc.close()
+        m.close()
 
 
 def test_join_similar_within_over_three_blocks(case):
