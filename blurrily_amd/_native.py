@@ -149,6 +149,9 @@ _ENTRIES = {
     "blurrily_storage_cluster_extend": (C.c_int, [_vp, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
                                                   C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32),
                                                   C.POINTER(C.c_uint64)]),
+    # clusters within caller-given blocks: an edge needs both ends under one block key
+    "blurrily_storage_cluster_within": (C.c_int, [_vp, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p,
+                                                  C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
 }
 EXPORTED_SYMBOLS = tuple(_ENTRIES)
 

@@ -192,4 +192,41 @@ struct ClusterExtendSweepArgs {
 };
 int launch_cluster_extend_sweep(const ClusterExtendSweepArgs& a, hipStream_t stream);
 
+// Clusters within blocks (cluster_within_kernels.hip): an edge needs both ends under one block key,
+// block_of[u] for number u.  A block is served by one of two kernels, both uniting in the one forest.
+// The direct kernel reads no image: a tile is up to kClusterWithinTile consecutive places of `order` (the numbers
+// sorted by (key, number)) inside one block, and its workgroup scores the tile's needles against the block's members
+// in front of the tile's last place, from the extraction's codes alone.  An edge is found from its end at the higher
+// place only.
+constexpr uint32_t kClusterWithinTile = 16;
+struct ClusterWithinTile {
+  uint32_t begin;                // the block's first place in `order`
+  uint32_t first;                // the tile's first place
+  uint32_t count;                // its places: 1 .. kClusterWithinTile, all of one block
+};
+struct ClusterWithinArgs {
+  const ClusterWithinTile* tiles;   // [n_tiles]
+  const uint32_t* order;         // [n_order] numbers, block after block, ascending inside a block
+  uint32_t        n_tiles;
+  uint32_t        n_order;
+  const uint16_t* qcodes;        // the extraction's (number u's q_ntri[u] distinct codes at qcodes + qoff[u] + u)
+  const uint64_t* qoff;
+  const uint32_t* q_ntri;        // (0: the map does not hold it, no node)
+  uint32_t        n_nodes;
+  uint32_t        min_permille;
+  uint32_t*       parent;
+  ClusterTotals*  totals;
+};
+int launch_cluster_within(const ClusterWithinArgs& a, hipStream_t stream);
+
+// cluster_sweep_kernel's sweep for the blocks too large to score directly: needle b / tasks of the launch is number
+// needles[s.q_base + b / tasks], it sweeps the windows in front of its own position as cluster_sweep_kernel does, and a
+// candidate node under another key than the needle's is passed over before it is counted.
+struct ClusterWithinSweepArgs {
+  ClusterSweepArgs s;            // (s.q_base and s.n count in needles)
+  const uint32_t*  needles;      // the swept blocks' numbers
+  const uint32_t*  block_of;     // [n_nodes] each number's key
+};
+int launch_cluster_within_sweep(const ClusterWithinSweepArgs& a, hipStream_t stream);
+
 }  // namespace blurrily

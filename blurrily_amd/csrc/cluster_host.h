@@ -1,5 +1,5 @@
 // cluster_host.h -- the host-side call sequence the clustering entries share (cluster.hip, cluster_levels.hip,
-// cluster_centres.hip, cluster_cores.hip, cluster_extend.hip): the node numbering and
+// cluster_centres.hip, cluster_cores.hip, cluster_extend.hip, cluster_within.hip): the node numbering and
 // ClusterCall, which owns a call's device scratch, runs what every entry does in front of its sweeps, fills the sweeps'
 // common arguments per image and chunk, and reads the totals back.  The device code is each entry's own.
 #pragma once
@@ -31,6 +31,27 @@ inline void number_nodes(const uint32_t* references, size_t n, std::vector<uint3
   }
 }
 
+// The same numbering for references that carry a key each (blurrily_storage_cluster_within's blocks): key_of[u] is number
+// u's.  False, with nothing to rely on in the outputs: a reference is listed more than once under different keys.  A
+// strictly ascending list names every reference once, so it cannot be, and is its own numbering as above.
+inline bool number_nodes_keyed(const uint32_t* references, const uint32_t* keys, size_t n, std::vector<uint32_t>& uniq,
+                               std::vector<uint32_t>& inv, std::vector<uint32_t>& key_of) {
+  bool ascending = true;
+  for (size_t i = 1; i < n && ascending; ++i) ascending = references[i - 1] < references[i];
+  if (ascending) { uniq.assign(references, references + n); key_of.assign(keys, keys + n); return true; }
+  std::vector<uint64_t> keyed(n);
+  for (size_t i = 0; i < n; ++i) keyed[i] = (uint64_t(references[i]) << 32) | i;
+  std::sort(keyed.begin(), keyed.end());
+  inv.resize(n);
+  for (size_t i = 0; i < n; ++i) {
+    const uint32_t ref = uint32_t(keyed[i] >> 32), key = keys[uint32_t(keyed[i])];
+    if (uniq.empty() || uniq.back() != ref) { uniq.push_back(ref); key_of.push_back(key); }
+    else if (key_of.back() != key) return false;
+    inv[uint32_t(keyed[i])] = uint32_t(uniq.size() - 1);
+  }
+  return true;
+}
+
 // One call of a clustering entry, from the entry's checks to its return.
 struct ClusterCall {
   ClusterCall(trigram_map m, hipStream_t stream) : m(m), stream(stream) {}
@@ -51,6 +72,10 @@ struct ClusterCall {
   // as many rows of n labels, totals_bytes of zeroed totals -- the uploads, the extraction, the images with their
   // per-rank tables, and the node tables: node_of_pos once, parent + k * nu per forest.
   int begin(const uint32_t* references, size_t n, uint32_t forests, size_t totals_bytes);
+  // ... with a numbering the entry made itself, before it asked for a GPU (number_nodes' or number_nodes_keyed's
+  // uniq and inv of n elements; both are taken over)
+  int begin(std::vector<uint32_t>&& numbering, std::vector<uint32_t>&& element_number, size_t n, uint32_t forests,
+            size_t totals_bytes);
 
   // `needles` needles (of the numbering, or of an entry's own list) over every image, in chunks: the sweep arguments
   // all entries share, handed to launch(const ClusterSweepArgs&), which adds the entry's own and launches.

@@ -17,8 +17,16 @@ int ClusterCall::alloc(void** p, size_t bytes, bool zeroed) {
 }
 
 int ClusterCall::begin(const uint32_t* references, size_t n_listed, uint32_t n_forests, size_t n_totals_bytes) {
+  std::vector<uint32_t> numbering, element_number;
+  number_nodes(references, n_listed, numbering, element_number);
+  return begin(std::move(numbering), std::move(element_number), n_listed, n_forests, n_totals_bytes);
+}
+
+int ClusterCall::begin(std::vector<uint32_t>&& numbering, std::vector<uint32_t>&& element_number, size_t n_listed,
+                       uint32_t n_forests, size_t n_totals_bytes) {
   n = n_listed; forests = n_forests; totals_bytes = n_totals_bytes;
-  number_nodes(references, n, uniq, inv);
+  uniq = std::move(numbering);
+  inv = std::move(element_number);
   nu = uniq.size();
   uint32_t* up_inv = nullptr;
   if (more(d_refs, nu * 4) < 0 || more(d_parent, forests * nu * 4) < 0 || more(d_labels, forests * n * 4) < 0 ||

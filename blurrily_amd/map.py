@@ -834,6 +834,37 @@ class RawMap:
         moved = was != now
         return old[moved], now[moved]
 
+    def cluster_within(self, references, blocks, min_permille):
+        """``cluster`` within blocks (blurrily_storage_cluster_within): ``blocks[i]`` is a 32-bit key for
+        ``references[i]``, and only references under one key are ever joined.  One call serves all blocks.  Returns
+        (labels[n] uint32, the number of components over all blocks, the number of within-block edges): what one
+        ``cluster`` call per block gives, the counts summed."""
+        self._check_open()
+        mp = _permille(min_permille)
+        refs, keys = self._refs(references), self._refs(blocks)
+        if len(keys) != len(refs):
+            raise ValueError(f"{len(keys)} block keys for {len(refs)} references")
+        n = len(refs)
+        labels = np.zeros(n, dtype=np.uint32)
+        n_clusters, n_edges = C.c_uint32(0), C.c_uint64(0)
+        ptr = lambda a: a.ctypes.data if n else None
+        _check(self._lib.blurrily_storage_cluster_within(self._h, ptr(refs), ptr(keys), n, mp, ptr(labels),
+                                                         C.byref(n_clusters), C.byref(n_edges)))
+        return labels, int(n_clusters.value), int(n_edges.value)
+
+    def duplicates_within(self, references, blocks, min_permille):
+        """The within-block clusters of two or more references, as ``duplicates`` gives them: a list of lists of
+        references, each ascending, ordered by label."""
+        refs = self._refs(references)
+        labels, _, _ = self.cluster_within(refs, blocks, min_permille)
+        refs, at = np.unique(refs, return_index=True)
+        labels = labels[at]
+        held = labels != _native.NO_CLUSTER
+        refs, labels = refs[held], labels[held]
+        order = np.argsort(labels, kind="stable")               # (refs ascending within a label)
+        _, starts, sizes = np.unique(labels[order], return_index=True, return_counts=True)
+        return [refs[order[s:s + k]].tolist() for s, k in zip(starts.tolist(), sizes.tolist()) if k >= 2]
+
     def sync_device(self):
         self._check_open()
         _check(self._lib.blurrily_storage_sync_device(self._h))

@@ -532,6 +532,29 @@ int blurrily_storage_cluster_extend(trigram_map haystack, const uint32_t* old_re
                                     uint32_t* labels_old, uint32_t* labels_new, uint32_t* n_clusters,
                                     uint64_t* n_edges);
 
+/* Clusters within blocks: blurrily_storage_cluster's components where an edge also needs both ends in one block --
+ * what entity resolution does after blocking by country, tenant or postcode, in one call for all blocks (DESIGN.md
+ * section 29).  blocks[i] is an opaque 32-bit key for references[i].  Nodes, T, R, m, the edge test,
+ * BLURRILY_NO_CLUSTER, deletes, pending puts and a reference put again: exactly as for blurrily_storage_cluster.
+ *   Edges:  that call's edges whose two ends carry the same key.  A component never spans two blocks.
+ *   Label:  the smallest reference among the nodes of a node's component.
+ * labels[i] belongs to references[i]; n_clusters (may be NULL): the components over all blocks; n_edges (may be NULL):
+ * the edges above, each once.  All outputs depend on the map's contents, the set of (reference, key) pairs and
+ * min_permille only: not on the list's order, the images the references live in, or the order of the device's unions.
+ * With all keys equal the outputs are byte for byte blurrily_storage_cluster's; with all keys distinct every held
+ * reference is its own label and n_edges is 0; in general the labels are those of one blurrily_storage_cluster call
+ * per block, and the two counts are the sums over those calls.  A reference may be listed more than once, under one
+ * key.  n == 0: success, nothing written but the two counts (0).  A small block is scored member against member from
+ * the device's copy of its members' trigrams, a large one sweeps the map as blurrily_storage_cluster does; option
+ * "scope_strategy" 1 forces the sweep for every block, 2 the direct form, 0 (the default) chooses per block.  With
+ * "devices" > 1 the primary device alone serves the call.
+ * 0, or -1 with errno: EINVAL before anything needs a GPU and with nothing written (haystack NULL, min_permille > 1000,
+ * references, blocks or labels NULL with n > 0, n above 0xFFFFFFF0, a reference listed more than once with different
+ * keys); ENODEV without a usable GPU; EIO if a bounded loop of the device's union-find ran out.  The labels are written
+ * only on success.  Not built: levels, centres, cores and extend within blocks, a _device variant, a protocol verb. */
+int blurrily_storage_cluster_within(trigram_map haystack, const uint32_t* references, const uint32_t* blocks, size_t n,
+                                    uint32_t min_permille, uint32_t* labels, uint32_t* n_clusters, uint64_t* n_edges);
+
 /* Tokeniser (ext/blurrily/tokeniser.h:34, tokeniser.c:59-119): `output` needs
  * strlen(input)+1 slots; returns the number of distinct codes, ascending. */
 int blurrily_tokeniser_parse_string(const char* input, uint16_t* output);
