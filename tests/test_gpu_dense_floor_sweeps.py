@@ -21,6 +21,7 @@ import similar_truth
 from blurrily_amd.map import _pack
 from cluster_centres_truth import CentresTruth
 from cluster_cores_truth import BORDER, CORE, CoresEdges
+from dense_truths import ArrayAbove, FlooredSimilar, _same_bytes, floor_bar
 from helpers import Oracle
 
 pytestmark = pytest.mark.gpu
@@ -30,61 +31,6 @@ MIN_DEGREES = (0, 2, 3, 5)
 # the family pair whose permille p* gives the last two floors, p* and p* + 1: of the thirteenth family (110 words),
 # the string without its first fifth and the one with its words reversed
 PAIR_FAMILY, PAIR_MEMBERS = 12, (4, 5)
-
-
-class FlooredSimilar(similar_truth.Truth):
-    """similar_truth.Truth for floors of at least `least`: only the candidates at or above `least` are ranked -- the
-    rows at or above a floor p >= least are the same prefix of either ranking -- which spares a glued needle the exact
-    fractions of the tens of thousands of references it shares a trigram with."""
-
-    def __init__(self, strings, refs, weights, least):
-        super().__init__(strings, refs, weights)
-        self.least = least
-
-    def rows(self, needle, limit, p):
-        assert p >= self.least
-        codes = Oracle.tokenise(needle)
-        T = len(codes)
-        if needle not in self._ranked:
-            mask = np.zeros(similar_truth.NUM_CODES, dtype=bool)
-            mask[codes] = True
-            matches = np.add.reduceat(mask[self.flat].astype(np.int64), self.starts)
-            matches[self.R == 0] = 0
-            i = np.nonzero((matches >= 1) & (1000 * matches >= self.least * (T + self.R - matches)))[0]
-            cands = zip(self.refs[i].tolist(), matches[i].tolist(), self.weights[i].tolist(), self.R[i].tolist())
-            self._ranked[needle] = similar_truth.ranked(cands, T)
-        return similar_truth.cut(self._ranked[needle], T, limit, p)
-
-
-class ArrayAbove(above_truth.Truth):
-    """above_truth.Truth with a needle's matches kept from one bar to the next and its rows as an array: the glued
-    needles have tens of thousands of rows at the low bars."""
-
-    def __init__(self, strings, refs, weights):
-        super().__init__(strings, refs, weights)
-        self._matches = {}
-
-    def rows(self, needle, mm, mp):
-        codes = Oracle.tokenise(needle)
-        T = len(codes)
-        t = above_truth.bar(T, mm, mp)
-        if T == 0 or t > T:
-            return np.zeros((0, 3), dtype=np.uint32)
-        if needle not in self._matches:
-            mask = np.zeros(above_truth.NUM_CODES, dtype=bool)
-            mask[codes] = True
-            matches = np.add.reduceat(mask[self.flat].astype(np.int64), self.starts)
-            matches[~self.has] = 0
-            self._matches[needle] = matches.astype(np.int16)      # (a string of these maps has under 2^15 trigrams)
-        matches = self._matches[needle].astype(np.int64)
-        keep = np.nonzero(matches >= t)[0]
-        order = keep[np.lexsort((self.refs[keep], self.weights[keep], -matches[keep]))]
-        return np.stack([self.refs[order], matches[order], self.weights[order]], axis=1).astype(np.uint32)
-
-
-def floor_bar(T, p):
-    """The bar of matches a sweep holds a needle of T trigrams to at floor p."""
-    return max(1, (p * T + 999) // 1000)
 
 
 @pytest.fixture(scope="module")
@@ -161,14 +107,6 @@ def test_the_upper_half_pair_and_a_pair_across_the_windows_are_edges(case):
         assert pair not in _edge_set(h, of[case.p_star + 1][2]), name
         # a family member of window 1 with an edge into window 0
         assert any(a in family and {h.loc[a][0], h.loc[b][0]} == {0, 1} for a, b in _edge_set(h, of[350][2])), name
-
-
-def _same_bytes(one, other):
-    for x, y in zip(one, other):
-        if isinstance(x, np.ndarray):
-            assert x.dtype == y.dtype and x.tobytes() == y.tobytes()
-        else:
-            assert x == y
 
 
 @pytest.mark.parametrize("name", ["short", "long"])
