@@ -3,7 +3,8 @@
 // declared in blurrily::detail has hidden visibility: none of it is a dynamic symbol of libblurrily_hip.so.
 //   c_abi.hip        lifecycle, put / delete / save / stats, find / find_batch entries, options, debug entries
 //   map_log.hip      the mutation log: ensure_device, apply_tombstones, map_ready, map_images
-//   find_run.hip     the batch search's launch logic: run_find_on, run_find (the timing events); stage_string_needles
+//   find_run.hip     the batch search's launch logic: run_find_on (its decisions: find_choice.h), run_find (the timing
+//                    events); stage_string_needles
 //   multi_device.hip replicas, run_find_multi
 //   host_batch.hip   host-buffer batches: needle_len, longest_needle, BatchBlocks; the chunked pipeline,
 //                    find_batch_host, find_few
@@ -28,6 +29,7 @@
 #include <vector>
 
 #include "device_index.h"
+#include "find_choice.h"
 #include "find_kernels.h"
 #include "hip_try.h"
 #include "host_index.h"
@@ -227,8 +229,7 @@ int  apply_tombstones(trigram_map m, hipStream_t stream);
 // what an entry does first: the map's pending work, then the device image (ENODEV without a usable GPU), the tombstones
 int  map_ready(trigram_map m, hipStream_t stream);
 
-// ---- find_run.hip -----------------------------------------------------------------------------------------------------
-uint32_t latency_ranges(size_t n, uint32_t limit, uint32_t n_windows, size_t wgs, uint32_t tasks_per_wg);
+// ---- find_run.hip (latency_ranges and the other decisions of run_find_on: find_choice.h) -------------------------------
 // (sm: a scoped find's masks, in the tombstone bitmap's place: they exclude the deleted ranks too)
 struct ScopeMasks { const uint32_t* base; const uint32_t* delta; };
 int run_find(trigram_map m, const char* d_packed, size_t packed_bytes, const uint64_t* d_offsets, size_t n,
