@@ -229,4 +229,45 @@ struct ClusterWithinSweepArgs {
 };
 int launch_cluster_within_sweep(const ClusterWithinSweepArgs& a, hipStream_t stream);
 
+// Cluster tree (cluster_tree_kernels.hip): the maximum spanning forest of the edges, heights in
+// whole per mille, by Boruvka rounds.  A round is one sweep, which chooses instead of uniting, then across launch
+// boundaries the merge and the flatten.
+// An edge's key, the total order "height descending, lower number ascending, higher number ascending" as one word that
+// only rises: h << 54 | (~lo & M27) << 27 | (~hi & M27), never 0 (lo < hi <= M27).  Hence at most 2^27 numbers.
+constexpr uint32_t kTreeNumberBits = 27;
+constexpr uint32_t kTreeNumberMask = (1u << kTreeNumberBits) - 1u;
+constexpr uint32_t kTreeMaxNodes   = 1u << kTreeNumberBits;
+
+// cluster_sweep_kernel's sweep with another ending: an edge whose ends lie in different components of comp[] (frozen
+// for the launch) raises best[] of both components to its key; nothing is united.  Round 1 counts the edges into
+// s.totals->edges; from round 2 on a needle whose component is closed does nothing.
+struct ClusterTreeSweepArgs {
+  ClusterSweepArgs    s;         // (s.parent is not used)
+  const uint32_t*     comp;      // [n_nodes] each number's component: its root when the round began
+  const uint8_t*      closed;    // [n_nodes] by component: no edge leaves it
+  unsigned long long* best;      // [n_nodes] by component, zero when the round begins
+  uint32_t            round;     // from 1
+};
+int launch_cluster_tree_sweep(const ClusterTreeSweepArgs& a, hipStream_t stream);
+
+// One chosen edge, as the caller gets it (blurrily_cluster_merge_t of include/blurrily_storage.h).
+struct ClusterTreeMerge { uint32_t a, b, permille; };
+
+// After a round's sweeps.  Merge: number i with best[i] != 0 unites its edge's ends in parent[], and the thread that
+// made the hook appends {refs[lo], refs[hi], h} to merges[] at (*n_merges)++; a root with best[i] == 0 is closed;
+// best[i] = 0 again.  Flatten, across a launch boundary: comp[i] = root of i.
+struct ClusterTreeRoundArgs {
+  uint32_t*           parent;    // [n_nodes]
+  const uint32_t*     refs;      // [n_nodes] ascending
+  uint32_t            n_nodes;
+  unsigned long long* best;      // [n_nodes]
+  uint32_t*           comp;      // [n_nodes]
+  uint8_t*            closed;    // [n_nodes]
+  ClusterTreeMerge*   merges;    // [n_nodes] (a forest has fewer edges than nodes)
+  uint32_t*           n_merges;
+  ClusterTotals*      totals;
+};
+int launch_cluster_tree_merge(const ClusterTreeRoundArgs& a, hipStream_t stream);
+int launch_cluster_tree_flatten(const ClusterTreeRoundArgs& a, hipStream_t stream);
+
 }  // namespace blurrily

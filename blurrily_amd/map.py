@@ -865,6 +865,71 @@ class RawMap:
         _, starts, sizes = np.unique(labels[order], return_index=True, return_counts=True)
         return [refs[order[s:s + k]].tolist() for s, k in zip(starts.tolist(), sizes.tolist()) if k >= 2]
 
+    def cluster_tree(self, references, min_permille):
+        """The single-linkage dendrogram of ``cluster`` at per-mille resolution (blurrily_storage_cluster_tree): the
+        maximum spanning forest of the edges at or above ``min_permille``, an edge's height being its similarity in
+        whole per mille, rounded down.  Returns (labels[n] uint32, n_clusters and n_edges as ``cluster`` gives them at
+        ``min_permille``, and between them merges[k, 3] uint32: rows ``[a, b, permille]`` with a < b, sorted by height
+        descending, then a, then b; k is the nodes minus the components) as ``(labels, merges, n_clusters, n_edges)``.
+        ``cut_tree`` gives the labels at any higher floor without another call."""
+        self._check_open()
+        mp = _permille(min_permille)
+        refs = self._refs(references)
+        n = len(refs)
+        labels = np.zeros(n, dtype=np.uint32)
+        merges = np.zeros((n, 3), dtype=np.uint32)
+        n_merges, n_clusters, n_edges = C.c_uint32(0), C.c_uint32(0), C.c_uint64(0)
+        ptr = lambda a: a.ctypes.data if n else None
+        _check(self._lib.blurrily_storage_cluster_tree(self._h, ptr(refs), n, mp, ptr(labels), ptr(merges),
+                                                       C.byref(n_merges), C.byref(n_clusters), C.byref(n_edges)))
+        return labels, merges[:int(n_merges.value)].copy(), int(n_clusters.value), int(n_edges.value)
+
+    @staticmethod
+    def cut_tree(references, labels, merges, floor, min_permille=0):
+        """The labels ``cluster(references, floor)`` would give, from a ``cluster_tree`` result alone: union-find in
+        numpy over the merges with ``permille >= floor``.  ``labels`` are the tree's (they tell which references the
+        map holds), ``min_permille`` the floor the tree was made at: the tree knows no edge below it, so a cut there
+        is refused (ValueError), as is one above 1000.  Needs no map and no GPU."""
+        floor, low = _permille(floor), _permille(min_permille)
+        if floor < low:
+            raise ValueError(f"floor {floor} below the tree's {low}: its edges are not in the tree")
+        refs, labels = np.asarray(references, dtype=np.uint32), np.asarray(labels, dtype=np.uint32)
+        merges = np.asarray(merges, dtype=np.uint32).reshape(-1, 3)
+        if refs.ndim != 1 or labels.shape != refs.shape:
+            raise ValueError("references and labels must be one-dimensional and of one length")
+        held = labels != _native.NO_CLUSTER
+        nodes = np.unique(refs[held])                             # ascending: the lowest index is the lowest reference
+        kept = merges[merges[:, 2] >= floor]
+        a, b = np.searchsorted(nodes, kept[:, 0]), np.searchsorted(nodes, kept[:, 1])
+        if len(kept) and (max(a.max(), b.max()) >= len(nodes) or (nodes[a] != kept[:, 0]).any() or (nodes[b] != kept[:, 1]).any()):
+            raise ValueError("a merge names a reference that the labels do not hold")
+        label = np.arange(len(nodes), dtype=np.int64)
+        while len(kept):                                          # lowest-label propagation with pointer jumping
+            low_of = np.minimum(label[a], label[b])
+            nxt = label.copy()
+            np.minimum.at(nxt, a, low_of)
+            np.minimum.at(nxt, b, low_of)
+            nxt = nxt[nxt]
+            if np.array_equal(nxt, label):
+                break
+            label = nxt
+        out = np.full(len(refs), _native.NO_CLUSTER, dtype=np.uint32)
+        out[held] = nodes[label[np.searchsorted(nodes, refs[held])]]
+        return out
+
+    @staticmethod
+    def merge_profile(merges, nodes=None):
+        """What a caller slides the cut by: per distinct height of a ``cluster_tree`` result, highest first,
+        ``{permille, merges, n_clusters}`` -- the merges at or above it and the clusters a cut there leaves among
+        ``nodes`` references (default: the references the merges name, so singletons are left out)."""
+        merges = np.asarray(merges, dtype=np.uint32).reshape(-1, 3)
+        if nodes is None:
+            nodes = len(np.unique(merges[:, :2]))
+        heights, counts = np.unique(merges[:, 2], return_counts=True)
+        done = np.cumsum(counts[::-1])
+        return [{"permille": int(h), "merges": int(k), "n_clusters": int(nodes) - int(k)}
+                for h, k in zip(heights[::-1].tolist(), done.tolist())]
+
     def sync_device(self):
         self._check_open()
         _check(self._lib.blurrily_storage_sync_device(self._h))
@@ -904,7 +969,10 @@ class RawMap:
         """Names of the find kernels the last batched find launched, in launch order (blurrily_storage_last_kernels)."""
         self._check_open()
         buf = C.create_string_buffer(512)
-        self._lib.blurrily_storage_last_kernels(self._h, buf, len(buf))
+        need = self._lib.blurrily_storage_last_kernels(self._h, buf, len(buf))
+        if need >= len(buf):                              # (a call of many launches: the whole list, not its first 511 bytes)
+            buf = C.create_string_buffer(need + 1)
+            self._lib.blurrily_storage_last_kernels(self._h, buf, len(buf))
         return [k for k in buf.value.decode().split("+") if k]
 
     def tune(self, packed, offsets, n, limit):

@@ -555,6 +555,34 @@ int blurrily_storage_cluster_extend(trigram_map haystack, const uint32_t* old_re
 int blurrily_storage_cluster_within(trigram_map haystack, const uint32_t* references, const uint32_t* blocks, size_t n,
                                     uint32_t min_permille, uint32_t* labels, uint32_t* n_clusters, uint64_t* n_edges);
 
+/* Cluster tree: the single-linkage dendrogram of the clusters above, at per-mille resolution, for a caller who wants
+ * the floor at which two references first meet or wants to slide the cut afterwards.  Nodes, T,
+ * R, m, the edge test, BLURRILY_NO_CLUSTER, repeats, absent references, unlisted bridges, deletes, pending puts and a
+ * reference put again: exactly as for blurrily_storage_cluster.
+ *   Height: an edge's height is h = floor(1000 * m / (T_a + T_b - m)) in 64-bit integers, so h >= f exactly when the
+ *           edge passes that call's test at floor f.  Edges below min_permille do not exist.
+ *   Order:  edges are totally ordered by (height descending, lower reference ascending, higher reference ascending).
+ *   Merges: the maximum spanning forest of the edges under that order, which is unique: the edges Kruskal's algorithm
+ *           keeps when it takes them in that order.  merges[0 .. *n_merges) are its edges {a, b, permille} with a < b
+ *           as references and permille the height, sorted by that same order; merges needs room for n records.
+ *           n_merges == nodes - n_clusters, always.
+ * Uniting the ends of the merges with permille >= f, for any f >= min_permille, gives exactly the components of
+ * blurrily_storage_cluster at floor f.  labels, n_clusters and n_edges are byte for byte what that call returns at
+ * min_permille.  All outputs depend on the map's contents, the list as a set and min_permille only; two runs give
+ * identical bytes.  The device sweeps the map once per Boruvka round, a handful of times.  n_merges, n_clusters and
+ * n_edges may each be NULL.  n == 0: success, nothing written but the counts given (0).  With "devices" > 1 the primary
+ * device alone serves the call.
+ * 0, or -1 with errno: EINVAL before anything needs a GPU and with nothing written (haystack NULL, min_permille > 1000,
+ * references, labels or merges NULL with n > 0, n above BLURRILY_CLUSTER_TREE_MAX: the device orders edges by one
+ * 64-bit word that holds the height and both ends in 27 bits each); ENODEV without a usable GPU; EIO if a bounded loop
+ * of the device's union-find or the bound on the rounds ran out.  The labels and merges are written only on success.
+ * Not built: a tree within blocks or scopes, a _device variant, other linkages, a protocol verb. */
+#define BLURRILY_CLUSTER_TREE_MAX 0x8000000u
+typedef struct { uint32_t a, b, permille; } blurrily_cluster_merge_t;
+int blurrily_storage_cluster_tree(trigram_map haystack, const uint32_t* references, size_t n, uint32_t min_permille,
+                                  uint32_t* labels, blurrily_cluster_merge_t* merges, uint32_t* n_merges,
+                                  uint32_t* n_clusters, uint64_t* n_edges);
+
 /* Tokeniser (ext/blurrily/tokeniser.h:34, tokeniser.c:59-119): `output` needs
  * strlen(input)+1 slots; returns the number of distinct codes, ascending. */
 int blurrily_tokeniser_parse_string(const char* input, uint16_t* output);
