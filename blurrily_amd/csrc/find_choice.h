@@ -1,6 +1,7 @@
 // find_choice.h -- the batch search's decisions as plain arithmetic (find_run.hip's run_find_on acts on them): the ranges
 // of latency mode, the class of a batch, the static rule for the short needles' sweep, the pick among measured sweeps,
-// the verdict on a watched batch.  No HIP and no map here: tests/cpp/find_choice_check.cpp compiles it alone.
+// the verdict on a watched batch; and find_few's (host_batch.hip): its ranges, the merge's pool, the shared launch's shape.
+// No HIP and no map here: tests/cpp/find_choice_check.cpp compiles it alone.
 #pragma once
 #include <algorithm>
 #include <cstddef>
@@ -24,6 +25,48 @@ inline uint32_t latency_ranges(size_t n, uint32_t limit, uint32_t n_windows, siz
   const size_t target_tasks = (tasks_per_wg ? tasks_per_wg : n <= 60 ? 1 : 2) * wgs;      // (option "latency_tasks": 0 = this rule)
   uint32_t ranges = uint32_t(std::min<size_t>((n_windows + 1) / 2, target_tasks / n));   // ranges are whole window pairs
   return std::max<uint32_t>(1u, std::min<uint32_t>(ranges, std::max<uint32_t>(1u, 4096u / limit)));      // (the merge's pool)
+}
+
+// The ranges of a find_few call of n_rows needles with a posting (host_batch.hip): 1 -- the shared launch,
+// find_one_kernel -- unless few_max < n_rows <= mid_max; there latency mode's, lowered until its tasks fit the lists
+// the call's buffers hold (find_few_layout.h: FewLists::max_lists).  With tasks_per_wg 0 the bound never binds: the rule
+// aims at no more than two tasks per resident workgroup, 2 432 tasks on 1 216 workgroups against 4 608 lists; option
+// "latency_tasks" at 8 .. 16 is what reaches it.
+inline uint32_t few_ranges(size_t n_rows, uint32_t few_max, uint32_t mid_max, uint32_t limit, uint32_t n_windows, size_t wgs,
+                           uint32_t tasks_per_wg, size_t max_lists) {
+  if (n_rows <= few_max || n_rows > mid_max) return 1;
+  const uint32_t ranges = latency_ranges(n_rows, limit, n_windows, wgs, tasks_per_wg);
+  return uint32_t(std::min<size_t>(ranges, std::max<size_t>(1, max_lists / n_rows)));
+}
+
+// The pool of the merge behind latency mode's ranges: the power of two at or above ranges * limit, from 1 024.
+inline uint32_t merge_pool_cap(uint32_t ranges, uint32_t limit) {
+  uint32_t cap = 1024;
+  while (cap < ranges * limit) cap <<= 1;
+  return cap;
+}
+
+// The shared launch's shape (find_one_kernel): windows per workgroup and workgroups per needle.  One window per workgroup
+// while that fills at most max_grid of them, whole window pairs beyond; more than eight needles: about mid_workgroups
+// (a thousand) workgroups in all -- two rounds of what the chip holds --, i.e. several window pairs a workgroup (its
+// later steps arrive with its own threshold: one_select's cheap way); at least min_per (a test's way to the
+// several-steps-per-workgroup path on a small image).  Then as many more as keep a launch's lists, grid * n_rows, within
+// max_lists: the first three rules do that by themselves up to sixteen needles and at the default mid_workgroups --
+// the option may be set to 65 536, and a tunable changes a launch's shape, never whether the call succeeds.
+struct OneGrid { uint32_t per, grid; };
+inline OneGrid one_grid(uint32_t n_windows, uint32_t n_rows, uint32_t mid_workgroups, uint32_t min_per, uint32_t max_grid,
+                        size_t max_lists) {
+  const auto whole_pairs = [](uint32_t per) { return per + (per > 1 ? per & 1u : 0u); };
+  uint32_t per = 1;
+  if (n_windows > max_grid) per = whole_pairs((n_windows + max_grid - 1) / max_grid);
+  if (n_rows > 8) {                                       // (from nine needles on: measured, tools/mid_probe.py)
+    const uint32_t rows_wgs = std::max<uint32_t>(2u, mid_workgroups / n_rows);     // workgroups per needle
+    per = std::max(per, whole_pairs((n_windows + rows_wgs - 1) / rows_wgs));
+  }
+  per = std::max(per, min_per);
+  const uint32_t rows_max = uint32_t(std::max<size_t>(1, max_lists / std::max<uint32_t>(n_rows, 1u)));   // workgroups per needle the lists hold
+  per = std::max(per, whole_pairs((n_windows + rows_max - 1) / rows_max));
+  return OneGrid{per, (n_windows + per - 1) / per};
 }
 
 // The sweeps that can serve a batch's short needles (trigram_map_t::last_sweep, ws_choice).

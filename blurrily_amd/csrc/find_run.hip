@@ -308,14 +308,12 @@ static int fill_args(FindCall& c, const uint64_t* d_offsets, const RefNeedles* r
   trigram_map m = c.m;
   const DeviceIndex& ix = c.ix;
   FindArgs& a = c.a;
-  a.slice_se = ix.d_slice_se; a.ent = ix.d_ent; a.ref_of_rank = ix.d_ref_of_rank;
-  a.weight_of_rank = ix.d_weight_of_rank; a.n_refs = ix.n_refs; a.n_windows = ix.n_windows;
+  image_args(ix, &a);
   a.offsets = rn ? rn->qoff : d_offsets; a.qcodes = rn ? rn->codes : static_cast<const uint16_t*>(m->ws_codes.p);
-  a.q_ntri = c.q_ntri; a.q_nb = c.q_nb; a.q_start = c.q_start; a.win_max_tri = ix.d_win_max_tri; a.nib_windows = ix.nib_windows;
+  a.q_ntri = c.q_ntri; a.q_nb = c.q_nb; a.q_start = c.q_start;
   a.results = d_results; a.counts = d_counts; a.limit = c.limit;
   a.floor = c.floor;
   a.tomb = d_tomb;
-  a.dense_min8 = ix.dense_min8;
   a.nm_dense = std::max((m->nm_dense + 7u) & ~7u, ix.dense_min8);
   a.nm_cmin = 0;                                     // (set per sweep: run_sweep)
   a.stats = m->collect_stats ? m->d_stats : nullptr;

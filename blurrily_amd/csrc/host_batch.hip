@@ -1,5 +1,6 @@
 // host_batch.hip -- host-buffer batches: the chunked three-stream pipeline, the one-piece batch through pinned
 // staging, and a handful of needles (or ONE, the caller waiting) in one launch without copies (find_few).
+#include "find_few_layout.h"
 #include "map_internal.h"
 
 using namespace blurrily;
@@ -291,187 +292,177 @@ int find_batch_host(trigram_map m, const char* packed, const uint64_t* offsets, 
 }
 
 // ---- ONE needle, the caller waiting -- or a handful: one launch, no copies (find_kernels.hip: find_one_kernel) --------
-// The reference's only call shape (ext/blurrily/map_ext.c:131-162 -> storage.c:477-580), and small host-buffer batches
-// (a server's coalesced FINDs under light load).  needle i = s[i][0 .. len[i]) (up to its first NUL).  Returns 0 with
-// counts[] and rows filled (results + i * limit), -1 with errno, or kOneNotTaken when the finds have to go the batch's
-// way: a limit of 0 or above kOneMaxKeep, more than kMidMaxNeedles needles, a needle of more than 64 distinct trigrams,
-// timing or request counters switched on, option "one_launch" 0.  Mutations the base image does not hold yet are
-// served: tombstones inside the select, pending puts by a second launch over the delta image.
-constexpr size_t kOneRowBytes = kOneMaxKeep * sizeof(trigram_match_t);
-// the pinned page per image: [kMidMaxNeedles] rows | [kMidMaxNeedles][2] count, sequence word | codes [kMidMaxNeedles][64] | T
-constexpr size_t kOneWordsAt = kMidMaxNeedles * kOneRowBytes;
-constexpr size_t kOneCodesAt = kOneWordsAt + kMidMaxNeedles * 8 + 64;
-constexpr size_t kOneTAt = kOneCodesAt + kMidMaxNeedles * 64 * sizeof(uint16_t);
-// ... | postings [kMidMaxNeedles] | start window [kMidMaxNeedles] | code offsets [kMidMaxNeedles + 1] (latency mode's needle arrays)
-constexpr size_t kMidNbAt = kOneTAt + kMidMaxNeedles * sizeof(uint32_t);
-constexpr size_t kMidStartAt = kMidNbAt + kMidMaxNeedles * sizeof(uint32_t);
-constexpr size_t kMidOffAt = (kMidStartAt + kMidMaxNeedles * sizeof(uint32_t) + 7) & ~size_t(7);
-constexpr size_t kOneHostBytes = kMidOffAt + (kMidMaxNeedles + 1) * sizeof(uint64_t) + 64;
-// lists a launch may leave: up to sixteen rows of kOneMaxGrid workgroups, or more rows of fewer (find_few aims at a
-// thousand workgroups in all)
-constexpr size_t kOneMaxLists = size_t(kOneMaxNeedles) * kOneMaxGrid;
+// find_few, at the end, is the sequence; its steps stand here in its order.  The pinned page and the device lists it
+// shares with the kernels are laid out in find_few_layout.h; what it decides is find_choice.h's arithmetic.
+namespace {
 
-int find_few(trigram_map m, const char* const* s, const size_t* len, size_t n, uint16_t limit, trigram_match results,
-             uint32_t* counts) {
-  if (!m->one.enabled || limit == 0 || limit > kOneMaxKeep || n == 0 || n > kMidMaxNeedles || m->timing || m->collect_stats)
-    return kOneNotTaken;
-  uint16_t codes[kMidMaxNeedles * 64];
-  uint32_t T[kMidMaxNeedles];
-  {
-    uint16_t buf[256];
-    for (size_t i = 0; i < n; ++i) {
-      if (len[i] > 255) return kOneNotTaken;
-      const int t = tokenise(s[i], len[i], buf);            // tokeniser.c:59-119
-      if (t > 64) return kOneNotTaken;
-      T[i] = uint32_t(t);
-      std::memcpy(codes + i * 64, buf, size_t(t) * sizeof(uint16_t));
-    }
+constexpr FewPage  kPage(kOneMaxKeep, kMidMaxNeedles);
+constexpr FewLists kLists(kOneMaxKeep, kOneMaxGrid, kOneMaxNeedles, kMidMaxNeedles);
+
+// A call's needles -- tokenised, then compacted to the rows of the grid: the needles that have a posting -- and what the
+// launches share.  (Declared without an initialiser: nothing clears the 16 KiB of codes.)
+struct FewCall {
+  trigram_map m;
+  uint32_t    limit;
+  uint16_t    codes[kMidMaxNeedles * 64];                          // [row][64]
+  uint32_t    T[kMidMaxNeedles];
+  uint32_t    row_of[kMidMaxNeedles], row_nb[kMidMaxNeedles], n_rows;   // a row's needle, its postings (saturated)
+  uint32_t    ranges;                                              // latency mode's, on the base image (1: the shared launch)
+  uint32_t    seq;
+  bool mid() const { return ranges > 1; }
+  // more rows than travel as kernel arguments: the shared launch reads the codes from the pinned page (both images' launches the first image's copy)
+  bool far() const { return n_rows > kOneMaxNeedles; }
+};
+
+// false: a needle the launch does not take (more than 255 bytes, more than 64 distinct trigrams)
+bool tokenise_needles(FewCall& c, const char* const* s, const size_t* len, size_t n) {
+  uint16_t buf[256];
+  for (size_t i = 0; i < n; ++i) {
+    if (len[i] > 255) return false;
+    const int t = tokenise(s[i], len[i], buf);              // tokeniser.c:59-119
+    if (t > 64) return false;
+    c.T[i] = uint32_t(t);
+    std::memcpy(c.codes + i * 64, buf, size_t(t) * sizeof(uint16_t));
   }
-  DeviceScope scope(m->dev.device);
-  // what the reference's find does first: sort the needle's dirty buckets (storage.c:516), sum their sizes (:498-503)
-  if (m->host->dirty_buckets())
-    for (size_t i = 0; i < n; ++i)
-      for (uint32_t k = 0; k < T[i]; ++k) m->host->sort_bucket_if_dirty(codes[i * 64 + k]);
-  if (ensure_device(m) < 0) return -1;
-  // Mutations the base image does not hold (DESIGN.md "Mutation and device sync"): deletes are tombstone bits the select
-  // looks at, pending puts live in a small delta image searched by a SECOND launch; the two lists of a needle are
-  // merged here (they hold disjoint references).  A log that has overflowed is folded by ensure_device above.
-  const bool with_tomb = log_of(m)->n_tomb != 0, with_delta = !log_of(m)->pending.empty() && m->delta.device >= 0;
-  // needles without a posting return no rows (storage.c:503) and take no row of the grid
-  uint32_t row_of[kMidMaxNeedles], row_nb[kMidMaxNeedles], n_rows = 0;
+  return true;
+}
+
+// what the reference's find does first: sort the needle's dirty buckets (storage.c:516), sum their sizes (:498-503: compact_rows)
+void sort_dirty_buckets_of(const FewCall& c, size_t n) {
+  if (!c.m->host->dirty_buckets()) return;
+  for (size_t i = 0; i < n; ++i)
+    for (uint32_t k = 0; k < c.T[i]; ++k) c.m->host->sort_bucket_if_dirty(c.codes[i * 64 + k]);
+}
+
+// needles without a posting return no rows (storage.c:503) and take no row of the grid; returns the rows
+uint32_t compact_rows(FewCall& c, size_t n, uint32_t* counts) {
+  uint32_t n_rows = 0;
   for (size_t i = 0; i < n; ++i) {
     uint64_t nb = 0;
-    for (uint32_t k = 0; k < T[i]; ++k) nb += m->host->bucket(codes[i * 64 + k]).used;
+    for (uint32_t k = 0; k < c.T[i]; ++k) nb += c.m->host->bucket(c.codes[i * 64 + k]).used;
     counts[i] = 0;
     if (nb == 0) continue;
-    if (n_rows != i) { std::memmove(codes + n_rows * 64, codes + i * 64, 64 * sizeof(uint16_t)); T[n_rows] = T[i]; }
-    row_nb[n_rows] = nb > 0xFFFFFFFFull ? 0xFFFFFFFFu : uint32_t(nb);
-    row_of[n_rows++] = uint32_t(i);
+    if (n_rows != i) { std::memmove(c.codes + n_rows * 64, c.codes + i * 64, 64 * sizeof(uint16_t)); c.T[n_rows] = c.T[i]; }
+    c.row_nb[n_rows] = nb > 0xFFFFFFFFull ? 0xFFFFFFFFu : uint32_t(nb);
+    c.row_of[n_rows++] = uint32_t(i);
   }
-  if (n_rows == 0) return 0;
-  auto& O = m->one;
-  NameScope name_scope(&m->last_kernels);                 // (the launches below note their kernels' names in the map)
-  m->last_kernels.clear();
-  m->last_sweep = 0;                                      // (no sweep of a class of batches: a single launch, or latency mode)
-  if (!O.h_out) {
-    // stream, pinned page and its device address: built in locals and kept only when ALL of them exist (a half-made set
-    // -- a stream without its page -- would have the next find skip this block and poll a null page)
-    hipStream_t st = nullptr;
-    unsigned char *h = nullptr, *d = nullptr;
-    hipError_t e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&h), 2 * kOneHostBytes, hipHostMallocMapped | hipHostMallocCoherent);
-    if (e == hipSuccess) e = hipHostGetDevicePointer(reinterpret_cast<void**>(&d), h, 0);
-    if (e != hipSuccess) {
-      std::fprintf(stderr, "blurrily_hip: the single find's stream / pinned page: %s\n", hipGetErrorString(e));
-      if (h) (void)hipHostFree(h);
-      if (st) (void)hipStreamDestroy(st);
-      errno = (e == hipErrorOutOfMemory) ? ENOMEM : EIO;
-      return -1;
+  return c.n_rows = n_rows;
+}
+
+// On first use: stream, pinned page and its device address, built in locals and kept only when ALL of them exist (a
+// half-made set -- a stream without its page -- would have the next find skip this step and poll a null page)
+int make_page(trigram_map_t::One& O) {
+  if (O.h_out) return 0;
+  hipStream_t st = nullptr;
+  unsigned char *h = nullptr, *d = nullptr;
+  hipError_t e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
+  if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&h), 2 * kPage.bytes, hipHostMallocMapped | hipHostMallocCoherent);
+  if (e == hipSuccess) e = hipHostGetDevicePointer(reinterpret_cast<void**>(&d), h, 0);
+  if (e != hipSuccess) {
+    std::fprintf(stderr, "blurrily_hip: the single find's stream / pinned page: %s\n", hipGetErrorString(e));
+    if (h) (void)hipHostFree(h);
+    if (st) (void)hipStreamDestroy(st);
+    errno = (e == hipErrorOutOfMemory) ? ENOMEM : EIO;
+    return -1;
+  }
+  std::memset(h, 0, 2 * kPage.bytes);
+  O.stream = st; O.h_out = h; O.d_out = d;
+  return 0;
+}
+
+// ... and both images' lists, zeroed once: every launch leaves tickets and queue at zero and the flags at a spent seq
+int make_lists(trigram_map_t::One& O) {
+  if (O.d_parts.p) return 0;
+  if (O.d_parts.reserve(2 * kLists.bytes, O.stream) < 0) return -1;
+  BLURRILY_HIP_TRY(hipMemsetAsync(O.d_parts.p, 0, 2 * kLists.bytes, O.stream));
+  return 0;
+}
+
+// Into the base image's page, each behind a release fence: latency mode's needle arrays -- what its tokeniser would have
+// left on the device: postings, the window of the needle's own length class, where its codes start --, and the codes
+// and trigram counts where they do not travel as kernel arguments.
+void stage_needles(const FewCall& c, const size_t* len) {
+  unsigned char* page = c.m->one.h_out;
+  if (c.mid()) {
+    uint32_t *h_nb = kPage.nb(page), *h_start = kPage.start(page);
+    uint64_t* h_off = kPage.offsets(page);
+    for (uint32_t r = 0; r < c.n_rows; ++r) {
+      h_nb[r] = c.row_nb[r];
+      h_start[r] = c.m->dev.h_start_win[std::min<size_t>(len[c.row_of[r]], 255)];   // (tokenise_kernel: start_win[len])
+      h_off[r] = uint64_t(r) * 63;                          // a needle's codes start at qcodes + offsets[q] + q: [needle][64]
     }
-    std::memset(h, 0, 2 * kOneHostBytes);
-    O.stream = st; O.h_out = h; O.d_out = d;
-  }
-  if (with_tomb && apply_tombstones(m, O.stream) < 0) return -1;       // (deletes since the last find: their bits are set first)
-  const size_t key_bytes = kOneMaxLists * kOneMaxKeep * 8, flag_bytes = kOneMaxLists * 4, ticket_bytes = (kMidMaxNeedles + 1) * 4;   // (+ latency mode's queue word)
-  const size_t part_bytes = key_bytes + flag_bytes + ticket_bytes;
-  if (!O.d_parts.p) {
-    if (O.d_parts.reserve(2 * part_bytes, O.stream) < 0) return -1;
-    BLURRILY_HIP_TRY(hipMemsetAsync(O.d_parts.p, 0, 2 * part_bytes, O.stream));
-  }
-  // More than few_max rows: the BASE image is searched in latency mode -- find_kernel<..., RANGED>, a needle's windows cut
-  // into ranges, a task per workgroup: beyond about thirty needles its pipelined steps beat find_one_kernel's exact
-  // selects -- but without the batch path's copies: the per-needle arrays its tokeniser would have left
-  // on the device (trigram counts, postings, the window of the needle's own length class, where its codes start) are
-  // written here, into the pinned page, and read over the link by the tasks; the merge writes rows, counts and
-  // sequence words back into the page (merge_parts_pinned_kernel), where this thread polls them as it does
-  // find_one_kernel's.  Two launches, no copy, no stream synchronise (the batch path: a copy in, the tokeniser, the
-  // find, the merge, a copy out, a synchronise).  The delta image, a window or two, keeps find_one_kernel.
-  const uint32_t mid_ranges = (n_rows > O.few_max && n_rows <= O.mid_max)
-      ? latency_ranges(n_rows, limit, m->dev.n_windows, size_t(m->n_cus) * find_wgs_per_cu(), m->latency_tasks) : 1u;
-  const bool mid = mid_ranges > 1;
-  if (mid) {
-    uint32_t* h_nb = reinterpret_cast<uint32_t*>(O.h_out + kMidNbAt);
-    uint32_t* h_start = reinterpret_cast<uint32_t*>(O.h_out + kMidStartAt);
-    uint64_t* h_off = reinterpret_cast<uint64_t*>(O.h_out + kMidOffAt);
-    for (uint32_t r = 0; r < n_rows; ++r) {
-      h_nb[r] = row_nb[r];
-      h_start[r] = m->dev.h_start_win[std::min<size_t>(len[row_of[r]], 255)];   // (tokenise_kernel: start_win[len])
-      h_off[r] = uint64_t(r) * 63;                        // a needle's codes start at qcodes + offsets[q] + q: [needle][64]
-    }
-    h_off[n_rows] = uint64_t(n_rows) * 63;
+    h_off[c.n_rows] = uint64_t(c.n_rows) * 63;
     __atomic_thread_fence(__ATOMIC_RELEASE);
   }
-  // more than kOneMaxNeedles rows, or latency mode: the codes travel in the pinned page (both images' launches read the first image's copy)
-  const bool far = n_rows > kOneMaxNeedles;
-  if (far || mid) {
-    std::memcpy(O.h_out + kOneCodesAt, codes, size_t(n_rows) * 64 * sizeof(uint16_t));
-    std::memcpy(O.h_out + kOneTAt, T, size_t(n_rows) * sizeof(uint32_t));
+  if (c.far() || c.mid()) {
+    std::memcpy(kPage.codes(page), c.codes, size_t(c.n_rows) * 64 * sizeof(uint16_t));
+    std::memcpy(kPage.T(page), c.T, size_t(c.n_rows) * sizeof(uint32_t));
     __atomic_thread_fence(__ATOMIC_RELEASE);
   }
-  const uint32_t seq = ++O.seq ? O.seq : ++O.seq;         // (never 0: what the words hold before the first find)
-  // one launch per image: [0] the base image, [1] the delta image of the pending puts (its own lists, flags and rows)
-  auto launch_on = [&](const DeviceIndex& ix, const uint32_t* d_tomb, int which) -> int {
-    FindArgs a{};
-    a.slice_se = ix.d_slice_se; a.ent = ix.d_ent; a.ref_of_rank = ix.d_ref_of_rank;
-    a.weight_of_rank = ix.d_weight_of_rank; a.n_refs = ix.n_refs; a.n_windows = ix.n_windows;
-    a.win_max_tri = ix.d_win_max_tri; a.nib_windows = ix.nib_windows; a.dense_min8 = ix.dense_min8;
-    a.limit = limit; a.keep = limit; a.pool_cap = 512;
-    a.tomb = d_tomb;
+}
+
+// what either launch on image `which` reads: the image, the limit, the deleted ranks
+int few_args(const FewCall& c, const DeviceIndex& ix, const uint32_t* d_tomb, [[maybe_unused]] int which, FindArgs* a) {
+  image_args(ix, a);
+  a->limit = c.limit; a->keep = c.limit; a->pool_cap = 512;
+  a->tomb = d_tomb;
 #ifdef BLURRILY_TRACE
-    if (!m->d_phase) BLURRILY_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&m->d_phase), kPhaseBytes));
-    if (which == 0) a.phase_clocks = m->d_phase;       // (trace build: find_one_kernel's wall-clock marks, 16 per workgroup)
+  if (!c.m->d_phase) BLURRILY_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c.m->d_phase), kPhaseBytes));
+  if (which == 0) a->phase_clocks = c.m->d_phase;        // (trace build: find_one_kernel's wall-clock marks, 16 per workgroup)
 #endif
-    unsigned char* dp = static_cast<unsigned char*>(O.d_parts.p) + which * part_bytes;
-    unsigned char* d_rows = O.d_out + which * kOneHostBytes;
-    if (mid && which == 0) {
-      const size_t wgs = size_t(m->n_cus) * find_wgs_per_cu();
-      const uint32_t tasks = n_rows * mid_ranges;           // (<= 2 wgs: far below kOneMaxLists, whose keys and flags it borrows)
-      a.offsets = reinterpret_cast<const uint64_t*>(O.d_out + kMidOffAt);
-      a.qcodes = reinterpret_cast<const uint16_t*>(O.d_out + kOneCodesAt);
-      a.q_ntri = reinterpret_cast<const uint32_t*>(O.d_out + kOneTAt);
-      a.q_nb = reinterpret_cast<const uint32_t*>(O.d_out + kMidNbAt);
-      a.q_start = reinterpret_cast<const uint32_t*>(O.d_out + kMidStartAt);
-      a.nm_dense = std::max((m->nm_dense + 7u) & ~7u, ix.dense_min8);
-      a.nm_cmin = 0;                                        // (ranges leave nothing out of a step's count: measured, slower)
-      a.n_work = tasks; a.ranges = mid_ranges; a.short_only = 1;
-      a.part_keys = reinterpret_cast<unsigned long long*>(dp);
-      a.part_count = reinterpret_cast<uint32_t*>(dp + key_bytes);
-      a.queue = reinterpret_cast<uint32_t*>(dp + key_bytes + flag_bytes) + kMidMaxNeedles;   // (zero between launches: the merge hands it back)
-      a.pool_cap = find_pool_cap(limit);
-      if (launch_find(a, false, uint32_t(std::min<size_t>(tasks, wgs)), O.stream) < 0) return -1;
-      uint32_t merge_cap = 1024;
-      while (merge_cap < mid_ranges * limit) merge_cap <<= 1;
-      a.pool_cap = merge_cap;
-      return launch_merge_parts_pinned(a, n_rows, reinterpret_cast<trigram_match_t*>(d_rows),
-                                       reinterpret_cast<uint32_t*>(d_rows + kOneWordsAt), seq, O.stream);
-    }
-    // one window per workgroup while that fills at most kOneMaxGrid of them, whole window pairs beyond; more than
-    // eight needles: about a thousand workgroups in all -- two rounds of what the chip holds --, i.e. several
-    // window pairs a workgroup (its later steps arrive with its own threshold: one_select's cheap way)
-    uint32_t per = 1;
-    if (ix.n_windows > kOneMaxGrid) { per = (ix.n_windows + kOneMaxGrid - 1) / kOneMaxGrid; per += per & 1u; }
-    if (n_rows > 8) {                                     // (from nine needles on: measured, tools/mid_probe.py)
-      const uint32_t rows_wgs = std::max<uint32_t>(2u, m->one.mid_workgroups / n_rows);     // workgroups per needle
-      const uint32_t per_far = (ix.n_windows + rows_wgs - 1) / rows_wgs;
-      per = std::max(per, per_far + (per_far > 1 ? per_far & 1u : 0u));
-    }
-    per = std::max(per, O.min_per);                       // (a test's way to the several-steps-per-workgroup path on a small image)
-    const uint32_t grid = (ix.n_windows + per - 1) / per;
-    if (size_t(grid) * n_rows > kOneMaxLists) { errno = EINVAL; return -1; }   // (cannot happen: grid <= kOneMaxGrid, far grids are small)
-    return launch_find_one(a, codes, T, n_rows, per, grid, reinterpret_cast<unsigned long long*>(dp),
-                           reinterpret_cast<uint32_t*>(dp + key_bytes), reinterpret_cast<trigram_match_t*>(d_rows),
-                           reinterpret_cast<uint32_t*>(d_rows + kOneWordsAt), seq, O.stream, uint32_t(m->n_cus),
-                           far ? reinterpret_cast<const uint16_t*>(O.d_out + kOneCodesAt) : nullptr,
-                           far ? reinterpret_cast<const uint32_t*>(O.d_out + kOneTAt) : nullptr,
-                           far ? reinterpret_cast<uint32_t*>(dp + key_bytes + flag_bytes) : nullptr);
-  };
-  if (launch_on(m->dev, with_tomb ? m->dev.d_tomb : nullptr, 0) < 0) return -1;
-  if (with_delta && launch_on(m->delta, nullptr, 1) < 0) return -1;
-  // A row's last store is its sequence word; the host polls the words in the pinned page instead of waiting for the
-  // runtime to notice the kernel's completion signal (an interrupt or a slower poll: 10 us and more).
+  return 0;
+}
+
+// More than few_max rows: the BASE image is searched in latency mode -- find_kernel<..., RANGED>, a needle's windows cut
+// into ranges, a task per workgroup: beyond about thirty needles its pipelined steps beat find_one_kernel's exact
+// selects -- but without the batch path's copies: the tasks read the needle arrays from the pinned
+// page, over the link, and the merge writes rows, counts and sequence words back into it (merge_parts_pinned_kernel),
+// where the host polls them as it does find_one_kernel's.  Two launches, no copy, no stream synchronise (the batch
+// path: a copy in, the tokeniser, the find, the merge, a copy out, a synchronise).
+int launch_latency(const FewCall& c, const uint32_t* d_tomb) {
+  trigram_map m = c.m;
+  auto& O = m->one;
+  FindArgs a{};
+  if (few_args(c, m->dev, d_tomb, 0, &a) < 0) return -1;
+  unsigned char* lists = static_cast<unsigned char*>(O.d_parts.p);
+  const size_t wgs = size_t(m->n_cus) * find_wgs_per_cu();
+  const uint32_t tasks = c.n_rows * c.ranges;             // (<= kLists.max_lists: few_ranges)
+  a.offsets = kPage.offsets(O.d_out); a.qcodes = kPage.codes(O.d_out); a.q_ntri = kPage.T(O.d_out);
+  a.q_nb = kPage.nb(O.d_out); a.q_start = kPage.start(O.d_out);
+  a.nm_dense = std::max((m->nm_dense + 7u) & ~7u, m->dev.dense_min8);
+  a.nm_cmin = 0;                                          // (ranges leave nothing out of a step's count: measured, slower)
+  a.n_work = tasks; a.ranges = c.ranges; a.short_only = 1;
+  a.part_keys = kLists.keys(lists);
+  a.part_count = kLists.mid_counts(lists);
+  a.queue = kLists.queue(lists);
+  a.pool_cap = find_pool_cap(c.limit);
+  if (launch_find(a, false, uint32_t(std::min<size_t>(tasks, wgs)), O.stream) < 0) return -1;
+  a.pool_cap = merge_pool_cap(c.ranges, c.limit);
+  return launch_merge_parts_pinned(a, c.n_rows, kPage.rows(O.d_out), kPage.words(O.d_out), c.seq, O.stream);
+}
+
+// The shared launch on image `which` ([0] the base image, [1] the delta image of the pending puts: its own lists, flags,
+// tickets and rows): find_one_kernel, a row of the grid per needle.
+int launch_shared(const FewCall& c, const DeviceIndex& ix, const uint32_t* d_tomb, int which) {
+  trigram_map m = c.m;
+  auto& O = m->one;
+  FindArgs a{};
+  if (few_args(c, ix, d_tomb, which, &a) < 0) return -1;
+  unsigned char* lists = kLists.image(static_cast<unsigned char*>(O.d_parts.p), which);
+  unsigned char* page = kPage.image(O.d_out, which);
+  const OneGrid g = one_grid(ix.n_windows, c.n_rows, O.mid_workgroups, O.min_per, kOneMaxGrid, kLists.max_lists);
+  const bool far = c.far();
+  return launch_find_one(a, c.codes, c.T, c.n_rows, g.per, g.grid, kLists.keys(lists), kLists.flags(lists), kPage.rows(page),
+                         kPage.words(page), c.seq, O.stream, uint32_t(m->n_cus), far ? kPage.codes(O.d_out) : nullptr,
+                         far ? kPage.T(O.d_out) : nullptr, far ? kLists.tickets(lists) : nullptr);
+}
+
+// A row's last store is its sequence word; the host polls the words in the pinned page instead of waiting for the
+// runtime to notice the kernel's completion signal (an interrupt or a slower poll: 10 us and more).
+int wait_for_rows(const trigram_map_t::One& O, uint32_t n_rows, int n_images, uint32_t seq) {
   uint64_t spins = 0;
-  for (int which = 0; which < (with_delta ? 2 : 1); ++which) {
-    volatile uint32_t* words = reinterpret_cast<volatile uint32_t*>(O.h_out + which * kOneHostBytes + kOneWordsAt);
+  for (int which = 0; which < n_images; ++which) {
+    volatile uint32_t* words = kPage.words(kPage.image(O.h_out, which));
     for (uint32_t r = 0; r < n_rows; ++r) {
       while (words[2 * r + 1] != seq) {
 #if defined(__x86_64__)
@@ -486,35 +477,63 @@ int find_few(trigram_map m, const char* const* s, const size_t* len, size_t n, u
     }
   }
   __atomic_thread_fence(__ATOMIC_ACQUIRE);
-  const volatile uint32_t* w0 = reinterpret_cast<const volatile uint32_t*>(O.h_out + kOneWordsAt);
-  const volatile uint32_t* w1 = reinterpret_cast<const volatile uint32_t*>(O.h_out + kOneHostBytes + kOneWordsAt);
-  for (uint32_t r = 0; r < n_rows; ++r) {
-    const uint32_t i = row_of[r];
-    const trigram_match_t* a_rows = reinterpret_cast<const trigram_match_t*>(O.h_out + r * kOneRowBytes);
-    const uint32_t got_a = w0[2 * r], na = got_a < limit ? got_a : uint32_t(limit);
+  return 0;
+}
+
+// The rows of the page to the caller: the base image's as they are, or a needle's two lists merged
+void rows_out(const FewCall& c, bool with_delta, trigram_match results, uint32_t* counts) {
+  unsigned char *page0 = kPage.image(c.m->one.h_out, 0), *page1 = kPage.image(c.m->one.h_out, 1);
+  const volatile uint32_t *w0 = kPage.words(page0), *w1 = kPage.words(page1);
+  const uint32_t limit = c.limit;
+  for (uint32_t r = 0; r < c.n_rows; ++r) {
+    const uint32_t i = c.row_of[r];
     trigram_match_t* out = results + size_t(i) * limit;
-    if (!with_delta) {
-      counts[i] = na;
-      std::memcpy(out, a_rows, size_t(na) * sizeof(trigram_match_t));
-      continue;
-    }
-    // result order: matches descending, weight ascending, reference ascending (storage.c:129-138, :566)
-    const trigram_match_t* b_rows = reinterpret_cast<const trigram_match_t*>(O.h_out + kOneHostBytes + r * kOneRowBytes);
-    const uint32_t got_b = w1[2 * r], nb_ = got_b < limit ? got_b : uint32_t(limit);
-    uint32_t ia = 0, ib = 0, k = 0;
-    while (k < limit && (ia < na || ib < nb_)) {
-      bool take_a;
-      if (ia >= na) take_a = false;
-      else if (ib >= nb_) take_a = true;
-      else {
-        const trigram_match_t x = a_rows[ia], y = b_rows[ib];
-        take_a = x.matches != y.matches ? x.matches > y.matches : x.weight != y.weight ? x.weight < y.weight : x.reference < y.reference;
-      }
-      out[k++] = take_a ? a_rows[ia++] : b_rows[ib++];
-    }
-    counts[i] = k;
+    if (with_delta) { counts[i] = merge_rows(kPage.rows(page0, r), w0[2 * r], kPage.rows(page1, r), w1[2 * r], limit, out); continue; }
+    const uint32_t got = w0[2 * r], na = got < limit ? got : limit;
+    counts[i] = na;
+    std::memcpy(out, kPage.rows(page0, r), size_t(na) * sizeof(trigram_match_t));
   }
-  O.taken += n_rows;
+}
+
+}  // namespace
+
+// The reference's only call shape (ext/blurrily/map_ext.c:131-162 -> storage.c:477-580), and small host-buffer batches
+// (a server's coalesced FINDs under light load).  needle i = s[i][0 .. len[i]) (up to its first NUL).  Returns 0 with
+// counts[] and rows filled (results + i * limit), -1 with errno, or kOneNotTaken when the finds have to go the batch's
+// way: a limit of 0 or above kOneMaxKeep, more than kMidMaxNeedles needles, a needle of more than 64 distinct trigrams,
+// timing or request counters switched on, option "one_launch" 0.  Mutations the base image does not hold yet are
+// served (DESIGN.md "Mutation and device sync"): deletes are tombstone bits the select looks at, pending puts live in a
+// small delta image searched by a SECOND launch -- a window or two: always the shared launch --, and the two lists of a
+// needle are merged here (they hold disjoint references).  A log that has overflowed is folded by ensure_device.
+int find_few(trigram_map m, const char* const* s, const size_t* len, size_t n, uint16_t limit, trigram_match results,
+             uint32_t* counts) {
+  if (!m->one.enabled || limit == 0 || limit > kOneMaxKeep || n == 0 || n > kMidMaxNeedles || m->timing || m->collect_stats)
+    return kOneNotTaken;
+  FewCall c;
+  c.m = m; c.limit = limit;
+  if (!tokenise_needles(c, s, len, n)) return kOneNotTaken;
+  DeviceScope scope(m->dev.device);
+  sort_dirty_buckets_of(c, n);
+  if (ensure_device(m) < 0) return -1;
+  const bool with_tomb = log_of(m)->n_tomb != 0, with_delta = !log_of(m)->pending.empty() && m->delta.device >= 0;
+  if (compact_rows(c, n, counts) == 0) return 0;
+  auto& O = m->one;
+  NameScope name_scope(&m->last_kernels);                 // (the launches below note their kernels' names in the map)
+  m->last_kernels.clear();
+  m->last_sweep = 0;                                      // (no sweep of a class of batches: a single launch, or latency mode)
+  if (make_page(O) < 0) return -1;
+  if (with_tomb && apply_tombstones(m, O.stream) < 0) return -1;       // (deletes since the last find: their bits are set first)
+  if (make_lists(O) < 0) return -1;
+  c.ranges = few_ranges(c.n_rows, O.few_max, O.mid_max, limit, m->dev.n_windows, size_t(m->n_cus) * find_wgs_per_cu(),
+                        m->latency_tasks, kLists.max_lists);
+  stage_needles(c, len);
+  c.seq = ++O.seq ? O.seq : ++O.seq;                      // (never 0: what the words hold before the first find)
+  const uint32_t* d_tomb = with_tomb ? m->dev.d_tomb : nullptr;
+  if ((c.mid() ? launch_latency(c, d_tomb) : launch_shared(c, m->dev, d_tomb, 0)) < 0) return -1;
+  if (with_delta && launch_shared(c, m->delta, nullptr, 1) < 0) return -1;
+  if (wait_for_rows(O, c.n_rows, with_delta ? 2 : 1, c.seq) < 0) return -1;
+  rows_out(c, with_delta, results, counts);
+  O.taken += c.n_rows;
   return 0;
 }
 

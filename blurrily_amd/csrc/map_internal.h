@@ -7,7 +7,7 @@
 //                    events); stage_string_needles
 //   multi_device.hip replicas, run_find_multi
 //   host_batch.hip   host-buffer batches: needle_len, longest_needle, BatchBlocks; the chunked pipeline,
-//                    find_batch_host, find_few
+//                    find_batch_host, find_few (its page and lists: find_few_layout.h; its decisions: find_choice.h)
 //   refs.hip         by reference: refs_extract, ExtractionOnHost, stage_reference_needles, get / find_references entries
 //   scope.hip        scoped find, a scope per needle; behind scope_internal.h with scope_similar.hip and scope_above.hip,
 //                    the scoped similarity and threshold finds
@@ -187,9 +187,9 @@ struct trigram_map_t {
   // sequence word into, the per-workgroup lists and the ticket on the device
   struct One {
     hipStream_t    stream = nullptr;
-    unsigned char* h_out = nullptr;     // per image: [kMidMaxNeedles][kOneMaxKeep] rows | [..][2] count, sequence word | codes | T (kOneHostBytes)
+    unsigned char* h_out = nullptr;     // per image: a page as find_few_layout.h lays it out (FewPage)
     unsigned char* d_out = nullptr;     // the same memory as the device addresses it
-    blurrily::detail::DeviceBuffer   d_parts;             // per image: [kOneMaxLists][kOneMaxKeep] keys | [kOneMaxLists] flags | [kMidMaxNeedles] tickets
+    blurrily::detail::DeviceBuffer   d_parts;             // per image: the lists as find_few_layout.h lays them out (FewLists)
     uint32_t       seq = 0;
     bool           enabled = true;      // option "one_launch"
     uint32_t       min_per = 0;         // option "one_windows_per_wg": at least this many windows per workgroup (0: as few as the grid allows)
@@ -290,6 +290,12 @@ struct MapImages {
   const uint32_t* tomb[2];
 };
 MapImages map_images(trigram_map m);                                                             // map_log.hip
+// What every find launch reads of the image it searches.
+inline void image_args(const DeviceIndex& ix, FindArgs* a) {
+  a->slice_se = ix.d_slice_se; a->ent = ix.d_ent; a->ref_of_rank = ix.d_ref_of_rank;
+  a->weight_of_rank = ix.d_weight_of_rank; a->n_refs = ix.n_refs; a->n_windows = ix.n_windows;
+  a->win_max_tri = ix.d_win_max_tri; a->nib_windows = ix.nib_windows; a->dense_min8 = ix.dense_min8;
+}
 // Windows per workgroup of a sweep over nc needles: a small batch spreads each needle's windows over the GPU, a large
 // one gives a needle one workgroup (at_least: a floor of the caller's).
 inline uint32_t windows_per_workgroup(const trigram_map_t* m, const DeviceIndex& ix, size_t nc, uint64_t at_least = 1) {

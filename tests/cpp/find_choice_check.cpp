@@ -1,5 +1,5 @@
-// find_choice_check.cpp -- the decisions of run_find_on (blurrily_amd/csrc/find_choice.h) against expectations written
-// down by hand from the expressions they were taken out of.  Stand-alone: tests/test_find_choice.py builds and runs it,
+// find_choice_check.cpp -- the decisions of run_find_on and find_few (blurrily_amd/csrc/find_choice.h) against expectations
+// written down by hand from the expressions they were taken out of.  Stand-alone: tests/test_find_choice.py builds and runs it,
 // once plainly and once under the address and undefined-behaviour sanitizers.
 #include "find_choice.h"
 
@@ -33,6 +33,131 @@ static void the_latency_ranges() {
                                      r.tasks_per_wg, got, r.ranges);
     EXPECT(got == r.ranges);
   }
+}
+
+// find_few's ranges: the shared launch outside few_max < n_rows <= mid_max, latency_ranges inside, lowered to 4 608 lists
+static void the_ranges_of_a_few() {
+  const size_t rows[] = {2, 24, 25, 60, 61, 128}, wgs[] = {608, 1216};
+  const uint32_t limits[] = {1, 10, 120}, windows[] = {2, 3, 5, 129, 515};
+  for (size_t n : rows)
+    for (uint32_t limit : limits)
+      for (uint32_t w : windows)
+        for (size_t g : wgs) {
+          // "latency_tasks" 0: the product always fits, the rule's own value; the defaults' gate (24, 128) and none (1, 128)
+          const uint32_t rule = latency_ranges(n, limit, w, g, 0);
+          EXPECT(n * rule <= 4608);
+          EXPECT(few_ranges(n, 24, 128, limit, w, g, 0, 4608) == (n > 24 ? rule : 1u));
+          EXPECT(few_ranges(n, 1, 128, limit, w, g, 0, 4608) == rule);
+          EXPECT(few_ranges(n, 1, uint32_t(n) - 1, limit, w, g, 0, 4608) == 1);      // beyond mid_max
+          if (w < 129) continue;
+          for (uint32_t tasks : {8u, 16u}) {                // the option that reaches the bound
+            const uint32_t free_ = latency_ranges(n, limit, w, g, tasks), got = few_ranges(n, 1, 128, limit, w, g, tasks, 4608);
+            EXPECT(got >= 1 && n * got <= 4608);
+            if (n * free_ <= 4608) EXPECT(got == free_);
+            else EXPECT(n * got >= 4608 - n + 1);           // no more taken than it must
+          }
+        }
+  // by hand: 25 needles on 608 workgroups 608 / 25 = 24 ranges, 128 needles two tasks a workgroup, 1 216 / 128 = 9;
+  // sixteen tasks a workgroup: 9 728 / 128 = 76 ranges, 9 728 tasks, lowered to 4 608 / 128 = 36; 25 needles at limit 1
+  // on 1 216 workgroups: 258 window pairs each, 6 450 tasks, lowered to 4 608 / 25 = 184
+  EXPECT(few_ranges(25, 24, 128, 10, 515, 608, 0, 4608) == 24);
+  EXPECT(few_ranges(128, 24, 128, 10, 515, 608, 0, 4608) == 9);
+  EXPECT(latency_ranges(128, 10, 515, 608, 16) == 76 && few_ranges(128, 24, 128, 10, 515, 608, 16, 4608) == 36);
+  EXPECT(latency_ranges(25, 1, 515, 1216, 16) == 258 && few_ranges(25, 24, 128, 1, 515, 1216, 16, 4608) == 184);
+}
+
+static void the_merges_pool() {
+  EXPECT(merge_pool_cap(1, 1) == 1024 && merge_pool_cap(8, 128) == 1024);      // ranges * limit 1 024
+  EXPECT(merge_pool_cap(41, 25) == 2048);                                      // 1 025
+  EXPECT(merge_pool_cap(2047, 1) == 2048 && merge_pool_cap(64, 64) == 4096 && merge_pool_cap(4097, 1) == 8192);
+}
+
+// the shared launch's {windows per workgroup, workgroups per needle}: the three rules' figures at 288 workgroups and 4 608
+// lists, where the lists' bound never binds; then where option "mid_workgroups" makes it bind
+static void the_shape_of_the_shared_launch() {
+  const uint32_t windows[7] = {1, 2, 129, 288, 289, 577, 1200}, rows[6] = {1, 8, 9, 16, 17, 128};
+  const uint32_t mid_workgroups[3] = {64, 256, 1024}, min_per[2] = {0, 2};
+  static const OneGrid want[2][3][7][6] = {{
+    // min_per 0, mid_workgroups 64
+    {
+     {{1, 1}, {1, 1}, {1, 1}, {1, 1}, {1, 1}, {1, 1}},   // 1 window
+     {{1, 2}, {1, 2}, {1, 2}, {1, 2}, {1, 2}, {1, 2}},   // 2 windows
+     {{1, 129}, {1, 129}, {20, 7}, {34, 4}, {44, 3}, {66, 2}},   // 129 windows
+     {{1, 288}, {1, 288}, {42, 7}, {72, 4}, {96, 3}, {144, 2}},   // 288 windows
+     {{2, 145}, {2, 145}, {42, 7}, {74, 4}, {98, 3}, {146, 2}},   // 289 windows
+     {{4, 145}, {4, 145}, {84, 7}, {146, 4}, {194, 3}, {290, 2}},   // 577 windows
+     {{6, 200}, {6, 200}, {172, 7}, {300, 4}, {400, 3}, {600, 2}},   // 1200 windows
+    },
+    // min_per 0, mid_workgroups 256
+    {
+     {{1, 1}, {1, 1}, {1, 1}, {1, 1}, {1, 1}, {1, 1}},
+     {{1, 2}, {1, 2}, {1, 2}, {1, 2}, {1, 2}, {1, 2}},
+     {{1, 129}, {1, 129}, {6, 22}, {10, 13}, {10, 13}, {66, 2}},
+     {{1, 288}, {1, 288}, {12, 24}, {18, 16}, {20, 15}, {144, 2}},
+     {{2, 145}, {2, 145}, {12, 25}, {20, 15}, {20, 15}, {146, 2}},
+     {{4, 145}, {4, 145}, {22, 27}, {38, 16}, {40, 15}, {290, 2}},
+     {{6, 200}, {6, 200}, {44, 28}, {76, 16}, {80, 15}, {600, 2}},
+    },
+    // min_per 0, mid_workgroups 1024
+    {
+     {{1, 1}, {1, 1}, {1, 1}, {1, 1}, {1, 1}, {1, 1}},
+     {{1, 2}, {1, 2}, {1, 2}, {1, 2}, {1, 2}, {1, 2}},
+     {{1, 129}, {1, 129}, {2, 65}, {4, 33}, {4, 33}, {18, 8}},
+     {{1, 288}, {1, 288}, {4, 72}, {6, 48}, {6, 48}, {36, 8}},
+     {{2, 145}, {2, 145}, {4, 73}, {6, 49}, {6, 49}, {38, 8}},
+     {{4, 145}, {4, 145}, {6, 97}, {10, 58}, {10, 58}, {74, 8}},
+     {{6, 200}, {6, 200}, {12, 100}, {20, 60}, {20, 60}, {150, 8}},
+    }}, {
+    // min_per 2, mid_workgroups 64
+    {
+     {{2, 1}, {2, 1}, {2, 1}, {2, 1}, {2, 1}, {2, 1}},
+     {{2, 1}, {2, 1}, {2, 1}, {2, 1}, {2, 1}, {2, 1}},
+     {{2, 65}, {2, 65}, {20, 7}, {34, 4}, {44, 3}, {66, 2}},
+     {{2, 144}, {2, 144}, {42, 7}, {72, 4}, {96, 3}, {144, 2}},
+     {{2, 145}, {2, 145}, {42, 7}, {74, 4}, {98, 3}, {146, 2}},
+     {{4, 145}, {4, 145}, {84, 7}, {146, 4}, {194, 3}, {290, 2}},
+     {{6, 200}, {6, 200}, {172, 7}, {300, 4}, {400, 3}, {600, 2}},
+    },
+    // min_per 2, mid_workgroups 256
+    {
+     {{2, 1}, {2, 1}, {2, 1}, {2, 1}, {2, 1}, {2, 1}},
+     {{2, 1}, {2, 1}, {2, 1}, {2, 1}, {2, 1}, {2, 1}},
+     {{2, 65}, {2, 65}, {6, 22}, {10, 13}, {10, 13}, {66, 2}},
+     {{2, 144}, {2, 144}, {12, 24}, {18, 16}, {20, 15}, {144, 2}},
+     {{2, 145}, {2, 145}, {12, 25}, {20, 15}, {20, 15}, {146, 2}},
+     {{4, 145}, {4, 145}, {22, 27}, {38, 16}, {40, 15}, {290, 2}},
+     {{6, 200}, {6, 200}, {44, 28}, {76, 16}, {80, 15}, {600, 2}},
+    },
+    // min_per 2, mid_workgroups 1024
+    {
+     {{2, 1}, {2, 1}, {2, 1}, {2, 1}, {2, 1}, {2, 1}},
+     {{2, 1}, {2, 1}, {2, 1}, {2, 1}, {2, 1}, {2, 1}},
+     {{2, 65}, {2, 65}, {2, 65}, {4, 33}, {4, 33}, {18, 8}},
+     {{2, 144}, {2, 144}, {4, 72}, {6, 48}, {6, 48}, {36, 8}},
+     {{2, 145}, {2, 145}, {4, 73}, {6, 49}, {6, 49}, {38, 8}},
+     {{4, 145}, {4, 145}, {6, 97}, {10, 58}, {10, 58}, {74, 8}},
+     {{6, 200}, {6, 200}, {12, 100}, {20, 60}, {20, 60}, {150, 8}},
+    }}};
+  for (int p = 0; p < 2; ++p)
+    for (int m = 0; m < 3; ++m)
+      for (int w = 0; w < 7; ++w)
+        for (int r = 0; r < 6; ++r) {
+          const OneGrid got = one_grid(windows[w], rows[r], mid_workgroups[m], min_per[p], 288, 4608), &exp = want[p][m][w][r];
+          if (got.per != exp.per || got.grid != exp.grid)
+            std::printf("one_grid(%u, %u, %u, %u) = {%u, %u}, not {%u, %u}\n", windows[w], rows[r], mid_workgroups[m], min_per[p],
+                        got.per, got.grid, exp.per, exp.grid);
+          EXPECT(got.per == exp.per && got.grid == exp.grid);
+        }
+  // "mid_workgroups" 8 192, 40 needles, 130 windows: the three rules give a window per workgroup, 130 * 40 = 5 200 lists;
+  // 4 608 / 40 = 115 workgroups per needle fit, so a window pair each: 65 * 40 = 2 600
+  const OneGrid g = one_grid(130, 40, 8192, 0, 288, 4608);
+  EXPECT(g.per == 2 && g.grid == 65 && g.grid * 40 <= 4608);
+  // ... at its largest, on 288 windows and 128 needles: 36 workgroups per needle fit, eight windows each
+  const OneGrid h = one_grid(288, 128, 65536, 0, 288, 4608);
+  EXPECT(h.per == 8 && h.grid == 36 && h.grid * 128 == 4608);
+  // ... and in whole window pairs: 100 windows over 36 workgroups are three each, so four
+  const OneGrid k = one_grid(100, 128, 65536, 0, 288, 4608);
+  EXPECT(k.per == 4 && k.grid == 25);
 }
 
 static void the_static_rule() {
@@ -177,6 +302,9 @@ int main() {
   the_class();
   the_order_of_a_measurement();
   the_latency_ranges();
+  the_ranges_of_a_few();
+  the_merges_pool();
+  the_shape_of_the_shared_launch();
   the_static_rule();
   the_pick();
   the_watch();

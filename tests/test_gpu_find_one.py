@@ -334,6 +334,41 @@ def test_latency_mode_over_the_pinned_page_at_its_edges(geo):
             m.set_option(key, value)
 
 
+@pytest.mark.parametrize("limit", [10, 120])
+def test_the_shared_launch_and_latency_mode_take_turns_on_one_map(geo, limit):
+    """find_few's two ways by turns on ONE map's page and lists (find_few_layout.h): single finds, a latency-mode batch,
+    singles, a batch whose needles travel as kernel arguments (completion flags), one whose codes come from the page
+    (tickets), latency mode again, singles again -- every row against the live reference, and last_kernels() naming
+    each call's launches.  Latency mode's counts have words of their own behind the lists; that they are clear of the
+    flags is tests/cpp/find_few_layout_check.cpp's to show, not this test's: a flag met early is a matter of timing."""
+    m, chk, strings = geo
+    rng = np.random.default_rng(330 + limit)
+    pick = lambda k: [strings[int(i)] for i in rng.integers(0, len(strings), size=k)]
+    shared, latency = ["find_one_kernel<1024>"], ["find_kernel<uint8_t,1024,true,true>", "merge_parts_pinned_kernel"]
+
+    def singles():
+        for nd in pick(4):
+            assert _find(m, nd, limit) == chk.find(nd, limit), (nd, limit)
+            assert m.last_kernels() == shared
+
+    def batch(n, kernels):
+        needles = pick(n)
+        rows, counts = m.find_batch_packed(*_pack(needles), limit)
+        assert m.last_kernels() == kernels, (n, limit)
+        for i, nd in enumerate(needles):
+            assert rows[i, :counts[i]].tolist() == chk.find(nd, limit), (n, limit, nd)
+
+    taken = m.get_option("one_taken")
+    singles()
+    batch(40, latency)
+    singles()
+    batch(12, shared)
+    batch(20, shared)
+    batch(40, latency)
+    singles()
+    assert m.get_option("one_taken") - taken == 3 * 4 + 40 + 12 + 20 + 40     # (haystack strings: every needle has postings)
+
+
 @pytest.mark.parametrize("n", [17, 32, 64, 128])
 def test_a_servers_coalesced_finds_share_one_launch(geo, n):
     """The same launch for up to 128 needles (option "few_max" raised to the kernel's limit): codes from the pinned page, a
