@@ -125,6 +125,8 @@ enum : uint32_t {
   kStatSlots          = 8,   // what blurrily_storage_find_stats reports
   kStatWsClocks       = 8,   // + 0..5: shader clocks of wave 0 per phase of wsweep_kernel, summed over workgroups
                              //   (filter, task set-up, count, scan, probe, select + write-back); debugging aid
+  kStatStepsPastDesc  = 14,  // needle-major steps of more than kDescUnits units (needle_major.inc): a worker walks the slice table
+                             //   for the units behind its descriptors; of kStatSteps (blurrily_debug_find_stats16)
   kStatAllSlots       = 16,
 };
 

@@ -30,6 +30,25 @@ __device__ __forceinline__ uint32_t wave_inclusive_sum(uint32_t x) {
 #undef BLURRILY_DPP_ADD
   return x;
 }
+// Fill-forward over the 64 lanes of a wave with the same moves: a lane whose d.y is 0 takes the pair of the nearest
+// lane below it whose d.y is not (none: it stays 0) -- "mine if I have one, else theirs" is associative, so the
+// scan's steps apply as they do to the sum.
+__device__ __forceinline__ void wave_fill_forward(uint2& d) {
+#define BLURRILY_DPP_FILL(ctrl_, rows_)                                                                        \
+  do {                                                                                                         \
+    const uint32_t px_ = uint32_t(__builtin_amdgcn_update_dpp(0, int(d.x), ctrl_, rows_, 0xF, false));         \
+    const uint32_t py_ = uint32_t(__builtin_amdgcn_update_dpp(0, int(d.y), ctrl_, rows_, 0xF, false));         \
+    const bool none_ = d.y == 0;                                                                               \
+    d.x = none_ ? px_ : d.x; d.y = none_ ? py_ : d.y;                                                          \
+  } while (0)
+  BLURRILY_DPP_FILL(0x111, 0xF);                                // row_shr:1
+  BLURRILY_DPP_FILL(0x112, 0xF);                                // row_shr:2
+  BLURRILY_DPP_FILL(0x114, 0xF);                                // row_shr:4
+  BLURRILY_DPP_FILL(0x118, 0xF);                                // row_shr:8
+  BLURRILY_DPP_FILL(0x142, 0xA);                                // row_bcast:15 -> rows 1 and 3
+  BLURRILY_DPP_FILL(0x143, 0xC);                                // row_bcast:31 -> rows 2 and 3
+#undef BLURRILY_DPP_FILL
+}
 
 struct UnitRing {
   // a step's header, ONE 16-byte read: .x the step the slot's table belongs to (past the end: none left); .y its units (bits
@@ -40,10 +59,18 @@ struct UnitRing {
   // per step (e & 3: a step's candidates are settled while the step after the next is being published) and window
   // parity: where the postings of the slices LEFT OUT of the count start in `ent` (their bitmaps sit in front of them)
   uint32_t hot[4][2][8];
-  // behind it: the two slots' tables (BLURRILY_TAB: 2 x 64 x 16 bytes, BLURRILY_BND: 2 x 64 x 8 bytes) in an area of
-  // 2 x ring_units_for(pool_cap) x 8 bytes; pend[2][kPendMax]
+  // behind it, in an area of 2 x ring_units_for(pool_cap) x 8 bytes: the two slots' tables (BLURRILY_TAB: 2 x 64 x 16
+  // bytes, BLURRILY_BND: 2 x 64 x 8 bytes -- what a step of more than kDescUnits units, and a step swept again, are
+  // walked by) and the two slots' unit descriptors (BLURRILY_DESC: 2 x kDescUnits x 8 bytes: entry k = unit k of the
+  // step, .x its first entry in `ent`, .y where its slice ends | its window's parity -- all a worker reads of a step
+  // of up to kDescUnits units); behind the area: pend[2][kPendMax]
 };
 constexpr uint32_t kNmMaxLeftOut = 8;                           // slices left out of one window's count at most (UnitRing::hot)
+constexpr uint32_t kDescUnits = 64;                             // units of a step the manager publishes descriptors of (a lane each)
+static_assert(kDescUnits == 64, "a lane of the manager per descriptor");
+constexpr uint32_t kRingTableBytes = 2 * 64 * 16 + 2 * 64 * 8 + 2 * kDescUnits * 8;
+static_assert(kRingTableBytes <= 2 * ring_units_for(512) * 8 && kRingTableBytes <= 2 * ring_units_for(1024) * 8,
+              "tables and descriptors lie in the ring area, in front of the pending lists (8 KiB and 4 KiB areas)");
 // the pending lists: behind the descriptors in the dynamic LDS
 __device__ __forceinline__ uint32_t* pend_list(UnitRing* ring, uint32_t slot, uint32_t ring_units) {
   return reinterpret_cast<uint32_t*>(reinterpret_cast<uint2*>(ring + 1) + 2 * ring_units) + slot * kPendMax;
@@ -60,6 +87,14 @@ __device__ __forceinline__ bool coop_can_leave(const FindArgs& A) {
 // behind its scan a worker's first unit of the next step -- loads that are meant to travel across the barriers.  The
 // waves of a sweep exchange data through LDS only.
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+// Between LDS stores of a wave's lanes and reads of them by OTHER lanes of the same wave: no instruction -- the LDS
+// serves a wave's accesses in order -- but the compiler, to which lanes are threads, may otherwise hand a lane its own
+// earlier store for the read (it did: the descriptors' read-back moved under the storing lanes' branch).
+__device__ __forceinline__ void wave_lds_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
 
 // why sweep_coop's hot loop was left
 enum : uint32_t { kLeftDone = 0, kLeftSlowScan = 2, kLeftSelect = 3 };
@@ -189,8 +224,24 @@ __device__ __forceinline__ void sweep_role(const FindArgs& A, const Needle& nd, 
   // step cost 15 % where 64 more VALU cost 9 %).  (Through
   // round-4's first version the manager listed every UNIT -- a store per unit from lanes looping over their slices,
   // queued behind the workers' atomics: 4 300 clocks per step, the wave the count barrier waited for in nine steps of ten.)
+  // Since the unit descriptors (BLURRILY_DESC) a worker goes through table and sums only for the units kDescUnits and
+  // up of a step that has them, and for a step swept again; the search above is then the manager's, once, for the
+  // step's first kDescUnits units: lane k = unit k.  No loop over units and no store per unit: a slice's lane stores
+  // its biased start and its end | parity where its FIRST unit's descriptor lies, the wave reads the 64 entries back --
+  // the one LDS round trip of a publish -- and every lane takes the entry of the last slice that starts at or in front
+  // of it (a fill-forward over the lanes in DPP moves); the unit's first entry is that start + 512 k.
 #define BLURRILY_TAB(s_) (reinterpret_cast<uint4*>(ring + 1) + (s_) * 64u)
 #define BLURRILY_BND(s_) (reinterpret_cast<uint2*>(reinterpret_cast<uint4*>(ring + 1) + 128u) + (s_) * 64u)
+#define BLURRILY_DESC(s_) (reinterpret_cast<uint2*>(reinterpret_cast<uint4*>(ring + 1) + 128u) + 128u + (s_) * kDescUnits)
+  // the descriptors of a worker's units of ring slot s_: lane j its j-th (unit wid + kWorkers j) of the first kDescUnits
+#define BLURRILY_DESC_MINE(s_) (BLURRILY_DESC(s_)[min(wid + kWorkers * lane, kDescUnits - 1u)])
+  // scalar bounds of a worker's j_-th unit from its descriptors ds_
+#define BLURRILY_UNIT_AT(ds_, j_, start_, end_, half_)                           \
+  do {                                                                           \
+    start_ = __builtin_amdgcn_readlane((ds_).x, (j_));                           \
+    end_ = __builtin_amdgcn_readlane((ds_).y, (j_));                             \
+    half_ = kNib ? (end_) & 1u : 0u;                                             \
+  } while (0)
   // scalar bounds of the step's unit k_ from the table in tb_ / its sums bd_ (E_: the even window's units)
 #define BLURRILY_UNIT_OF(tb_, bd_, E_, k_, start_, end_, half_)                  \
   do {                                                                           \
@@ -267,10 +318,24 @@ __device__ __forceinline__ void sweep_role(const FindArgs& A, const Needle& nd, 
     const uint32_t even_ = __builtin_amdgcn_readlane(incl0_, 63);                \
     const uint32_t incl1_ = kNib ? even_ + wave_inclusive_sum(units1_) : even_;  \
     const uint32_t total_ = kNib ? __builtin_amdgcn_readlane(incl1_, 63) : even_; \
+    const uint32_t ex0_ = incl0_ - units0_, ex1_ = incl1_ - units1_;             /* the slices' first units */ \
+    const uint32_t bs0_ = (A0) - (ex0_ << 9), bs1_ = (A1) - (ex1_ << 9);         /* their biased starts */ \
+    /* the descriptors' round trip first: the table's stores travel behind it.  (Slices end on multiples of eight \
+       entries -- device_index.hip --: bit 0 of an end is free for the parity, and an end with units is not 0.) */ \
+    uint2* const dsc_ = BLURRILY_DESC(s_);                                       \
+    dsc_[lane] = make_uint2(0u, 0u);                                             \
+    wave_lds_sync();                                                             \
+    if (units0_ && ex0_ < kDescUnits) dsc_[ex0_] = make_uint2(bs0_, (B0));       \
+    if (kNib && units1_ && ex1_ < kDescUnits) dsc_[ex1_] = make_uint2(bs1_, (B1) | 1u); \
+    wave_lds_sync();                            /* (lanes read what OTHER lanes stored) */ \
+    const unsigned long long dq_ = __hip_atomic_load(reinterpret_cast<unsigned long long*>(dsc_ + lane), __ATOMIC_RELAXED, \
+                                                     __HIP_MEMORY_SCOPE_WAVEFRONT); \
+    uint2 d_ = make_uint2(uint32_t(dq_), uint32_t(dq_ >> 32));                   \
     /* (a slice left out of the count lists no units: it is published as empty) */ \
-    BLURRILY_TAB(s_)[lane] = make_uint4((A0) - ((incl0_ - units0_) << 9), (A1) - ((incl1_ - units1_) << 9), \
-                                        units0_ ? (B0) : (A0) - ((incl0_ - units0_) << 9), units1_ ? (B1) : (A1) - ((incl1_ - units1_) << 9)); \
+    BLURRILY_TAB(s_)[lane] = make_uint4(bs0_, bs1_, units0_ ? (B0) : bs0_, units1_ ? (B1) : bs1_); \
     BLURRILY_BND(s_)[lane] = make_uint2(incl0_, incl1_);                         \
+    wave_fill_forward(d_);                                                       \
+    dsc_[lane] = make_uint2(d_.x + (lane << 9), d_.y);   /* (lanes past the step's units: never read) */ \
     /* the scan's bound, lowered by the most slices either window leaves out (a harvested counter is settled    \
        exactly, so a bound that is too low for the other window costs a look, nothing else) */ \
     const uint32_t lmost_ = max(ls_ & 15u, ls_ >> 4);                            \
@@ -282,35 +347,49 @@ __device__ __forceinline__ void sweep_role(const FindArgs& A, const Needle& nd, 
   // test before the atomics.  A unit's address is a scalar base (its first entry) plus the lane's 16 bytes:
   // nothing per unit and lane but the load itself and one compare.  (Up to four of a wave's units loaded before
   // the first is counted -- four loads in flight -- measured in round 3: 3.2 % SLOWER, 317.2 vs 307.4 ms.)
+#define BLURRILY_UNIT_STEP(x_, y_, h_)                                           \
+  do {                                                                           \
+    const bool live_ = lane8p < (y_) - (x_);    /* (y_ may carry the parity in bit 0: lane8p = 8 lane + 1) */ \
+    uint4 v_ = pend_;                                                            \
+    if (live_) v_ = *reinterpret_cast<const uint4*>(reinterpret_cast<const unsigned char*>(A.ent + (x_)) + lane16); \
+    if (STATS(A)) st_ent += min(512u, ((y_) & ~1u) - (x_));                      \
+    if (pend_live_) bump_unit_loaded<CT>(cnt32, pend_, pend_h_);                 \
+    pend_ = v_; pend_h_ = (h_); pend_live_ = live_;                              \
+  } while (0)
+  // (a worker's j-th unit of the step's first kDescUnits: two v_readlane of its descriptors, read a step ago behind the
+  // count barrier; the units behind them, of the few steps that have any: table and sums, read here)
 #define BLURRILY_COUNT_UNITS(s_, n_, have_mine_)                                 \
   do {                                                                           \
     uint4 pend_ = make_uint4(0, 0, 0, 0);                                        \
     uint32_t pend_h_ = 0;                                                        \
     bool pend_live_ = false;                                                     \
-    uint4 tl_ = tb_mine;                        /* (read a step ago, behind the count barrier) */ \
-    uint2 bl_ = bd_mine;                                                         \
-    if (!(have_mine_)) { tl_ = BLURRILY_TAB(s_)[lane]; bl_ = BLURRILY_BND(s_)[lane]; } \
-    const uint32_t even_ = kNib ? __builtin_amdgcn_readlane(bl_.x, 63) : 0u;     \
-    uint32_t k_ = wid;                                                           \
+    uint2 dl_ = ds_mine;                                                         \
+    if (!(have_mine_)) dl_ = BLURRILY_DESC_MINE(s_);                             \
+    uint32_t k_ = wid, j_ = 0;                                                   \
     if ((have_mine_) && pre_valid) {            /* the first unit is on its way since the scan before */ \
       pend_ = pre_v; pend_h_ = pre_h; pend_live_ = pre_live;                     \
       if (STATS(A) && wid < (n_)) {                                              \
-        uint32_t x_, y_, h_;                                                     \
-        BLURRILY_UNIT_OF(tl_, bl_, even_, wid, x_, y_, h_);                      \
-        st_ent += min(512u, y_ - x_);                                            \
+        const uint32_t x_ = __builtin_amdgcn_readlane(dl_.x, 0), y_ = __builtin_amdgcn_readlane(dl_.y, 0); \
+        st_ent += min(512u, (y_ & ~1u) - x_);                                    \
       }                                                                          \
-      k_ = wid + kWorkers;                                                       \
+      k_ = wid + kWorkers; j_ = 1;                                               \
     }                                                                            \
     pre_valid = false;                                                           \
-    for (; k_ < (n_); k_ += kWorkers) {                                          \
+    const uint32_t nd_ = min((n_), kDescUnits);                                  \
+    for (; k_ < nd_; k_ += kWorkers, ++j_) {                                     \
       uint32_t x_, y_, h_;                                                       \
-      BLURRILY_UNIT_OF(tl_, bl_, even_, k_, x_, y_, h_);                         \
-      const bool live_ = lane8 < y_ - x_;                                        \
-      uint4 v_ = pend_;                                                          \
-      if (live_) v_ = *reinterpret_cast<const uint4*>(reinterpret_cast<const unsigned char*>(A.ent + x_) + lane16); \
-      if (STATS(A)) st_ent += min(512u, y_ - x_);                                \
-      if (pend_live_) bump_unit_loaded<CT>(cnt32, pend_, pend_h_);               \
-      pend_ = v_; pend_h_ = h_; pend_live_ = live_;                              \
+      BLURRILY_UNIT_AT(dl_, j_, x_, y_, h_);                                     \
+      BLURRILY_UNIT_STEP(x_, y_, h_);                                            \
+    }                                                                            \
+    if ((n_) > kDescUnits) {                    /* (uniform: the header's count) */ \
+      const uint4 tl_ = BLURRILY_TAB(s_)[lane];                                  \
+      const uint2 bl_ = BLURRILY_BND(s_)[lane];                                  \
+      const uint32_t even_ = kNib ? __builtin_amdgcn_readlane(bl_.x, 63) : 0u;   \
+      for (; k_ < (n_); k_ += kWorkers) {                                        \
+        uint32_t x_, y_, h_;                                                     \
+        BLURRILY_UNIT_OF(tl_, bl_, even_, k_, x_, y_, h_);                       \
+        BLURRILY_UNIT_STEP(x_, y_, h_);                                          \
+      }                                                                          \
     }                                                                            \
     if (pend_live_) bump_unit_loaded<CT>(cnt32, pend_, pend_h_);                 \
   } while (0)
@@ -333,9 +412,8 @@ __device__ __forceinline__ void sweep_role(const FindArgs& A, const Needle& nd, 
     pre_live = false;                                                            \
     if (pre_valid && wid < nn_) {                                                \
       uint32_t x_, y_;                                                           \
-      const uint32_t even_ = kNib ? __builtin_amdgcn_readlane(bd_mine.x, 63) : 0u; \
-      BLURRILY_UNIT_OF(tb_mine, bd_mine, even_, wid, x_, y_, pre_h);             \
-      pre_live = lane8 < y_ - x_;                                                \
+      BLURRILY_UNIT_AT(ds_mine, 0u, x_, y_, pre_h);                              \
+      pre_live = lane8p < y_ - x_;                                               \
       if (pre_live) pre_v = *reinterpret_cast<const uint4*>(reinterpret_cast<const unsigned char*>(A.ent + x_) + lane16); \
     }                                                                            \
   } while (0)
@@ -413,9 +491,9 @@ __device__ __forceinline__ void sweep_role(const FindArgs& A, const Needle& nd, 
     }                                                                            \
   } while (0)
 
-  const uint32_t lane8 = lane * 8, lane16 = lane * 16;
+  const uint32_t lane8p = lane * 8 + 1, lane16 = lane * 16;     // (lane8p: BLURRILY_UNIT_STEP)
   PHASE_DECL;
-  uint32_t st_ent = 0, st_tab = 0, st_steps = 0, st_redo = 0;    // request counters (FindArgs::stats), wave-uniform
+  uint32_t st_ent = 0, st_tab = 0, st_steps = 0, st_redo = 0, st_past = 0;   // request counters (FindArgs::stats), wave-uniform
   // ---- the manager's state: the needle's codes, the table it will publish next and its visit index, the step before
   uint32_t mcode = 0, ta = 0, tb = 0, ta1 = 0, tb1 = 0, my_i = 0, p_prev = 0, ls_prev = 0;
   uint32_t rk0 = 0xFFu, rk1 = 0xFFu;                            // ranks of the held table's slices (BLURRILY_RANK)
@@ -426,13 +504,12 @@ __device__ __forceinline__ void sweep_role(const FindArgs& A, const Needle& nd, 
   thr_c = (static_cast<unsigned long long>(__builtin_amdgcn_readfirstlane(uint32_t(thr_c >> 32))) << 32) |
           __builtin_amdgcn_readfirstlane(uint32_t(thr_c));
   // ---- a worker's: its units of the step about to start (lane j: its j-th), the first of them loaded ahead
-  uint4 tb_mine = make_uint4(0, 0, 0, 0);
-  uint2 bd_mine = make_uint2(0, 0);
+  uint2 ds_mine = make_uint2(0, 0);
   uint4 pre_v = make_uint4(0, 0, 0, 0);
   uint32_t pre_h = 0;
   bool pre_live = false, pre_valid = false;
   (void)rk0; (void)rk1; (void)ranked; (void)wm_l; (void)wm_base; (void)thr_c; (void)mcode; (void)ta; (void)tb; (void)ta1; (void)tb1; (void)my_i; (void)p_prev; (void)ls_prev;
-  (void)tb_mine; (void)bd_mine; (void)pre_v; (void)pre_h; (void)pre_live; (void)pre_valid; (void)lane8; (void)lane16; (void)pend_cap;
+  (void)ds_mine; (void)pre_v; (void)pre_h; (void)pre_live; (void)pre_valid; (void)lane8p; (void)lane16; (void)pend_cap;
   if (MANAGER) PATH_FLAG(A, nd.q, kNib ? kPathNibble : kPathByte);
   if constexpr (MANAGER) {
     __builtin_amdgcn_s_setprio(3);                              // the wave everybody's next step waits for
@@ -447,7 +524,7 @@ __device__ __forceinline__ void sweep_role(const FindArgs& A, const Needle& nd, 
   const uint32_t scan_cap = min(tc, ScanTraits<CT>::kMaxCount);  // a counter of this sweep cannot exceed it
   __syncthreads();
   uint4 h_next = ring->hdr4[0];                                  // header of the step about to start
-  if constexpr (!MANAGER) { tb_mine = BLURRILY_TAB(0u)[lane]; bd_mine = BLURRILY_BND(0u)[lane]; }
+  if constexpr (!MANAGER) ds_mine = BLURRILY_DESC_MINE(0u);
 
   // The sweep is a HOT LOOP of steps that need nothing special -- header, units (the manager: its turn), barrier,
   // scan with the published bound (the manager: the step before's pending candidates), barrier, a glance at the pool --
@@ -464,6 +541,7 @@ __device__ __forceinline__ void sweep_role(const FindArgs& A, const Needle& nd, 
       n_units = hy_ & 0xFFFFu;
       if (p >= v1) { left = kLeftDone; break; }                 // no step left
       ++st_steps;
+      if (STATS(A) && n_units > kDescUnits) ++st_past;
       if constexpr (MANAGER) __builtin_amdgcn_s_setprio(3);     // (the rare paths leave it at 0)
       PHASE_MARK(0);                                            // loop overhead
       const bool tr_ = MANAGER || wid == 0;
@@ -484,7 +562,7 @@ __device__ __forceinline__ void sweep_role(const FindArgs& A, const Needle& nd, 
       // (this step's scan constants are taken out of the header before the next one is requested over it)
       const uint32_t nq_bias_ = __builtin_amdgcn_readfirstlane(h_next.z), nq_pre_ = __builtin_amdgcn_readfirstlane(h_next.w);
       h_next = ring->hdr4[s ^ 1u];
-      if constexpr (!MANAGER) { tb_mine = BLURRILY_TAB(s ^ 1u)[lane]; bd_mine = BLURRILY_BND(s ^ 1u)[lane]; }
+      if constexpr (!MANAGER) ds_mine = BLURRILY_DESC_MINE(s ^ 1u);
       if constexpr (MANAGER) {
         if (can_leave) {                                        // while the workers scan
           BLURRILY_PEND_SETTLE(s ^ 1u, (e - 1u) & 3u, p_prev, ls_prev);
@@ -564,7 +642,7 @@ __device__ __forceinline__ void sweep_role(const FindArgs& A, const Needle& nd, 
     have_thr = thr_c != kKeyInf;
     ++e;
     h_next = ring->hdr4[e & 1];                                 // (published behind step p's count barrier)
-    if constexpr (!MANAGER) { tb_mine = BLURRILY_TAB(e & 1)[lane]; bd_mine = BLURRILY_BND(e & 1)[lane]; }
+    if constexpr (!MANAGER) ds_mine = BLURRILY_DESC_MINE(e & 1);
   }
   if constexpr (MANAGER) PHASE_FLUSH_MANAGER(A); else PHASE_FLUSH(A);
   // (counted build: the needle's steps, summed over its sweeps, in bits 31:23 of its path word -- tools/steps_hist.py)
@@ -575,6 +653,7 @@ __device__ __forceinline__ void sweep_role(const FindArgs& A, const Needle& nd, 
     if (wid == 0) {
       atomicAdd(&STATS(A)[kStatSteps], static_cast<unsigned long long>(st_steps));
       atomicAdd(&STATS(A)[kStatResweeps], static_cast<unsigned long long>(st_redo));
+      atomicAdd(&STATS(A)[kStatStepsPastDesc], static_cast<unsigned long long>(st_past));
     }
   }
   if constexpr (MANAGER) __builtin_amdgcn_s_setprio(0);
@@ -583,12 +662,16 @@ __device__ __forceinline__ void sweep_role(const FindArgs& A, const Needle& nd, 
 #undef BLURRILY_MANAGER_TURN
 #undef BLURRILY_COUNT_WALK
 #undef BLURRILY_COUNT_UNITS
+#undef BLURRILY_UNIT_STEP
 #undef BLURRILY_PRELOAD
 #undef BLURRILY_PRODUCE
 #undef BLURRILY_RANK
 #undef BLURRILY_RANK_ONE
 #undef BLURRILY_LEAVE_OUT
 #undef BLURRILY_UNIT_OF
+#undef BLURRILY_UNIT_AT
+#undef BLURRILY_DESC_MINE
+#undef BLURRILY_DESC
 #undef BLURRILY_TAB
 #undef BLURRILY_PUBLISH_HDR
 #undef BLURRILY_FETCH_TABLE
@@ -653,7 +736,8 @@ __global__ __launch_bounds__(NT, (sizeof(CT) == 1 ? NT / 128 : NT / 256)) void f
   (void)wmt;
   __syncthreads();
 
-  const uint32_t n_work = A.n_work_dev ? *A.n_work_dev : A.n_work;
+  // (as a scalar: loaded through a VGPR it stayed in one for the kernel's lifetime -- in scratch, that is)
+  const uint32_t n_work = __builtin_amdgcn_readfirstlane(A.n_work_dev ? *A.n_work_dev : A.n_work);
 
   PHASE_NEEDLE_DECL;
   for (;;) {
