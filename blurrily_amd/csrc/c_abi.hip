@@ -60,37 +60,14 @@ int blurrily_storage_close(trigram_map* haystack) {
     DeviceScope scope(m->dev.device);
     for (Replica& r : m->replicas) free_replica(r);
     m->replicas.clear();
-    for (hipEvent_t e : {m->ev_ready, m->ev_t0, m->ev_t1}) if (e) (void)hipEventDestroy(e);
     if (m->dev.device >= 0) {
       (void)hipDeviceSynchronize();
       device_index_free(&m->dev);
     }
     if (m->delta.device >= 0) device_index_free(&m->delta);
     delete m->delta_host;
-    if (m->d_code_total_now) (void)hipFree(m->d_code_total_now);
-    if (m->d_stats) (void)hipFree(m->d_stats);
-    if (m->d_phase) (void)hipFree(m->d_phase);
-    m->ws_base_rows.release(); m->ws_base_counts.release(); m->ws_delta_rows.release(); m->ws_delta_counts.release();
-    for (auto& e : m->ev) if (e) (void)hipEventDestroy(e);
-    for (auto& e : m->tune_ev) if (e) (void)hipEventDestroy(e);
-    for (auto& w : m->watch_ev) for (auto& e : w) if (e) (void)hipEventDestroy(e);
-    m->ws_codes.release(); m->ws_small.release(); m->ws_parts.release(); m->ws_io_in.release();
-    m->ws_io_out.release(); m->ws_tomb.release(); m->ws_flags.release(); m->ws_refs.release();
-    m->ws_each.release(); m->ws_each_rows.release();
-    if (m->h_stage) (void)hipHostFree(m->h_stage);
-    if (m->h_scope) (void)hipHostFree(m->h_scope);
-    if (m->one.stream) { (void)hipStreamSynchronize(m->one.stream); (void)hipStreamDestroy(m->one.stream); }
-    if (m->one.h_out) (void)hipHostFree(m->one.h_out);
-    m->one.d_parts.release();
-    for (int i = 0; i < 2; ++i) {
-      if (m->pipe.h_in[i]) (void)hipHostFree(m->pipe.h_in[i]);
-      if (m->pipe.h_out[i]) (void)hipHostFree(m->pipe.h_out[i]);
-      m->pipe.d_in[i].release(); m->pipe.d_out[i].release();
-      for (hipEvent_t e : {m->pipe.ev_in[i], m->pipe.ev_run[i], m->pipe.ev_out[i]}) if (e) (void)hipEventDestroy(e);
-    }
-    for (hipStream_t s : {m->pipe.s_in, m->pipe.s_run, m->pipe.s_out}) if (s) (void)hipStreamDestroy(s);
     delete m->host;
-    delete m;
+    delete m;                                            // (what its finds hold on the device and of the runtime goes with it)
   }
   *haystack = nullptr;
   return 0;
@@ -278,129 +255,6 @@ int blurrily_storage_tune(trigram_map m, const char* packed, const uint64_t* off
 void blurrily_storage_set_timing(trigram_map m, int enabled) { m->timing = enabled != 0; }
 
 void blurrily_storage_set_stats(trigram_map m, int enabled) { m->collect_stats = enabled != 0; }
-
-// Tunables: one table, so that set and get cannot drift apart.  A map's options are plain fields read by its
-// next find (calls on one map are serial, as in the reference: no lock); the process-wide ones are atomics.
-namespace {
-struct OptionSlot { const char* key; long long lo, hi; };
-constexpr OptionSlot kMapOptions[] = {
-    {"wsweep", 0, 1}, {"ws_cmin", 1, 64}, {"ws_min_windows", 0, 1 << 20}, {"ws_min_needles", 0, 1ll << 32},
-    {"ws_min_slice", 0, 1ll << 31}, {"dense_min", 64, 65536}, {"host_chunk", 0, 1ll << 30},
-    {"ws_autotune", 0, 1}, {"ws_static_slice", 0, 1ll << 31}, {"ws_choice", 0, 0},
-    {"nm_cmin", 0, 64}, {"nm_dense", 64, 65536}, {"last_sweep", 0, 0}, {"devices", 1, 64},
-    {"nm_min_windows", 0, 1 << 20}, {"tuned_class", 0, 0}, {"tuned_nm_us", 0, 0}, {"tuned_ws_us", 0, 0},
-    {"tuned_leave_us", 0, 0}, {"small_sweep", 0, 1}, {"small_min_needles", 0, 1ll << 32},
-    {"one_launch", 0, 1}, {"one_taken", 0, 0}, {"one_windows_per_wg", 0, 1 << 20},
-    {"retunes", 0, 0}, {"tune_inject", 0, 3}, {"mid_workgroups", 64, 1 << 16}, {"few_max", 1, kMidMaxNeedles}, {"mid_max", 0, kMidMaxNeedles},
-    {"latency_tasks", 0, 16}, {"scope_strategy", 0, 2}, {"scope_direct_max", 0, 1ll << 40}};
-constexpr OptionSlot kProcessOptions[] = {{"host_threads", 0, 256}, {"build_trace", 0, 1}};
-int find_option(const OptionSlot* tab, size_t n, const char* key) {
-  for (size_t i = 0; i < n; ++i) if (std::strcmp(tab[i].key, key) == 0) return int(i);
-  return -1;
-}
-#define FIND_OPTION(tab, key) find_option(tab, sizeof(tab) / sizeof(tab[0]), key)
-}  // namespace
-
-int blurrily_storage_set_option(trigram_map m, const char* key, long long value) {
-  if (!key) { errno = EINVAL; return -1; }
-  if (!m) {
-    const int i = FIND_OPTION(kProcessOptions, key);
-    if (i < 0 || value < kProcessOptions[i].lo || value > kProcessOptions[i].hi) { errno = EINVAL; return -1; }
-    if (i == 0) set_host_threads(unsigned(value)); else set_build_trace(value != 0);
-    return 0;
-  }
-  const int i = FIND_OPTION(kMapOptions, key);
-  if (i < 0 || value < kMapOptions[i].lo || value > kMapOptions[i].hi) { errno = EINVAL; return -1; }
-  switch (i) {
-    case 0: m->build_opt.ws_enabled = value != 0; break;
-    case 1: m->ws_cmin = uint32_t(value); break;
-    case 2: m->build_opt.ws_min_windows = uint32_t(value); break;
-    case 3: m->ws_min_needles = uint32_t(std::min<long long>(value, 0xFFFFFFFFll)); break;
-    case 4: m->build_opt.ws_min_slice = uint32_t(value); break;
-    case 5:                                        // which slices have bitmaps: the image is rebuilt by the next find
-      if (m->build_opt.dense_min != uint32_t(value) && m->dev.device >= 0) m->log_overflow = true;
-      m->build_opt.dense_min = uint32_t(value);
-      break;
-    case 6: m->host_chunk = uint32_t(value); break;
-    case 7: m->ws_autotune = value != 0; break;
-    case 8: m->ws_static_slice = uint32_t(value); break;
-    case 9: break;                                       // (value 0 only: forget what was measured)
-    case 10: m->nm_cmin = uint32_t(value); break;
-    case 11: m->nm_dense = uint32_t(value); break;
-    case 12: m->last_sweep = 0; return 0;                // (value 0 only; nothing to measure again)
-    case 13:                                             // (replicas are made by the next large batch; dropped at once)
-      m->n_devices = uint32_t(value);
-      while (m->replicas.size() + 1 > m->n_devices) { free_replica(m->replicas.back()); m->replicas.pop_back(); }
-      return 0;
-    case 14: m->nm_min_windows = uint32_t(value); break;
-    case 15: case 16: case 17: case 18: return 0;        // (read-only: what the last measurement saw)
-    case 19: m->small_sweep = value != 0; break;
-    case 20: m->small_min_needles = uint32_t(std::min<long long>(value, 0xFFFFFFFFll)); break;
-    case 21: m->one.enabled = value != 0; return 0;      // (the single find's own launch; nothing to measure again)
-    case 22: return 0;                                   // (read-only)
-    case 23: m->one.min_per = uint32_t(value); return 0;
-    case 24: return 0;                                   // (read-only)
-    case 25: m->tune_inject = int(value); return 0;      // (tests: the next measurement's bad sample)
-    case 26: m->one.mid_workgroups = uint32_t(value); return 0;
-    case 27: m->one.few_max = uint32_t(value); return 0;
-    case 28: m->one.mid_max = uint32_t(value); return 0;
-    case 29: m->latency_tasks = uint32_t(value); return 0;
-    case 30: m->scope_strategy = uint32_t(value); return 0;   // (scoped finds only: nothing to measure again)
-    case 31: m->scope_direct_max = uint64_t(value); return 0;
-  }
-  if (i != 6) std::fill(std::begin(m->ws_choice), std::end(m->ws_choice), 0);   // the sweep's choice is measured again
-  return 0;
-}
-
-int blurrily_storage_get_option(trigram_map m, const char* key, long long* value) {
-  if (!key || !value) { errno = EINVAL; return -1; }
-  if (!m) {
-    const int i = FIND_OPTION(kProcessOptions, key);
-    if (i < 0) { errno = EINVAL; return -1; }
-    *value = i == 0 ? (long long)host_threads() : (long long)build_trace();
-    return 0;
-  }
-  switch (FIND_OPTION(kMapOptions, key)) {
-    case 0: *value = m->build_opt.ws_enabled; return 0;
-    case 1: *value = m->ws_cmin; return 0;
-    case 2: *value = m->build_opt.ws_min_windows; return 0;
-    case 3: *value = m->ws_min_needles; return 0;
-    case 4: *value = m->build_opt.ws_min_slice; return 0;
-    case 5: *value = m->build_opt.dense_min; return 0;
-    case 6: *value = m->host_chunk; return 0;
-    case 7: *value = m->ws_autotune; return 0;
-    case 8: *value = m->ws_static_slice; return 0;
-    case 9: {                                            // what was measured so far: class c's choice in bits 2c+1:2c
-      long long v = 0;                                   // (1 needle-major, 2 window-major, 3 needle-major with slices left out)
-      for (int c = 0; c < 8; ++c) v |= (long long)(m->ws_choice[c]) << (2 * c);
-      *value = v;
-      return 0;
-    }
-    case 10: *value = m->nm_cmin; return 0;
-    case 11: *value = m->nm_dense; return 0;
-    case 12: *value = m->last_sweep; return 0;
-    case 13: *value = m->n_devices; return 0;
-    case 14: *value = m->nm_min_windows; return 0;
-    case 15: *value = m->last_tuned; return 0;             // -1: nothing measured yet
-    case 16: case 17: case 18:                             // microseconds of the sweep in that measurement (0: it could not run)
-      *value = m->last_tuned < 0 ? 0 : (long long)(1000.0 * m->ws_tuned_ms[m->last_tuned][FIND_OPTION(kMapOptions, key) - 16]);
-      return 0;
-    case 19: *value = m->small_sweep; return 0;
-    case 20: *value = m->small_min_needles; return 0;
-    case 21: *value = m->one.enabled; return 0;
-    case 22: *value = (long long)m->one.taken; return 0;
-    case 23: *value = m->one.min_per; return 0;
-    case 24: *value = (long long)m->retunes; return 0;
-    case 25: *value = m->tune_inject; return 0;
-    case 26: *value = m->one.mid_workgroups; return 0;
-    case 27: *value = m->one.few_max; return 0;
-    case 28: *value = m->one.mid_max; return 0;
-    case 29: *value = m->latency_tasks; return 0;
-    case 30: *value = m->scope_strategy; return 0;
-    case 31: *value = (long long)m->scope_direct_max; return 0;
-    default: errno = EINVAL; return -1;
-  }
-}
 
 // debugging aid (tools/ws_probe.py): all counter slots, phase clocks of the window-major sweep included
 int blurrily_debug_find_stats16(trigram_map m, uint64_t* out16) {

@@ -117,20 +117,33 @@ inline bool watch_comparable(size_t watch_n, size_t tuned_n) {
   return tuned_n != 0 && watch_n * 2 >= tuned_n && watch_n <= tuned_n * 2;
 }
 
-// The verdict on a class's watched batch that took `ms` for watch_n needles, against tuned_us per needle at tuned_n: over
-// 10 % slower is a strike, and the second in a row, outside the hold-off, has the class measured again (*choice 0).
+// What a map keeps per class of batch (batch_class): the measured choice and what the measurement saw, and the watch
+// on it -- the chosen sweep's later batches of the class are bracketed by two events (the map's: read at the class's
+// next batch, never waited for).  Forgetting the choice (a set option, a new image) leaves everything else in place.
+struct ClassChoice {
+  int      choice = 0;                  // 0 not measured yet, or the kSweep* that serves the class
+  float    tuned_ms[3] = {0.f, 0.f, 0.f};   // what the measurement saw: needle-major, window-major, slices left out
+  size_t   tuned_n = 0;                 // the batch size it was measured at (the watch compares like with like)
+  float    tuned_us_per_needle = 0.f;   // of the sweep that was chosen
+  bool     watch_pending = false;       // a bracketed batch is under way or unread
+  size_t   watch_n = 0;                 // ... of this many needles
+  uint32_t strikes = 0;                 // consecutive batches of the class seen slow (one is noise: another tenant, a clock step)
+  uint32_t holdoff = 0;                 // batches of the class until it may be measured again
+};
+
+// The verdict on a class's watched batch that took `ms` for c->watch_n needles, against tuned_us_per_needle at tuned_n:
+// over 10 % slower is a strike, and the second in a row, outside the hold-off, has the class measured again (choice 0).
 // (TWO batches in a row: a single slow one -- seen on a shared box, 2.3 x inside bench.py's three timed steps --
 // would put a measurement of every sweep, twice, into a batch that had nothing wrong)
-inline void watch_verdict(float ms, size_t watch_n, size_t tuned_n, float tuned_us, int* choice, uint32_t* strikes,
-                          uint32_t* holdoff, uint64_t* retunes) {
-  if (!watch_n || !watch_comparable(watch_n, tuned_n) || !(tuned_us > 0.f) || *choice == 0) return;
-  const float us = 1000.f * ms / float(watch_n);
-  if (us <= 1.10f * tuned_us) {
-    *strikes = 0;
-  } else if (++*strikes >= 2 && *holdoff == 0) {
-    *choice = 0;
-    *holdoff = 16;
-    *strikes = 0;
+inline void watch_verdict(float ms, ClassChoice* c, uint64_t* retunes) {
+  if (!c->watch_n || !watch_comparable(c->watch_n, c->tuned_n) || !(c->tuned_us_per_needle > 0.f) || c->choice == 0) return;
+  const float us = 1000.f * ms / float(c->watch_n);
+  if (us <= 1.10f * c->tuned_us_per_needle) {
+    c->strikes = 0;
+  } else if (++c->strikes >= 2 && c->holdoff == 0) {
+    c->choice = 0;
+    c->holdoff = 16;
+    c->strikes = 0;
     ++*retunes;
   }
 }

@@ -124,7 +124,7 @@ static int run_nm(FindCall& c) {
 static int run_ws(FindCall& c) {
   FindArgs& a = c.a;
   c.whole_batch(c.n, 0, c.limit);
-  a.cmin = c.m->ws_cmin;
+  a.cmin = c.m->sweep.ws_cmin;
   // Phase 1: the needle-major kernel over the window pair of every needle's own length class seeds the
   // states (a needle's best matches live there, so its threshold is tight before the other windows are
   // visited).  (Seeding through wsweep_kernel's own robust path instead -- own_pass launches -- was
@@ -171,45 +171,31 @@ static int run_long(FindCall& c) {
 }
 
 static int run_sweep(FindCall& c, int which) {
-  c.a.nm_cmin = which == kSweepLeave ? c.m->nm_cmin : 0u;
+  c.a.nm_cmin = which == kSweepLeave ? c.m->sweep.nm_cmin : 0u;
   const int rc = which == kSweepWindows ? run_ws(c) : which == kSweepSmall ? run_small(c) : run_nm(c);
   c.a.nm_cmin = 0;                                     // (latency mode and the long-needle launches leave nothing out)
   return rc;
 }
 
-// k events, or none (a half-made set would be recorded into)
-static int make_events(hipEvent_t* out, int k) {
-  hipEvent_t ev[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  for (int i = 0; i < k; ++i)
-    if (hipEventCreate(&ev[i]) != hipSuccess) {
-      while (i--) (void)hipEventDestroy(ev[i]);
-      errno = EIO;
-      return -1;
-    }
-  std::copy(ev, ev + k, out);
-  return 0;
-}
-
 // what the class's last batch took, if it has finished (never waited for): slow against the measurement?
 static void watch_read(trigram_map m, int cls) {
-  if (!m->watch_pending[cls] || hipEventQuery(m->watch_ev[cls][1]) != hipSuccess) return;
+  if (!m->cls[cls].watch_pending || hipEventQuery(m->watch_ev[cls][1]) != hipSuccess) return;
   float ms = 0.f;
-  m->watch_pending[cls] = false;
+  m->cls[cls].watch_pending = false;
   if (hipEventElapsedTime(&ms, m->watch_ev[cls][0], m->watch_ev[cls][1]) == hipSuccess)
-    watch_verdict(ms, m->watch_n[cls], m->tuned_n[cls], m->tuned_us_per_needle[cls], &m->ws_choice[cls],
-                  &m->watch_strikes[cls], &m->retune_holdoff[cls], &m->retunes);   // (ws_choice 0: measured again, by this call)
+    watch_verdict(ms, &m->cls[cls], &m->retunes);      // (choice 0: measured again, by this call)
 }
 
 // the brackets of a watched batch: two events around the chosen sweep, read by watch_read at the class's next batch
 static int watch_begin(FindCall& c, int cls) {
-  if (!c.m->watch_ev[cls][1] && make_events(c.m->watch_ev[cls], 2) < 0) return -1;
+  if (c.m->watch_ev[cls].make() < 0) return -1;
   BLURRILY_HIP_TRY(hipEventRecord(c.m->watch_ev[cls][0], c.stream));
   return 0;
 }
 static int watch_end(FindCall& c, int cls) {
   BLURRILY_HIP_TRY(hipEventRecord(c.m->watch_ev[cls][1], c.stream));
-  c.m->watch_pending[cls] = true;
-  c.m->watch_n[cls] = c.n;
+  c.m->cls[cls].watch_pending = true;
+  c.m->cls[cls].watch_n = c.n;
   return 0;
 }
 
@@ -217,7 +203,7 @@ static int watch_end(FindCall& c, int cls) {
 // each, the better time of a sweep's two runs counting; the batch's rows are the last run's, the plain sweep's
 static int measure_sweeps(FindCall& c, int cls, bool ws_possible, bool leave_possible) {
   trigram_map m = c.m;
-  if (!m->tune_ev[0] && make_events(m->tune_ev, 7) < 0) return -1;
+  if (m->tune_ev.make() < 0) return -1;
   int order[6];
   measure_order(ws_possible, leave_possible, order);
   float ms_of[4] = {0.f, 0.f, 0.f, 0.f};               // by sweep: [1] plain, [2] window-major, [3] slices left out
@@ -234,11 +220,12 @@ static int measure_sweeps(FindCall& c, int cls, bool ws_possible, bool leave_pos
     ms_of[order[k]] = ms_of[order[k]] == 0.f ? ms : std::min(ms_of[order[k]], ms);
   }
   float best = 0.f;
-  m->ws_choice[cls] = pick_sweep(ms_of, &m->tune_inject, ws_possible, leave_possible, &best);
-  m->ws_tuned_ms[cls][0] = ms_of[1]; m->ws_tuned_ms[cls][1] = ms_of[2]; m->ws_tuned_ms[cls][2] = ms_of[3];
-  m->tuned_us_per_needle[cls] = 1000.f * best / float(c.n);
-  m->tuned_n[cls] = c.n;
-  m->watch_pending[cls] = false;
+  ClassChoice& cc = m->cls[cls];
+  cc.choice = pick_sweep(ms_of, &m->tune_inject, ws_possible, leave_possible, &best);
+  std::copy(ms_of + 1, ms_of + 4, cc.tuned_ms);
+  cc.tuned_us_per_needle = 1000.f * best / float(c.n);
+  cc.tuned_n = c.n;
+  cc.watch_pending = false;
   m->last_tuned = cls;
   return kSweepPlain;                                  // (the rows in place are the plain run's; all give the same)
 }
@@ -261,29 +248,29 @@ static int measure_sweeps(FindCall& c, int cls, bool ws_possible, bool leave_pos
 static int serve_short_needles(FindCall& c, size_t code_slots, bool scoped) {
   trigram_map m = c.m;
   const DeviceIndex& ix = c.ix;
-  if (m->small_sweep && ix.n_windows <= kSmallMaxWindows && c.limit <= kSmallMaxKeep && c.n >= m->small_min_needles)
+  if (m->sweep.small_sweep && ix.n_windows <= kSmallMaxWindows && c.limit <= kSmallMaxKeep && c.n >= m->sweep.small_min_needles)
     return run_sweep(c, kSweepSmall) < 0 ? -1 : kSweepSmall;
-  const bool leave_possible = m->nm_cmin != 0 && c.limit <= 1024 && find_can_leave(c.limit) && ix.n_bitmaps != 0;
-  const bool ws_possible = c.limit <= kWsMaxKeep && c.n >= m->ws_min_needles && ix.n_bitmaps != 0 &&
-                           m->build_opt.ws_can_run(ix.n_windows, ix.mean_hit_slice) && code_slots < 0xFFFFFFFFull;
+  const bool leave_possible = m->sweep.nm_cmin != 0 && c.limit <= 1024 && find_can_leave(c.limit) && ix.n_bitmaps != 0;
+  const bool ws_possible = c.limit <= kWsMaxKeep && c.n >= m->sweep.ws_min_needles && ix.n_bitmaps != 0 &&
+                           m->sweep.build_opt.ws_can_run(ix.n_windows, ix.mean_hit_slice) && code_slots < 0xFFFFFFFFull;
   // (a chunk of a host-buffer batch belongs to the class of the WHOLE batch: class_hint)
   const size_t n_cls = std::max(c.n, m->class_hint);
   const int cls = batch_class(n_cls, c.limit);
-  const bool tunable = m->ws_autotune && c.is_base() && n_cls >= 129 && (leave_possible || ws_possible);
+  const bool tunable = m->sweep.ws_autotune && c.is_base() && n_cls >= 129 && (leave_possible || ws_possible);
   // (counters must describe ONE sweep: a counted call neither measures nor watches the class; nor does a scoped call)
   const bool own = tunable && !c.cb && !scoped;
   if (own) watch_read(m, cls);
-  holdoff_tick(&m->retune_holdoff[cls], scoped);
-  const int held = m->ws_choice[cls];
+  holdoff_tick(&m->cls[cls].holdoff, scoped);
+  const int held = m->cls[cls].choice;
   int choice;
   if (tunable && held != 0 && (held != kSweepWindows || ws_possible) && (held != kSweepLeave || leave_possible))
     choice = held;
   else if (!own)
-    choice = static_sweep(n_cls, c.limit, ws_possible, leave_possible, ix.mean_hit_slice, m->ws_static_slice,
-                          ix.n_windows, m->nm_min_windows);
+    choice = static_sweep(n_cls, c.limit, ws_possible, leave_possible, ix.mean_hit_slice, m->sweep.ws_static_slice,
+                          ix.n_windows, m->sweep.nm_min_windows);
   else
     return measure_sweeps(c, cls, ws_possible, leave_possible);
-  const bool watch = own && m->tuned_us_per_needle[cls] > 0.f;     // (own: the choice is the measured one)
+  const bool watch = own && m->cls[cls].tuned_us_per_needle > 0.f;     // (own: the choice is the measured one)
   if (watch && watch_begin(c, cls) < 0) return -1;
   if (run_sweep(c, choice) < 0) return -1;
   if (watch && watch_end(c, cls) < 0) return -1;
@@ -314,9 +301,9 @@ static int fill_args(FindCall& c, const uint64_t* d_offsets, const RefNeedles* r
   a.results = d_results; a.counts = d_counts; a.limit = c.limit;
   a.floor = c.floor;
   a.tomb = d_tomb;
-  a.nm_dense = std::max((m->nm_dense + 7u) & ~7u, ix.dense_min8);
+  a.nm_dense = std::max((m->sweep.nm_dense + 7u) & ~7u, ix.dense_min8);
   a.nm_cmin = 0;                                     // (set per sweep: run_sweep)
-  a.stats = m->collect_stats ? m->d_stats : nullptr;
+  a.stats = m->collect_stats ? m->d_stats.h : nullptr;
   c.cb = a.stats != nullptr;
 #ifdef BLURRILY_TRACE
   const bool clocks = true;                          // (trace build: time stamps of a few needles' steps, timed kernels)
@@ -324,7 +311,7 @@ static int fill_args(FindCall& c, const uint64_t* d_offsets, const RefNeedles* r
   const bool clocks = c.cb;                          // wave 0's phase clocks per workgroup (counted build only)
 #endif
   if (clocks) {
-    if (!m->d_phase) BLURRILY_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&m->d_phase), kPhaseBytes));
+    if (m->d_phase.alloc(kPhaseWords) < 0) return -1;
     BLURRILY_HIP_TRY(hipMemsetAsync(m->d_phase, 0, kPhaseBytes, c.stream));
     a.phase_clocks = m->d_phase;
   }
@@ -391,10 +378,9 @@ static int run_find_on(trigram_map m, const DeviceIndex& ix, const uint32_t* d_c
 int run_find(trigram_map m, const char* d_packed, size_t packed_bytes, const uint64_t* d_offsets, size_t n,
              uint16_t limit, trigram_match d_results, uint32_t* d_counts, uint32_t* d_nb, bool maybe_long,
              bool maybe_mid, hipStream_t stream, const RefNeedles* rn, const ScopeMasks* sm) {
-  if (m->timing && !m->ev[0])                          // (every timed run_find_on goes through here: its events, at first use)
-    for (auto& e : m->ev) BLURRILY_HIP_TRY(hipEventCreate(&e));
+  if (m->timing && m->ev.make() < 0) return -1;        // (every timed run_find_on goes through here: its events, at first use)
   if (m->collect_stats) {
-    if (!m->d_stats) BLURRILY_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&m->d_stats), kStatAllSlots * 8));
+    if (m->d_stats.alloc(kStatAllSlots) < 0) return -1;
     BLURRILY_HIP_TRY(hipMemsetAsync(m->d_stats, 0, kStatAllSlots * 8, stream));
     if (m->ws_flags.reserve(std::max<size_t>(n, 1) * sizeof(uint32_t), stream) < 0) return -1;
     BLURRILY_HIP_TRY(hipMemsetAsync(m->ws_flags.p, 0, std::max<size_t>(n, 1) * sizeof(uint32_t), stream));

@@ -15,12 +15,8 @@ constexpr size_t kStageBytes = 1 << 20;   // pinned staging per direction for sm
 static int find_batch_chunked_run(trigram_map m, const char* packed, const uint64_t* offsets, size_t n, uint16_t limit,
                               trigram_match results, uint32_t* counts, bool raw, uint32_t* non_ascii, size_t chunk) {
   auto& P = m->pipe;
-  if (!P.s_in) {
-    for (hipStream_t* s : {&P.s_in, &P.s_run, &P.s_out}) BLURRILY_HIP_TRY(hipStreamCreateWithFlags(s, hipStreamNonBlocking));
-    for (int i = 0; i < 2; ++i)
-      for (hipEvent_t* e : {&P.ev_in[i], &P.ev_run[i], &P.ev_out[i]})
-        BLURRILY_HIP_TRY(hipEventCreateWithFlags(e, hipEventDisableTiming));
-  }
+  for (Stream* s : {&P.s_in, &P.s_run, &P.s_out}) if (s->make() < 0) return -1;
+  for (Events<2>* e : {&P.ev_in, &P.ev_run, &P.ev_out}) if (e->make(hipEventDisableTiming) < 0) return -1;
   // staging sizes: the largest chunk's bytes in (rebased offsets | needles) and out (counts | flags | rows)
   size_t max_packed = 0;
   for (size_t a = 0; a < n; a += chunk) {
@@ -31,16 +27,10 @@ static int find_batch_chunked_run(trigram_map m, const char* packed, const uint6
   const size_t in_cap = C.in_bytes, out_cap = C.out_bytes;
   if (P.h_in_bytes < in_cap || P.h_out_bytes < out_cap) {
     BLURRILY_HIP_TRY(hipDeviceSynchronize());
-    for (int i = 0; i < 2; ++i) {
-      if (P.h_in[i]) (void)hipHostFree(P.h_in[i]);
-      if (P.h_out[i]) (void)hipHostFree(P.h_out[i]);
-      P.h_in[i] = P.h_out[i] = nullptr;
-    }
+    for (int i = 0; i < 2; ++i) { P.h_in[i].reset(); P.h_out[i].reset(); }
     P.h_in_bytes = P.h_out_bytes = 0;
-    for (int i = 0; i < 2; ++i) {
-      BLURRILY_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&P.h_in[i]), in_cap));
-      BLURRILY_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&P.h_out[i]), out_cap));
-    }
+    for (int i = 0; i < 2; ++i)
+      if (P.h_in[i].alloc(in_cap) < 0 || P.h_out[i].alloc(out_cap) < 0) return -1;
     P.h_in_bytes = in_cap; P.h_out_bytes = out_cap;
   }
   for (int i = 0; i < 2; ++i)
@@ -67,7 +57,7 @@ static int find_batch_chunked_run(trigram_map m, const char* packed, const uint6
     const int i = int(k & 1);
     if (drain(i) < 0) return -1;                                  // chunk k-2: its staging and device blocks are free again
     // ---- stage chunk k: offsets rebased to the chunk, its needles; how long they can be --------------
-    uint64_t* h_off = reinterpret_cast<uint64_t*>(P.h_in[i]);
+    uint64_t* h_off = reinterpret_cast<uint64_t*>(P.h_in[i].h);
     const uint64_t base = offsets[a];
     for (size_t j = 0; j <= c; ++j) h_off[j] = offsets[a + j] - base;
     const size_t bytes = size_t(offsets[b] - base);
@@ -271,7 +261,7 @@ int find_batch_host(trigram_map m, const char* packed, const uint64_t* offsets, 
   // Small batches (the single blurrily_storage_find above all) go through pinned staging: one
   // copy in, one copy out, instead of four pageable ones.
   const bool staged = B.in_bytes <= kStageBytes && B.out_bytes <= kStageBytes;
-  if (staged && !m->h_stage) BLURRILY_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&m->h_stage), 2 * kStageBytes));
+  if (staged && !m->h_stage && m->h_stage.alloc(2 * kStageBytes) < 0) return -1;
   if (staged) {
     B.fill_in(m->h_stage, packed, offsets);
     BLURRILY_HIP_TRY(hipMemcpyAsync(d_in, m->h_stage, B.in_bytes, hipMemcpyHostToDevice, stream));
@@ -353,20 +343,13 @@ uint32_t compact_rows(FewCall& c, size_t n, uint32_t* counts) {
 // half-made set -- a stream without its page -- would have the next find skip this step and poll a null page)
 int make_page(trigram_map_t::One& O) {
   if (O.h_out) return 0;
-  hipStream_t st = nullptr;
-  unsigned char *h = nullptr, *d = nullptr;
-  hipError_t e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
-  if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&h), 2 * kPage.bytes, hipHostMallocMapped | hipHostMallocCoherent);
-  if (e == hipSuccess) e = hipHostGetDevicePointer(reinterpret_cast<void**>(&d), h, 0);
-  if (e != hipSuccess) {
-    std::fprintf(stderr, "blurrily_hip: the single find's stream / pinned page: %s\n", hipGetErrorString(e));
-    if (h) (void)hipHostFree(h);
-    if (st) (void)hipStreamDestroy(st);
-    errno = (e == hipErrorOutOfMemory) ? ENOMEM : EIO;
-    return -1;
-  }
+  Stream st;
+  HostPage h;
+  unsigned char* d = nullptr;
+  if (st.make() < 0 || h.alloc(2 * kPage.bytes, hipHostMallocMapped | hipHostMallocCoherent) < 0) return -1;
+  BLURRILY_HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&d), h, 0));
   std::memset(h, 0, 2 * kPage.bytes);
-  O.stream = st; O.h_out = h; O.d_out = d;
+  O.stream = std::move(st); O.h_out = std::move(h); O.d_out = d;
   return 0;
 }
 
@@ -407,7 +390,7 @@ int few_args(const FewCall& c, const DeviceIndex& ix, const uint32_t* d_tomb, [[
   a->limit = c.limit; a->keep = c.limit; a->pool_cap = 512;
   a->tomb = d_tomb;
 #ifdef BLURRILY_TRACE
-  if (!c.m->d_phase) BLURRILY_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c.m->d_phase), kPhaseBytes));
+  if (c.m->d_phase.alloc(kPhaseWords) < 0) return -1;
   if (which == 0) a->phase_clocks = c.m->d_phase;        // (trace build: find_one_kernel's wall-clock marks, 16 per workgroup)
 #endif
   return 0;
@@ -429,7 +412,7 @@ int launch_latency(const FewCall& c, const uint32_t* d_tomb) {
   const uint32_t tasks = c.n_rows * c.ranges;             // (<= kLists.max_lists: few_ranges)
   a.offsets = kPage.offsets(O.d_out); a.qcodes = kPage.codes(O.d_out); a.q_ntri = kPage.T(O.d_out);
   a.q_nb = kPage.nb(O.d_out); a.q_start = kPage.start(O.d_out);
-  a.nm_dense = std::max((m->nm_dense + 7u) & ~7u, m->dev.dense_min8);
+  a.nm_dense = std::max((m->sweep.nm_dense + 7u) & ~7u, m->dev.dense_min8);
   a.nm_cmin = 0;                                          // (ranges leave nothing out of a step's count: measured, slower)
   a.n_work = tasks; a.ranges = c.ranges; a.short_only = 1;
   a.part_keys = kLists.keys(lists);

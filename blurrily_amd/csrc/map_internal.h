@@ -1,7 +1,12 @@
 // map_internal.h -- the map object behind the C ABI (include/blurrily_storage.h) and what its sources share: the
 // error macro, the device scratch types, and the internal functions that cross translation units.  Everything
 // declared in blurrily::detail has hidden visibility: none of it is a dynamic symbol of libblurrily_hip.so.
-//   c_abi.hip        lifecycle, put / delete / save / stats, find / find_batch entries, options, debug entries
+// The map, trigram_map_t, is three things besides its images and its mutation log: the sweep's settings (SweepSettings:
+// what a replica takes over from the primary, in one assignment), the measured choice per class of batch (cls[8]:
+// find_choice.h's ClassChoice; forget_choices) and the device resources of its finds, every one in an owner of
+// hip_owned.h -- deleting a map gives them all back, and no function names them to free them.
+//   c_abi.hip        lifecycle, put / delete / save / stats, find / find_batch entries, debug entries
+//   options.hip      blurrily_storage_set_option / get_option: one row per option
 //   map_log.hip      the mutation log: ensure_device, apply_tombstones, map_ready, map_images
 //   find_run.hip     the batch search's launch logic: run_find_on (its decisions: find_choice.h), run_find (the timing
 //                    events); stage_string_needles
@@ -31,6 +36,7 @@
 #include "device_index.h"
 #include "find_choice.h"
 #include "find_kernels.h"
+#include "hip_owned.h"
 #include "hip_try.h"
 #include "host_index.h"
 #include "similar.h"
@@ -52,21 +58,6 @@ struct DeviceScope {
   ~DeviceScope() { if (changed) (void)hipSetDevice(prev); }
   DeviceScope(const DeviceScope&) = delete;
   DeviceScope& operator=(const DeviceScope&) = delete;
-};
-
-// Device scratch that lives as long as the map and only ever grows.
-struct DeviceBuffer {
-  void*  p = nullptr;
-  size_t bytes = 0;
-  int reserve(size_t want, hipStream_t stream) {
-    if (want <= bytes) return 0;
-    if (p) { (void)hipStreamSynchronize(stream); (void)hipFree(p); p = nullptr; bytes = 0; }
-    const size_t grow = std::max(want, bytes + bytes / 2);
-    BLURRILY_HIP_TRY(hipMalloc(&p, grow));
-    bytes = grow;
-    return 0;
-  }
-  void release() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
 };
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
@@ -91,15 +82,32 @@ struct PendingPut {
 // "devices" > 1: one more copy of the map's device side, on another visible device (or, with more replicas than
 // devices, on one that already has one): clones of the primary's images, a map object of its own for the scratch
 // buffers, events and measured choices its finds need, a stream, and staging for its shard of a batch.
-struct Replica {
+struct __attribute__((visibility("hidden"))) Replica {
   int            device = -1;
   bool           same_device = false;   // it sits on the primary's own device (more replicas than devices)
   bool           peer_access = false;   // its device and the primary's reach each other's memory directly (both ways, enabled)
   trigram_map_t* side = nullptr;        // dev / delta / d_code_total_now are the clones; host == nullptr; mirror_of = the primary
   uint64_t       base_builds = 0, delta_image_version = 0, log_version = 0;   // the primary's, as of the clones
-  hipStream_t    stream = nullptr;
-  hipEvent_t     ev_done = nullptr, ev_t0 = nullptr, ev_t1 = nullptr;
+  blurrily::detail::Stream    stream;
+  blurrily::detail::Events<1> ev_done;  // (timing disabled)
+  blurrily::detail::Events<2> ev_t;     // around its shard's search, in timing mode
   blurrily::detail::DeviceBuffer d_in, d_out;   // [offsets | needles] of the batch, [rows | counts | nb_entries] of its shard
+};
+
+// The tunables of the batch sweeps that a replica's finds read as the primary's do (blurrily_storage_set_option;
+// defaults from the measured gate): a replica takes them over in one assignment.
+struct SweepSettings {
+  blurrily::IndexBuildOptions build_opt;          // ws_enabled, ws_min_windows, ws_min_slice, dense_min
+  uint32_t    ws_cmin = 3;              // a left-out slice must leave at least this many counted matches
+  uint32_t    nm_cmin = 3;              // the same for the needle-major sweep (0: it leaves nothing out)
+  uint32_t    nm_dense = 3072;          // ... which leaves out slices of at least this many postings only (4 096 through round 5;
+                                        // round 6, same rows: configs[2] 120.8 -> 119.1 ms per 300 k needles, four times the haystack 135.1 -> 129.9)
+  bool        small_sweep = true;       // images of at most kSmallMaxWindows windows: find_small_kernel serves large batches at limits up to 64
+  uint32_t    small_min_needles = 4096; // ... from this many needles on (below: two chains per CU are not the limit)
+  uint32_t    nm_min_windows = 256;     // ... and, where the choice is not measured, on images of at least this many windows
+  uint32_t    ws_min_needles = 16384;   // smaller batches: needle-major
+  bool        ws_autotune = true;       // measure the choice per class of batch on first use (run_find_on)
+  uint32_t    ws_static_slice = 2200;   // the static rule's mean_hit_slice (autotune off): break-even of the skewed family
 };
 
 struct trigram_map_t {
@@ -107,7 +115,8 @@ struct trigram_map_t {
   const trigram_map_t* mirror_of = nullptr;   // a replica's side map: the mutation log that counts is this map's
   std::vector<Replica> replicas;        // "devices" - 1 of them
   uint32_t    n_devices = 1;            // option "devices": shards of a large batch (the primary's included)
-  hipEvent_t  ev_ready = nullptr, ev_t0 = nullptr, ev_t1 = nullptr;   // multi-device batches
+  blurrily::detail::Events<1> ev_ready; // multi-device batches: the caller's needles are in place (timing disabled)
+  blurrily::detail::Events<2> ev_t;     // ... and around the primary's shard, in timing mode
   blurrily::DeviceIndex dev;                      // base image
   // log of puts/deletes the base image does not contain yet
   std::unordered_map<uint32_t, PendingPut> pending;   // by reference
@@ -122,50 +131,31 @@ struct trigram_map_t {
   uint64_t    base_builds = 0;
   blurrily::HostIndex*  delta_host = nullptr;
   blurrily::DeviceIndex delta;                    // image of `pending` only
-  uint32_t*   d_code_total_now = nullptr;   // [kNumCodes] bucket sizes of the whole map (base run's nb_entries)
+  blurrily::detail::DeviceMem<uint32_t> d_code_total_now;   // [kNumCodes] bucket sizes of the whole map (base run's nb_entries)
   blurrily::detail::DeviceBuffer ws_base_rows, ws_base_counts, ws_delta_rows, ws_delta_counts;
-  // tunables of the window-major sweep (blurrily_storage_set_option; defaults from the measured gate)
-  blurrily::IndexBuildOptions build_opt;          // ws_enabled, ws_min_windows, ws_min_slice, dense_min
-  uint32_t    ws_cmin = 3;              // a left-out slice must leave at least this many counted matches
-  uint32_t    nm_cmin = 3;              // the same for the needle-major sweep (0: it leaves nothing out)
-  uint32_t    nm_dense = 3072;          // ... which leaves out slices of at least this many postings only (4 096 through round 5;
-                                        // round 6, same rows: configs[2] 120.8 -> 119.1 ms per 300 k needles, four times the haystack 135.1 -> 129.9)
-  bool        small_sweep = true;       // images of at most kSmallMaxWindows windows: find_small_kernel serves large batches at limits up to 64
-  uint32_t    small_min_needles = 4096; // ... from this many needles on (below: two chains per CU are not the limit)
-  uint32_t    nm_min_windows = 256;     // ... and, where the choice is not measured, on images of at least this many windows
-  uint32_t    ws_min_needles = 16384;   // smaller batches: needle-major
-  bool        ws_autotune = true;       // measure the choice per class of batch on first use (run_find_on)
-  uint32_t    ws_static_slice = 2200;   // the static rule's mean_hit_slice (autotune off): break-even of the skewed family
-  int         ws_choice[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // per class: 0 not measured yet, 1 needle-major, 2 window-major,
-                                                   // 3 needle-major with slices left out
-  float       ws_tuned_ms[8][3] = {};   // what the measurement saw (needle-major, window-major, slices left out)
+  SweepSettings sweep;
+  // the sweep that serves each class of batch, measured by the class's first batch and WATCHED afterwards: one that ran
+  // over 10 % slower per needle than what the measurement saw has the class measured again -- at most once in sixteen
+  // batches (find_choice.h: ClassChoice, watch_verdict)
+  blurrily::detail::ClassChoice cls[8];
+  blurrily::detail::Events<2>   watch_ev[8];      // a class's watched batch: around the chosen sweep
+  blurrily::detail::Events<7>   tune_ev;          // a measurement: between its runs
   int         last_tuned = -1;          // the class measured most recently ("tuned_*_us" report its figures)
   int         last_sweep = 0;           // which sweep the last large batch of short needles took (1 / 2 / 3; 0: none yet)
   uint32_t latency_tasks = 0;           // option "latency_tasks": tasks latency mode aims at per resident workgroup (0: latency_ranges' rule)
   std::string last_kernels;             // the find kernels the last batch on the base image launched, '+'-joined (blurrily_storage_last_kernels)
   size_t      class_hint = 0;           // a chunked host batch: the WHOLE batch's size decides the class, not the chunk's
-  hipEvent_t  tune_ev[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  // a measured choice is WATCHED: the chosen sweep's later batches of the class are bracketed by two events (read at the
-  // class's next batch, never waited for); one that ran over 10 % slower per needle than what the measurement saw has
-  // the class measured again -- at most once in sixteen batches
-  hipEvent_t  watch_ev[8][2] = {};
-  bool        watch_pending[8] = {false, false, false, false, false, false, false, false};
-  size_t      watch_n[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  size_t      tuned_n[8] = {0, 0, 0, 0, 0, 0, 0, 0};      // the batch size a class was measured at (the watch compares like with like)
-  float       tuned_us_per_needle[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};   // of the sweep that was chosen
-  uint32_t    retune_holdoff[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  uint32_t    watch_strikes[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // consecutive batches of the class seen slow (one is noise: another tenant, a clock step)
   uint64_t    retunes = 0;              // classes measured again because a batch ran slow (option "retunes", read-only)
   int         tune_inject = 0;          // (tests) the next measurement sees this sweep at HALF its time: a bad sample to recover from
   int         n_cus = 0;
   bool        timing = false;
   bool        collect_stats = false;    // request counters of the find kernels (FindArgs::stats)
-  unsigned long long* d_stats = nullptr;   // [kStatSlots], zeroed by every run_find while collecting
-  unsigned long long* d_phase = nullptr;   // [kPhaseWorkgroups][16] phase clocks of the counted build's last launch
+  blurrily::detail::DeviceMem<unsigned long long> d_stats;   // [kStatAllSlots], zeroed by every run_find while collecting
+  blurrily::detail::DeviceMem<unsigned long long> d_phase;   // [kPhaseWorkgroups][16] phase clocks of the counted build's last launch
   blurrily::detail::DeviceBuffer ws_flags;                   // [n] path flags of the last find while collecting (FindArgs::path_flags)
   size_t      n_flags = 0;
   double      last_find_ms = 0.0, last_tok_ms = 0.0;
-  hipEvent_t  ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  blurrily::detail::Events<4> ev;       // timing mode: around the front end and around the find
   blurrily::detail::DeviceBuffer ws_codes, ws_small, ws_parts, ws_io_in, ws_io_out;
   blurrily::detail::DeviceBuffer ws_refs;                 // by reference: the extraction's arrays and the references' codes (refs_extract)
   // scoped find: options "scope_strategy" (0 auto, 1 mask, 2 direct) and "scope_direct_max" (the
@@ -176,18 +166,18 @@ struct trigram_map_t {
   // finds take 193 against 122 us -- profiles/scope_geonames.json)
   uint32_t    scope_strategy = 0;
   uint64_t    scope_direct_max = 150000;
-  unsigned char* h_scope = nullptr;     // [kScopePageBytes in | kScopePageBytes out]
+  blurrily::detail::HostPage h_scope;   // [kScopePageBytes in | kScopePageBytes out]
   unsigned char* d_scope = nullptr;     // the same memory as the device addresses it
   // a scope per needle: the call's plan on the device (scope table, workgroup order, the groups'
   // needles, their rows) and on the host (what is uploaded; kept until the next such call)
   blurrily::detail::DeviceBuffer ws_each, ws_each_rows;
   std::vector<unsigned char> h_each;
-  unsigned char* h_stage = nullptr;     // pinned host staging: [kStageBytes in | kStageBytes out]
+  blurrily::detail::HostPage h_stage;   // pinned host staging: [kStageBytes in | kStageBytes out]
   // the single find's own launch (find_one): a stream, host-coherent pinned memory the kernel writes rows, count and a
   // sequence word into, the per-workgroup lists and the ticket on the device
-  struct One {
-    hipStream_t    stream = nullptr;
-    unsigned char* h_out = nullptr;     // per image: a page as find_few_layout.h lays it out (FewPage)
+  struct __attribute__((visibility("hidden"))) One {
+    blurrily::detail::Stream   stream;
+    blurrily::detail::HostPage h_out;   // per image: a page as find_few_layout.h lays it out (FewPage)
     unsigned char* d_out = nullptr;     // the same memory as the device addresses it
     blurrily::detail::DeviceBuffer   d_parts;             // per image: the lists as find_few_layout.h lays them out (FewLists)
     uint32_t       seq = 0;
@@ -202,11 +192,10 @@ struct trigram_map_t {
   } one;
   // large host-buffer batches go in chunks through a three-stream pipeline (find_batch_chunked)
   uint32_t    host_chunk = 131072;      // needles per chunk (option "host_chunk"; 0: never chunk)
-  struct Pipe {
-    hipStream_t s_in = nullptr, s_run = nullptr, s_out = nullptr;
-    hipEvent_t  ev_in[2] = {nullptr, nullptr}, ev_run[2] = {nullptr, nullptr}, ev_out[2] = {nullptr, nullptr};
-    unsigned char* h_in[2] = {nullptr, nullptr};     // pinned
-    unsigned char* h_out[2] = {nullptr, nullptr};
+  struct __attribute__((visibility("hidden"))) Pipe {
+    blurrily::detail::Stream    s_in, s_run, s_out;
+    blurrily::detail::Events<2> ev_in, ev_run, ev_out;   // (timing disabled) one per slot
+    blurrily::detail::HostPage  h_in[2], h_out[2];       // pinned
     size_t h_in_bytes = 0, h_out_bytes = 0;
     blurrily::detail::DeviceBuffer d_in[2], d_out[2];
   } pipe;
@@ -215,7 +204,11 @@ struct trigram_map_t {
 namespace blurrily {
 namespace detail __attribute__((visibility("hidden"))) {
 
-constexpr size_t kPhaseWorkgroups = 8192, kPhaseBytes = kPhaseWorkgroups * 16 * 8;
+constexpr size_t kPhaseWorkgroups = 8192, kPhaseWords = kPhaseWorkgroups * 16, kPhaseBytes = kPhaseWords * 8;
+// The measured choices are forgotten -- every class is measured again by its next batch -- when an option that bears
+// on them is set, when the base image is rebuilt, when a replica's image is cloned again.  What the watch holds
+// (the figures, the strikes, the hold-off) stays.
+inline void forget_choices(trigram_map_t* m) { for (ClassChoice& c : m->cls) c.choice = 0; }
 constexpr uint64_t kMaxBatchNeedles = 0xFFFFFFF0ull;   // needles (or references) a call takes: the kernels count them in 32 bits
 
 // ---- map_log.hip ------------------------------------------------------------------------------------------------------
@@ -367,20 +360,13 @@ template <class Rows> int above_row_off(size_t n, Rows rows, const void* results
   return 1;
 }
 // device scratch of one threshold call, freed on the way out (b[8], b[9]: the scoped calls' own)
-struct AboveScratch {
-  DeviceBuffer b[10];
-  ~AboveScratch() { for (auto& x : b) x.release(); }
-};
+struct AboveScratch { DeviceBuffer b[10]; };
 // What the count step found, kept for the emit step: per image and needle, on the device and on the host.
 struct AboveCounted {
   DeviceBuffer          d_counts;      // [n_img * n]
   std::vector<uint32_t> cnt;           // the same, read back
   size_t                n = 0;
   uint32_t              n_img = 0;
-  AboveCounted() = default;
-  AboveCounted(const AboveCounted&) = delete;
-  AboveCounted& operator=(const AboveCounted&) = delete;
-  ~AboveCounted() { d_counts.release(); }
   uint64_t rows(size_t q) const { return uint64_t(cnt[q]) + (n_img > 1 ? cnt[n + q] : 0u); }
 };
 // The threshold find in its two steps.  above_count: the rows of each of n needles over the map as it is now (waits for
@@ -411,10 +397,7 @@ struct SimilarTables {
 };
 int similar_table(DeviceIndex* ix, hipStream_t stream, SimilarTables& call, SimilarTable* out);
 // device scratch of one similarity call, freed on the way out (b[8], b[9]: the scoped calls' own)
-struct SimilarScratch {
-  DeviceBuffer b[10];
-  ~SimilarScratch() { for (auto& x : b) x.release(); }
-};
+struct SimilarScratch { DeviceBuffer b[10]; };
 // The top-`limit` rows of n needles over the map as it is now, to host memory: results / row_ntri [n * limit],
 // counts [n].  sm: a scoped call's masks, in the tombstone bitmaps' place.
 int similar_run(trigram_map m, size_t n, const NeedleView& N, uint32_t limit, uint32_t min_permille,

@@ -42,9 +42,9 @@ bool log_empty(const trigram_map_t* m) { const trigram_map_t* l = log_of(m); ret
 int ensure_device(trigram_map m) {
   const bool have_base = m->dev.device >= 0;
   if (!have_base || m->log_overflow || m->pending.size() + m->n_tomb > log_budget(m)) {
-    if (device_index_build(*m->host, &m->dev, m->build_opt) < 0) return -1;
+    if (device_index_build(*m->host, &m->dev, m->sweep.build_opt) < 0) return -1;
     ++m->base_builds;
-    std::fill(std::begin(m->ws_choice), std::end(m->ws_choice), 0);     // a new image: measure again
+    forget_choices(m);                                 // a new image: measure again
     clear_log(m);
     if (m->n_cus == 0) {
       hipDeviceProp_t prop;
@@ -59,7 +59,7 @@ int ensure_device(trigram_map m) {
   if (m->delta_image_version != m->delta_puts_version) {
     if (m->pending.empty()) {
       if (m->delta.device >= 0) device_index_free(&m->delta);
-    } else if (device_index_build(*m->delta_host, &m->delta, m->build_opt) < 0) {
+    } else if (device_index_build(*m->delta_host, &m->delta, m->sweep.build_opt) < 0) {
       return -1;
     }
     m->delta_image_version = m->delta_puts_version;
@@ -67,8 +67,7 @@ int ensure_device(trigram_map m) {
   // whole-map bucket sizes (nb_entries of the base run)
   std::vector<uint32_t> totals(kNumCodes);
   for (uint32_t t = 0; t < kNumCodes; ++t) totals[t] = m->host->bucket(t).used;
-  if (!m->d_code_total_now)
-    BLURRILY_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&m->d_code_total_now), kNumCodes * sizeof(uint32_t)));
+  if (m->d_code_total_now.alloc(kNumCodes) < 0) return -1;
   BLURRILY_HIP_TRY(hipMemcpy(m->d_code_total_now, totals.data(), kNumCodes * sizeof(uint32_t), hipMemcpyHostToDevice));
   m->delta_version = m->log_version;
   return 0;

@@ -12,6 +12,7 @@ namespace detail {
 // its glue one call at a time, ext/blurrily/map_ext.c:131-162 -- SURVEY.md section 8(e)'s partition, replicate and
 // shard contiguously, behind the C ABI instead of behind torch.distributed)
 
+// (on its device, its stream idle: then the side map and the replica give back what they hold)
 void free_replica(Replica& r) {
   int prev = -1;
   (void)hipGetDevice(&prev);
@@ -21,19 +22,8 @@ void free_replica(Replica& r) {
     trigram_map s = r.side;
     if (s->dev.device >= 0) device_index_free(&s->dev);
     if (s->delta.device >= 0) device_index_free(&s->delta);
-    if (s->d_code_total_now) (void)hipFree(s->d_code_total_now);
-    if (s->d_stats) (void)hipFree(s->d_stats);
-    if (s->d_phase) (void)hipFree(s->d_phase);
-    s->ws_base_rows.release(); s->ws_base_counts.release(); s->ws_delta_rows.release(); s->ws_delta_counts.release();
-    for (auto& e : s->ev) if (e) (void)hipEventDestroy(e);
-    for (auto& e : s->tune_ev) if (e) (void)hipEventDestroy(e);
-    for (auto& w : s->watch_ev) for (auto& e : w) if (e) (void)hipEventDestroy(e);
-    s->ws_codes.release(); s->ws_small.release(); s->ws_parts.release(); s->ws_flags.release(); s->ws_tomb.release();
     delete s;
   }
-  r.d_in.release(); r.d_out.release();
-  for (hipEvent_t e : {r.ev_done, r.ev_t0, r.ev_t1}) if (e) (void)hipEventDestroy(e);
-  if (r.stream) (void)hipStreamDestroy(r.stream);
   r = Replica();
   if (prev >= 0) (void)hipSetDevice(prev);
 }
@@ -78,36 +68,28 @@ static int ensure_replicas(trigram_map m) {
                              "travel through host memory\n", m->dev.device, r.device, can ? "enabling it failed" : "not offered");
     }
     DeviceScope on(r.device);
-    if (hipStreamCreateWithFlags(&r.stream, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreateWithFlags(&r.ev_done, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreate(&r.ev_t0) != hipSuccess || hipEventCreate(&r.ev_t1) != hipSuccess) {
+    if (r.stream.make() < 0 || r.ev_done.make(hipEventDisableTiming) < 0 || r.ev_t.make() < 0) {
       free_replica(r);
       errno = EIO;
       return -1;
     }
-    m->replicas.push_back(r);
+    m->replicas.push_back(std::move(r));
   }
-  if (!m->ev_ready) {
-    BLURRILY_HIP_TRY(hipEventCreateWithFlags(&m->ev_ready, hipEventDisableTiming));
-    BLURRILY_HIP_TRY(hipEventCreate(&m->ev_t0));
-    BLURRILY_HIP_TRY(hipEventCreate(&m->ev_t1));
-  }
+  if (m->ev_ready.make(hipEventDisableTiming) < 0 || m->ev_t.make() < 0) return -1;
   for (Replica& r : m->replicas) {
     trigram_map s = r.side;
-    // options and measured choices follow the primary's
-    s->build_opt = m->build_opt; s->ws_cmin = m->ws_cmin; s->nm_cmin = m->nm_cmin; s->nm_dense = m->nm_dense;
-    s->ws_min_needles = m->ws_min_needles; s->ws_autotune = m->ws_autotune; s->ws_static_slice = m->ws_static_slice;
-    s->nm_min_windows = m->nm_min_windows; s->small_sweep = m->small_sweep; s->small_min_needles = m->small_min_needles;
-    for (int c = 0; c < 8; ++c) if (m->ws_choice[c]) s->ws_choice[c] = m->ws_choice[c];
+    // the sweep's settings and the measured choices follow the primary's: its choice where it has one -- and, after a
+    // clone, only those
+    s->sweep = m->sweep;
     s->n_cus = 0;
     if (r.base_builds != m->base_builds || s->dev.device < 0) {
       if (device_index_clone(m->dev, r.device, &s->dev) < 0) return -1;
-      std::fill(std::begin(s->ws_choice), std::end(s->ws_choice), 0);
-      for (int c = 0; c < 8; ++c) s->ws_choice[c] = m->ws_choice[c];
+      forget_choices(s);
       r.base_builds = m->base_builds;
       r.log_version = ~0ull;                                   // (tombstones and totals below)
       r.delta_image_version = ~0ull;
     }
+    for (int c = 0; c < 8; ++c) if (m->cls[c].choice) s->cls[c].choice = m->cls[c].choice;
     if (s->n_cus == 0) {
       hipDeviceProp_t prop;
       BLURRILY_HIP_TRY(hipGetDeviceProperties(&prop, r.device));
@@ -123,8 +105,7 @@ static int ensure_replicas(trigram_map m) {
       BLURRILY_HIP_TRY(hipMemcpyPeer(s->dev.d_tomb, r.device, m->dev.d_tomb, m->dev.device,
                                      ((size_t(m->dev.n_refs) + 31) / 32 + 1) * sizeof(uint32_t)));
       if (m->d_code_total_now) {
-        if (!s->d_code_total_now)
-          BLURRILY_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&s->d_code_total_now), kNumCodes * sizeof(uint32_t)));
+        if (s->d_code_total_now.alloc(kNumCodes) < 0) return -1;
         BLURRILY_HIP_TRY(hipMemcpyPeer(s->d_code_total_now, r.device, m->d_code_total_now, m->dev.device,
                                        kNumCodes * sizeof(uint32_t)));
       }
@@ -145,7 +126,7 @@ static int run_find_multi_enqueue(trigram_map m, const char* d_packed, size_t pa
   if (ensure_replicas(m) < 0) return -1;
   const size_t R = m->replicas.size() + 1;
   const int P = m->dev.device;
-  BLURRILY_HIP_TRY(hipEventRecord(m->ev_ready, stream));      // the caller's needles are in place behind this
+  BLURRILY_HIP_TRY(hipEventRecord(m->ev_ready[0], stream));      // the caller's needles are in place behind this
   const bool timing = m->timing;
   auto bound = [&](size_t r) { return n * r / R; };
   const size_t off_bytes = align_up((n + 1) * sizeof(uint64_t), 256);
@@ -161,7 +142,7 @@ static int run_find_multi_enqueue(trigram_map m, const char* d_packed, size_t pa
       return -1;
     unsigned char* in = static_cast<unsigned char*>(r.d_in.p);
     unsigned char* out = static_cast<unsigned char*>(r.d_out.p);
-    BLURRILY_HIP_TRY(hipStreamWaitEvent(r.stream, m->ev_ready, 0));
+    BLURRILY_HIP_TRY(hipStreamWaitEvent(r.stream, m->ev_ready[0], 0));
     BLURRILY_HIP_TRY(hipMemcpyPeerAsync(in, r.device, d_offsets, P, (n + 1) * sizeof(uint64_t), r.stream));
     if (packed_bytes)
       BLURRILY_HIP_TRY(hipMemcpyPeerAsync(in + off_bytes, r.device, d_packed, P, packed_bytes, r.stream));
@@ -170,38 +151,38 @@ static int run_find_multi_enqueue(trigram_map m, const char* d_packed, size_t pa
     uint32_t* nb = reinterpret_cast<uint32_t*>(out + row_bytes + cnt_bytes);
     r.side->timing = false;
     r.side->collect_stats = false;
-    if (timing) BLURRILY_HIP_TRY(hipEventRecord(r.ev_t0, r.stream));
+    if (timing) BLURRILY_HIP_TRY(hipEventRecord(r.ev_t[0], r.stream));
     // (the shard's offsets are the batch's own, from its first needle on: they index the whole needle buffer)
     if (run_find(r.side, reinterpret_cast<const char*>(in + off_bytes), packed_bytes,
                  reinterpret_cast<const uint64_t*>(in) + a, c, limit, rows, counts, d_nb ? nb : nullptr, true, true,
                  r.stream) < 0)
       return -1;
-    if (timing) BLURRILY_HIP_TRY(hipEventRecord(r.ev_t1, r.stream));
+    if (timing) BLURRILY_HIP_TRY(hipEventRecord(r.ev_t[1], r.stream));
     if (limit)
       BLURRILY_HIP_TRY(hipMemcpyPeerAsync(d_results + a * size_t(limit), P, rows, r.device,
                                           c * size_t(limit) * sizeof(trigram_match_t), r.stream));
     BLURRILY_HIP_TRY(hipMemcpyPeerAsync(d_counts + a, P, counts, r.device, c * sizeof(uint32_t), r.stream));
     if (d_nb) BLURRILY_HIP_TRY(hipMemcpyPeerAsync(d_nb + a, P, nb, r.device, c * sizeof(uint32_t), r.stream));
-    BLURRILY_HIP_TRY(hipEventRecord(r.ev_done, r.stream));
+    BLURRILY_HIP_TRY(hipEventRecord(r.ev_done[0], r.stream));
   }
   // the primary's own shard, on the caller's stream (its timing mode would wait for it: the replicas are under way)
   const size_t c0 = bound(1);
   m->timing = false;
-  if (timing) BLURRILY_HIP_TRY(hipEventRecord(m->ev_t0, stream));
+  if (timing) BLURRILY_HIP_TRY(hipEventRecord(m->ev_t[0], stream));
   const int rc = run_find(m, d_packed, packed_bytes, d_offsets, c0, limit, d_results, d_counts, d_nb, true, true, stream);
   m->timing = timing;
   if (rc < 0) return -1;
-  if (timing) BLURRILY_HIP_TRY(hipEventRecord(m->ev_t1, stream));
+  if (timing) BLURRILY_HIP_TRY(hipEventRecord(m->ev_t[1], stream));
   for (size_t k = 0; k + 1 < R; ++k)
-    if (bound(k + 2) > bound(k + 1)) BLURRILY_HIP_TRY(hipStreamWaitEvent(stream, m->replicas[k].ev_done, 0));
+    if (bound(k + 2) > bound(k + 1)) BLURRILY_HIP_TRY(hipStreamWaitEvent(stream, m->replicas[k].ev_done[0], 0));
   if (timing) {                                               // last_find_kernel_ms: the slowest shard's search
     BLURRILY_HIP_TRY(hipStreamSynchronize(stream));
     float ms = 0.f, worst = 0.f;
-    BLURRILY_HIP_TRY(hipEventElapsedTime(&worst, m->ev_t0, m->ev_t1));
+    BLURRILY_HIP_TRY(hipEventElapsedTime(&worst, m->ev_t[0], m->ev_t[1]));
     for (size_t k = 0; k + 1 < R; ++k) {
       if (bound(k + 2) == bound(k + 1)) continue;
       DeviceScope on(m->replicas[k].device);
-      BLURRILY_HIP_TRY(hipEventElapsedTime(&ms, m->replicas[k].ev_t0, m->replicas[k].ev_t1));
+      BLURRILY_HIP_TRY(hipEventElapsedTime(&ms, m->replicas[k].ev_t[0], m->replicas[k].ev_t[1]));
       worst = std::max(worst, ms);
     }
     m->last_find_ms = worst;

@@ -172,16 +172,11 @@ int scope_run(trigram_map m, blurrily_scope sc, const char* d_packed, size_t pac
 // The pinned page small direct batches go through (m->h_scope, mapped at m->d_scope), made at first use.
 int scope_page(trigram_map m) {
   if (m->h_scope) return 0;
-  unsigned char *h = nullptr, *d = nullptr;
-  hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&h), 2 * kScopePageBytes, hipHostMallocMapped | hipHostMallocCoherent);
-  if (e == hipSuccess) e = hipHostGetDevicePointer(reinterpret_cast<void**>(&d), h, 0);
-  if (e != hipSuccess) {
-    std::fprintf(stderr, "blurrily_hip: the scoped find's pinned page: %s\n", hipGetErrorString(e));
-    if (h) (void)hipHostFree(h);
-    errno = (e == hipErrorOutOfMemory) ? ENOMEM : EIO;
-    return -1;
-  }
-  m->h_scope = h; m->d_scope = d;
+  HostPage h;
+  unsigned char* d = nullptr;
+  if (h.alloc(2 * kScopePageBytes, hipHostMallocMapped | hipHostMallocCoherent) < 0) return -1;
+  BLURRILY_HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&d), h, 0));
+  m->h_scope = std::move(h); m->d_scope = d;
   return 0;
 }
 
@@ -212,7 +207,6 @@ int blurrily_scope_close(blurrily_scope* scope) {
   blurrily_scope sc = *scope;
   if (sc) {
     if (sc->d_refs.p || sc->d_mask[0].p || sc->d_mask[1].p || sc->d_direct.p) (void)hipDeviceSynchronize();
-    sc->d_refs.release(); sc->d_mask[0].release(); sc->d_mask[1].release(); sc->d_direct.release();
     delete sc;
   }
   *scope = nullptr;

@@ -25,6 +25,7 @@ struct blurrily_scope_t {
   blurrily::detail::DeviceBuffer d_direct;
   const uint32_t *m_off = nullptr, *m_ref = nullptr, *m_weight = nullptr;
   const uint16_t* m_codes = nullptr;
+  __attribute__((visibility("hidden"))) ~blurrily_scope_t() = default;   // (its buffers go with it; not a dynamic symbol)
 };
 
 namespace blurrily {

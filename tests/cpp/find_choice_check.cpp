@@ -219,16 +219,18 @@ static void the_order_of_a_measurement() {
   }
 }
 
-struct Watched {                                               // one class's state, as trigram_map_t keeps it
-  int choice = 3;
-  uint32_t strikes = 0, holdoff = 0;
+namespace {
+struct Watched : ClassChoice {                                 // one class's state, as trigram_map_t keeps it
+  Watched() { choice = 3; }
   uint64_t retunes = 0;
-  // a watched batch of watch_n needles at us_per_needle, the class measured at 10 us per needle over 4 096
-  void batch(float us_per_needle, size_t watch_n = 4096, size_t tuned_n = 4096, float tuned_us = 10.f) {
-    watch_verdict(us_per_needle * float(watch_n) / 1000.f, watch_n, tuned_n, tuned_us, &choice, &strikes, &holdoff, &retunes);
+  // a watched batch of n needles at us_per_needle, the class measured at 10 us per needle over 4 096
+  void batch(float us_per_needle, size_t n = 4096, size_t tuned_at = 4096, float tuned_us = 10.f) {
+    watch_n = n; tuned_n = tuned_at; tuned_us_per_needle = tuned_us;
+    watch_verdict(us_per_needle * float(n) / 1000.f, this, &retunes);
   }
   bool is(int c, uint32_t s, uint32_t h, uint64_t r) const { return choice == c && strikes == s && holdoff == h && retunes == r; }
 };
+}  // namespace
 
 static void the_watch() {
   EXPECT(watch_comparable(2048, 4096) && watch_comparable(8192, 4096));
