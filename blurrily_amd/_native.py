@@ -155,6 +155,11 @@ _ENTRIES = {
     # the single-linkage dendrogram: the maximum spanning forest of the edges, heights in whole per mille
     "blurrily_storage_cluster_tree": (C.c_int, [_vp, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p,
                                                 C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
+    # the dendrogram of cluster_cores' cores: core heights, and the forest of the edges capped by them
+    "blurrily_storage_cluster_core_tree": (C.c_int, [_vp, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p,
+                                                     C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32),
+                                                     C.POINTER(C.c_uint32), C.POINTER(C.c_uint64),
+                                                     C.POINTER(C.c_uint64)]),
 }
 EXPORTED_SYMBOLS = tuple(_ENTRIES)
 
@@ -219,4 +224,5 @@ NO_SCOPE = 0xFFFFFFFF                                  # BLURRILY_NO_SCOPE: a ne
 NO_CLUSTER = 0xFFFFFFFF                                # BLURRILY_NO_CLUSTER: the label of a reference the map does not hold
 KIND_NONE, KIND_NOISE, KIND_BORDER, KIND_CORE = 0, 1, 2, 3   # BLURRILY_KIND_*: the kinds of a cluster_cores call
 CLUSTER_MAX_LEVELS = 8                                 # BLURRILY_CLUSTER_MAX_LEVELS: the floors one cluster_levels call takes
+NO_CORE = 0xFFFFFFFF                                   # BLURRILY_NO_CORE: the core height of a reference that has none
 CLUSTER_TREE_MAX = 1 << 27                             # BLURRILY_CLUSTER_TREE_MAX: the references one cluster_tree call takes

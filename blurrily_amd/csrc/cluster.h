@@ -270,4 +270,60 @@ struct ClusterTreeRoundArgs {
 int launch_cluster_tree_merge(const ClusterTreeRoundArgs& a, hipStream_t stream);
 int launch_cluster_tree_flatten(const ClusterTreeRoundArgs& a, hipStream_t stream);
 
+// Cluster core tree (cluster_core_tree_kernels.hip): the dendrogram of cluster_cores' cores at
+// every floor.  core[u] is number u's core height, the min_degree-th largest height among its edges (kNoCore: no node,
+// or fewer edges), and the forest is the cluster tree's over the edges between two numbers with a core height, an
+// edge's height capped by both.
+// The core heights come from histogram refinement: while they are sought, core[u] is the lower end of a bracket of
+// `span` heights that holds u's, above[u] counts u's edges above the bracket, and a sweep sorts every edge whose height
+// lies in an end's bracket into one of that end's kCoreBuckets counters, each `width` = ceil(span / kCoreBuckets)
+// heights wide.  The settle picks the counter in which the count from the top reaches min_degree: the next bracket,
+// `width` heights wide.  A width of 1 is the last.
+constexpr uint32_t kCoreBuckets = 32;
+constexpr uint32_t kNoCore      = 0xFFFFFFFFu;
+
+// cluster_sweep_kernel's sweep once more: every edge, found from its end at the higher position, adds 1 to the counter
+// of each end whose bracket holds its height.  Nothing is united, no bracket is written.  count_edges: the edges are
+// added to totals->t.edges (the first sweep's).
+struct ClusterCoreHeightSweepArgs {
+  ClusterSweepArgs    s;         // (s.parent and s.totals are not used)
+  const uint32_t*     core;      // [n_nodes] the brackets' lower ends (kNoCore: out of the running)
+  uint32_t*           hist;      // [n_nodes * kCoreBuckets] zero when the sweep begins
+  uint32_t            span;      // heights in a bracket
+  uint32_t            width;     // heights in a counter: ceil(span / kCoreBuckets)
+  uint32_t            count_edges;
+  ClusterCoresTotals* totals;
+};
+int launch_cluster_core_height_sweep(const ClusterCoreHeightSweepArgs& a, hipStream_t stream);
+
+// A thread per number.  pass == 0, before any sweep: core[u] = kNoCore for a number that is no node, 1000 with
+// min_degree == 0 (final: no sweep follows), else min_permille, the first bracket's lower end; above[u] = 0.
+// pass >= 1, after that sweep: the walk from the top counter, the new core[u] and above[u], the counters zeroed; a
+// node whose edges are fewer than min_degree (pass 1 alone can tell) gets kNoCore, and a later pass that finds no
+// counter sets the error word.
+struct ClusterCoreHeightSettleArgs {
+  uint32_t*           core;      // [n_nodes]
+  uint32_t*           above;     // [n_nodes]
+  uint32_t*           hist;      // [n_nodes * kCoreBuckets]
+  const uint32_t*     ntri;      // [n_nodes] (0: no node)
+  uint32_t            n_nodes;
+  uint32_t            min_permille;
+  uint32_t            min_degree;
+  uint32_t            pass;
+  uint32_t            width;     // of the sweep just finished
+  ClusterCoresTotals* totals;
+};
+int launch_cluster_core_height_settle(const ClusterCoreHeightSettleArgs& a, hipStream_t stream);
+
+// cluster_tree_sweep_kernel's sweep over the edges between numbers with a core height (core[] final), the key's height
+// min(h, core[lo], core[hi]).  Round 1 counts those edges into totals->core_edges, and with count_edges (no height
+// sweep ran: every edge is one of them) into totals->t.edges too.
+struct ClusterCoreTreeSweepArgs {
+  ClusterTreeSweepArgs t;        // (t.s.parent and t.s.totals are not used)
+  const uint32_t*      core;     // [n_nodes]
+  uint32_t             count_edges;
+  ClusterCoresTotals*  totals;
+};
+int launch_cluster_core_tree_sweep(const ClusterCoreTreeSweepArgs& a, hipStream_t stream);
+
 }  // namespace blurrily

@@ -1,5 +1,5 @@
 // cluster_forest.h -- what the clustering kernels' translation units share (cluster_kernels.hip,
-// cluster_levels_kernels.hip, cluster_centres_kernels.hip, cluster_cores_kernels.hip, cluster_extend_kernels.hip, cluster_within_kernels.hip, cluster_tree_kernels.hip): the sweeps' workgroup shape and the lock-free union-find forest in device memory.  The
+// cluster_levels_kernels.hip, cluster_centres_kernels.hip, cluster_cores_kernels.hip, cluster_extend_kernels.hip, cluster_within_kernels.hip, cluster_tree_kernels.hip, cluster_core_tree_kernels.hip): the sweeps' workgroup shape and the lock-free union-find forest in device memory.  The
 // forest's invariants and why relaxed agent-scope atomics are enough: cluster_kernels.hip's header comment.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -917,6 +917,52 @@ class RawMap:
         out[held] = nodes[label[np.searchsorted(nodes, refs[held])]]
         return out
 
+    def cluster_core_tree(self, references, min_permille, min_degree):
+        """The dendrogram of ``cluster_cores``' cores at every floor from ``min_permille`` up
+        (blurrily_storage_cluster_core_tree).  A node's core height is the ``min_degree``-th largest height among its
+        edges, and an edge between two nodes that have one joins them at the least of its own height and theirs.
+        Returns ``(labels, core_permille, merges, n_clusters, n_edges, n_core_edges)``: labels[n] and core_permille[n]
+        uint32 (``_native.NO_CORE`` for a reference the map does not hold or a node of fewer than ``min_degree`` edges),
+        merges[k, 3] uint32 rows ``[a, b, permille]`` as ``cluster_tree`` gives them, and ``cluster_cores``' three
+        counts at ``(min_permille, min_degree)``.  ``cut_core_tree`` gives the cores and their labels at any higher
+        floor without another call."""
+        self._check_open()
+        mp = _permille(min_permille)
+        md = _u32(min_degree, "min_degree")
+        refs = self._refs(references)
+        n = len(refs)
+        labels, core_permille = (np.zeros(n, dtype=np.uint32) for _ in range(2))
+        merges = np.zeros((n, 3), dtype=np.uint32)
+        n_merges, n_clusters, n_edges, n_core_edges = C.c_uint32(0), C.c_uint32(0), C.c_uint64(0), C.c_uint64(0)
+        ptr = lambda a: a.ctypes.data if n else None
+        _check(self._lib.blurrily_storage_cluster_core_tree(self._h, ptr(refs), n, mp, md, ptr(labels),
+                                                            ptr(core_permille), ptr(merges), C.byref(n_merges),
+                                                            C.byref(n_clusters), C.byref(n_edges),
+                                                            C.byref(n_core_edges)))
+        return (labels, core_permille, merges[:int(n_merges.value)].copy(), int(n_clusters.value), int(n_edges.value),
+                int(n_core_edges.value))
+
+    @staticmethod
+    def cut_core_tree(references, labels, core_permille, merges, floor, min_permille=0):
+        """What ``cluster_cores(references, floor, min_degree)`` says of the cores, from a ``cluster_core_tree`` result
+        alone: ``(labels_at_floor, is_core)``.  A reference is a core at ``floor`` when its core height is at least
+        ``floor``; the cores are labelled by the smallest reference of their component under the merges with
+        ``permille >= floor``, every other node by its own reference (its anchor needs its degree at that floor,
+        which the tree does not hold), and a reference that is no node keeps ``NO_CLUSTER``.  ``min_permille`` is the
+        floor the tree was made at; a cut below it or above 1000 is refused (ValueError).  Needs no map and no GPU."""
+        core = np.asarray(core_permille, dtype=np.uint32)
+        refs = np.asarray(references, dtype=np.uint32)
+        if core.shape != refs.shape:
+            raise ValueError("references and core_permille must be of one length")
+        cut = RawMap.cut_tree(refs, labels, merges, floor, min_permille)   # (checks the rest)
+        is_core = (core != _native.NO_CORE) & (core >= _permille(floor)) & (cut != _native.NO_CLUSTER)
+        merges = np.asarray(merges, dtype=np.uint32).reshape(-1, 3)
+        kept = merges[merges[:, 2] >= floor]
+        if not np.isin(kept[:, :2], refs[is_core]).all():
+            raise ValueError("a merge at this floor names a reference that is no core there")
+        held = cut != _native.NO_CLUSTER
+        return np.where(is_core | ~held, cut, refs), is_core
+
     @staticmethod
     def merge_profile(merges, nodes=None):
         """What a caller slides the cut by: per distinct height of a ``cluster_tree`` result, highest first,
@@ -1137,6 +1183,12 @@ class Map(RawMap):
 
     def find_by_reference(self, reference, limit=LIMIT_DEFAULT):
         return super().find_by_reference(reference, limit)
+
+    def dense_tree(self, references, min_permille, min_degree):
+        """``cluster_core_tree`` over the references as a set: ``(refs, labels, core_permille, merges)``, refs
+        ascending without repeats -- what ``cut_core_tree`` takes, the counts left out."""
+        refs = np.unique(self._refs(references))
+        return (refs,) + super().cluster_core_tree(refs, min_permille, min_degree)[:3]
 
     def find_batch_by_reference(self, references, limit=LIMIT_DEFAULT):
         """``[self.find_by_reference(r, limit) for r in references]`` in one GPU batch."""

@@ -583,6 +583,43 @@ int blurrily_storage_cluster_tree(trigram_map haystack, const uint32_t* referenc
                                   uint32_t* labels, blurrily_cluster_merge_t* merges, uint32_t* n_merges,
                                   uint32_t* n_clusters, uint64_t* n_edges);
 
+/* Cluster core tree: the dendrogram of blurrily_storage_cluster_cores' cores, for a caller who does not know the floor
+ * in advance.  Uniting the ends of the merges with permille >= f, for any f >= min_permille,
+ * gives every reference with core_permille >= f (BLURRILY_NO_CORE aside) the label blurrily_storage_cluster_cores
+ * gives it at (f, min_degree).  The cores of that call are exactly those references.
+ * Nodes, T, R, m, the edge test, the height h, BLURRILY_NO_CLUSTER, repeats, absent references, unlisted bridges,
+ * deletes, pending puts, a reference put again, "devices" > 1 and the cap BLURRILY_CLUSTER_TREE_MAX: exactly as for
+ * blurrily_storage_cluster_tree.  Edges below min_permille do not exist.
+ *   Core height: c(x) is the min_degree-th largest h among x's edges, ties counted as often as they occur, so x is a
+ *           core at floor f exactly when c(x) >= f.  core_permille[i] is that of references[i]; BLURRILY_NO_CORE for
+ *           a reference that is no node and for a node with fewer than min_degree edges.  With min_degree == 0 every
+ *           node's is 1000.
+ *   Tree edges: the edges whose two ends both have a core height, each at the capped height
+ *           H = min(h, c(a), c(b)): H >= f exactly when the edge joins two cores at floor f.
+ *   Merges: the maximum spanning forest of the tree edges under blurrily_storage_cluster_tree's total order with H as
+ *           the height, unique: {a, b, permille = H} with a < b, sorted by that order; merges needs room for n records.
+ *   Labels: for a node with a core height the smallest reference of its component in that forest, for any other node
+ *           its own reference, BLURRILY_NO_CLUSTER for no node.
+ *   Counts: n_clusters, the components among the nodes with a core height -- blurrily_storage_cluster_cores'
+ *           n_clusters at (min_permille, min_degree) -- and n_merges == those nodes - n_clusters; n_edges, every edge,
+ *           byte for byte blurrily_storage_cluster's; n_core_edges, the tree edges, each once: that call's
+ *           n_core_edges.  Each of the four, and n_merges, may be NULL.
+ * All outputs depend on the map's contents, the list as a set, min_permille and min_degree only; two runs give
+ * identical bytes.  The device sweeps the map at most twice for the core heights (not at all with min_degree == 0) and
+ * once per Boruvka round.  n == 0: success, nothing written but the counts given (0).
+ * 0, or -1 with errno: EINVAL before anything needs a GPU and with nothing written (haystack NULL, min_permille > 1000,
+ * references, labels, core_permille or merges NULL with n > 0, n above BLURRILY_CLUSTER_TREE_MAX; any min_degree is
+ * valid); ENODEV without a usable GPU; EIO if a bounded loop of the device or the bound on the rounds ran out.  labels,
+ * core_permille and merges are written only on success.
+ * Not built: the borders' anchors at a cut (they need the degree at that floor), a tree within blocks, a _device
+ * variant, a protocol verb. */
+#define BLURRILY_NO_CORE 0xFFFFFFFFu
+int blurrily_storage_cluster_core_tree(trigram_map haystack, const uint32_t* references, size_t n,
+                                       uint32_t min_permille, uint32_t min_degree,
+                                       uint32_t* labels, uint32_t* core_permille,
+                                       blurrily_cluster_merge_t* merges, uint32_t* n_merges,
+                                       uint32_t* n_clusters, uint64_t* n_edges, uint64_t* n_core_edges);
+
 /* Tokeniser (ext/blurrily/tokeniser.h:34, tokeniser.c:59-119): `output` needs
  * strlen(input)+1 slots; returns the number of distinct codes, ascending. */
 int blurrily_tokeniser_parse_string(const char* input, uint16_t* output);
