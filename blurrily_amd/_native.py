@@ -155,6 +155,11 @@ _ENTRIES = {
     # the single-linkage dendrogram: the maximum spanning forest of the edges, heights in whole per mille
     "blurrily_storage_cluster_tree": (C.c_int, [_vp, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p,
                                                 C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
+    # ... of old and new references together, from the old ones' records and sweeps of the new ones alone
+    "blurrily_storage_cluster_tree_extend": (C.c_int, [_vp, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p,
+                                                       C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                       C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                                       C.POINTER(C.c_uint64)]),
     # the dendrogram of cluster_cores' cores: core heights, and the forest of the edges capped by them
     "blurrily_storage_cluster_core_tree": (C.c_int, [_vp, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p,
                                                      C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32),

@@ -270,6 +270,38 @@ struct ClusterTreeRoundArgs {
 int launch_cluster_tree_merge(const ClusterTreeRoundArgs& a, hipStream_t stream);
 int launch_cluster_tree_flatten(const ClusterTreeRoundArgs& a, hipStream_t stream);
 
+// Cluster tree extend (cluster_tree_extend_kernels.hip): the tree of old and new nodes together
+// from the records the caller holds for the old ones.  The rounds are the cluster tree's, merge and flatten as they
+// are; what offers edges to best[] differs: the new nodes' sweeps, and the old records.
+// cluster_tree_sweep_kernel's sweep with cluster_extend_sweep_kernel's needles: needle b / tasks of the launch is node
+// new_nodes[t.s.q_base + b / tasks], it sweeps EVERY window of the image, and a candidate that is the needle, or a new
+// node at a higher position, is skipped.  Round 1 counts the edges with a new end into t.s.totals->edges.
+struct ClusterTreeExtendSweepArgs {
+  ClusterTreeSweepArgs t;        // (t.s.q_base and t.s.n count in new_nodes; t.s.parent is not used)
+  const uint32_t*      new_nodes;   // the new nodes' numbers
+  const uint32_t*      is_new;   // [(n_nodes + 31) / 32]
+};
+int launch_cluster_tree_extend_sweep(const ClusterTreeExtendSweepArgs& a, hipStream_t stream);
+
+// The old records, a thread each.  Resolve, once per call: keys[i] = record i's key over the numbers of its two
+// references, its height as the caller gives it, or 0 when an end is not listed, not held (ntri == 0) or new, or the
+// height is below min_permille.  Offer, every round between the sweeps and the merge: a record with keys[i] != 0 whose
+// ends lie in different components of comp[] raises best[] of both to its key.
+struct ClusterTreeExtendRecordsArgs {
+  const ClusterTreeMerge* records;   // [n_records] the caller's, a < b as references
+  uint32_t            n_records;
+  const uint32_t*     refs;      // [n_nodes] ascending
+  const uint32_t*     ntri;      // [n_nodes]
+  const uint32_t*     is_new;    // [(n_nodes + 31) / 32]
+  uint32_t            n_nodes;
+  uint32_t            min_permille;
+  unsigned long long* keys;      // [n_records]
+  const uint32_t*     comp;      // [n_nodes]
+  unsigned long long* best;      // [n_nodes]
+};
+int launch_cluster_tree_extend_resolve(const ClusterTreeExtendRecordsArgs& a, hipStream_t stream);
+int launch_cluster_tree_extend_offer(const ClusterTreeExtendRecordsArgs& a, hipStream_t stream);
+
 // Cluster core tree (cluster_core_tree_kernels.hip): the dendrogram of cluster_cores' cores at
 // every floor.  core[u] is number u's core height, the min_degree-th largest height among its edges (kNoCore: no node,
 // or fewer edges), and the forest is the cluster tree's over the edges between two numbers with a core height, an

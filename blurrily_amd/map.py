@@ -917,6 +917,64 @@ class RawMap:
         out[held] = nodes[label[np.searchsorted(nodes, refs[held])]]
         return out
 
+    @staticmethod
+    def _records(merges, what):
+        """Tree records as a contiguous uint32[k, 3]; values that do not fit are refused, as ``_refs`` refuses them."""
+        rows = np.asarray(merges)
+        if rows.size == 0:
+            return np.zeros((0, 3), dtype=np.uint32)
+        if rows.ndim != 2 or rows.shape[1] != 3:
+            raise ValueError(f"{what} must be rows of [a, b, permille]")
+        if rows.dtype != np.uint32:
+            rows = np.array([_u32(v, what) for v in rows.reshape(-1).tolist()], dtype=np.uint32).reshape(-1, 3)
+        return np.ascontiguousarray(rows)
+
+    def cluster_tree_extend(self, old_refs, old_merges, new_refs, min_permille):
+        """The tree of ``old_refs`` and ``new_refs`` together, from the records the caller holds for the old ones
+        (blurrily_storage_cluster_tree_extend): only the new references sweep the map, the old ones are spoken for by
+        ``old_merges``.  With ``old_merges`` from ``cluster_tree(old_refs, f)`` for some ``f <= min_permille`` on old
+        rows unchanged since, the lists disjoint and every reference held, the result is ``cluster_tree``'s over both
+        lists at ``min_permille``; a component that lost a member to a delete is re-treed on its own first.  Returns
+        ``(labels_old, labels_new, merges, n_clusters, n_edges)``: merges[k, 3] uint32 as ``cluster_tree`` gives them,
+        n_edges the edges with a new end, each once.  ``cut_tree`` and ``merge_profile`` take the records as they
+        are; ``tree_changes`` tells which of the caller's to delete and to insert."""
+        self._check_open()
+        mp = _permille(min_permille)
+        old, new = self._refs(old_refs), self._refs(new_refs)
+        records = self._records(old_merges, "old_merges")
+        if len(records) > len(old):
+            raise ValueError(f"{len(records)} old records for {len(old)} old references: a forest has fewer")
+        if len(records) and ((records[:, 0] >= records[:, 1]).any() or (records[:, 2] > 1000).any()):
+            raise ValueError("an old record needs a < b and permille <= 1000")
+        n = len(old) + len(new)
+        labels_old, labels_new = np.zeros(len(old), dtype=np.uint32), np.zeros(len(new), dtype=np.uint32)
+        merges = np.zeros((n, 3), dtype=np.uint32)
+        n_merges, n_clusters, n_edges = C.c_uint32(0), C.c_uint32(0), C.c_uint64(0)
+        ptr = lambda a: a.ctypes.data if len(a) else None
+        _check(self._lib.blurrily_storage_cluster_tree_extend(self._h, ptr(old), len(old), ptr(records), len(records),
+                                                              ptr(new), len(new), mp, ptr(labels_old), ptr(labels_new),
+                                                              ptr(merges), C.byref(n_merges), C.byref(n_clusters),
+                                                              C.byref(n_edges)))
+        return labels_old, labels_new, merges[:int(n_merges.value)].copy(), int(n_clusters.value), int(n_edges.value)
+
+    @staticmethod
+    def tree_changes(old_merges, merges):
+        """What a database update after ``cluster_tree_extend`` needs: ``(removed, added)``, uint32[r, 3] and
+        uint32[s, 3] -- the records of ``old_merges`` that ``merges`` no longer holds and the records of ``merges``
+        that ``old_merges`` did not hold, whole rows compared, each in the tree's order (height descending, then a,
+        then b).  Needs no map and no GPU."""
+        was, now = RawMap._records(old_merges, "old_merges"), RawMap._records(merges, "merges")
+        # equal rows get one number: whole records are compared, the height included
+        _, number = np.unique(np.concatenate([was, now]), axis=0, return_inverse=True)
+        number = number.reshape(-1)
+        gone = ~np.isin(number[:len(was)], number[len(was):])
+        come = ~np.isin(number[len(was):], number[:len(was)])
+
+        def ordered(rows):
+            return rows[np.lexsort((rows[:, 1], rows[:, 0], 1000 - rows[:, 2].astype(np.int64)))]
+
+        return ordered(was[gone]), ordered(now[come])
+
     def cluster_core_tree(self, references, min_permille, min_degree):
         """The dendrogram of ``cluster_cores``' cores at every floor from ``min_permille`` up
         (blurrily_storage_cluster_core_tree).  A node's core height is the ``min_degree``-th largest height among its

@@ -583,6 +583,49 @@ int blurrily_storage_cluster_tree(trigram_map haystack, const uint32_t* referenc
                                   uint32_t* labels, blurrily_cluster_merge_t* merges, uint32_t* n_merges,
                                   uint32_t* n_clusters, uint64_t* n_edges);
 
+/* Cluster tree extend: the cluster tree of old and new references together, from the records the caller already holds
+ * for the old ones -- what a job that keeps a tree does after a put, without sweeping the old references again
+ * (DESIGN.md section 37).  Nodes, T, R, m, the height h, the total order, the records' form and order,
+ * BLURRILY_NO_CLUSTER, repeats, absent references, unlisted bridges, deletes, pending puts, a reference put again and
+ * the cap BLURRILY_CLUSTER_TREE_MAX (on n_old + n_new): exactly as for blurrily_storage_cluster_tree.  Old and new:
+ * exactly as for blurrily_storage_cluster_extend -- a node named by new_refs is NEW, whatever old_refs says of it.
+ *   Candidates: (a) every old record {a, b, permille} with permille >= min_permille whose two ends are both OLD nodes;
+ *           its height is taken on trust, nothing is computed again.  A record with an end that is not held, not
+ *           listed or new does not exist.  (b) Every edge of blurrily_storage_cluster_tree at min_permille with at
+ *           least one new end, at its height h.  Pairs of two old nodes are not looked at: the records speak for them.
+ *   Merges: the maximum spanning forest of the candidates under the total order, as that call gives its own;
+ *           merges needs room for n_old + n_new records.  Labels: the smallest reference of a node's component in it.
+ * labels_old[i] belongs to old_refs[i], labels_new[j] to new_refs[j].  n_edges: the edges of (b), each once; the
+ * records are not counted.
+ * The contract: when the lists are disjoint, every listed reference is held, and old_merges is what
+ * blurrily_storage_cluster_tree(old_refs, f_old) returned for some f_old <= min_permille with the map's old rows
+ * unchanged since, then the records, the two label arrays together and n_clusters are byte for byte what
+ * blurrily_storage_cluster_tree gives for the two lists in one at min_permille, and n_edges is that call's minus the
+ * tree call's over old_refs at min_permille.  (Under a strict total order the forest is unique, and an old edge the old
+ * forest left out is the worst of a cycle that is still there: it stays out.)  So a floor above the old tree's is
+ * allowed: the records below it are passed over.
+ * The records are taken on trust.  A floor BELOW the old tree's cannot be told -- the old-old edges between the two
+ * floors are missing, and nothing looks for them -- nor can a tree made before a delete or a put-again of a member,
+ * whose component may have split: run blurrily_storage_cluster_tree over that one component's remaining members, put
+ * its records in the place of the component's, then extend.  Records that are no tree's (cycles, duplicates, made-up
+ * heights) are accepted all the same: the result is the forest of the candidate set as it stands, and the call returns.
+ * n_new == 0: the forest of the records at or above the floor, n_edges 0; n_old == 0:
+ * blurrily_storage_cluster_tree(new_refs).  Both 0: success, nothing written but the counts given (0).  n_merges,
+ * n_clusters and n_edges may each be NULL.  With "devices" > 1 the primary device alone serves the call.
+ * 0, or -1 with errno: EINVAL before anything needs a GPU and with nothing written (haystack NULL, min_permille > 1000,
+ * old_refs or labels_old NULL with n_old > 0, new_refs or labels_new NULL with n_new > 0, old_merges NULL with
+ * n_old_merges > 0, merges NULL with n_old + n_new > 0, n_old + n_new above BLURRILY_CLUSTER_TREE_MAX, n_old_merges
+ * above n_old, an old record with a >= b or permille > 1000); ENODEV without a usable GPU; EIO if a bounded loop of the
+ * device's union-find or the bound on the rounds ran out.  The labels and merges are written only on success.
+ * Not built: taking references out of a tree, extending the core tree, blocks or scopes, a _device variant, a protocol
+ * verb. */
+int blurrily_storage_cluster_tree_extend(trigram_map haystack, const uint32_t* old_refs, size_t n_old,
+                                         const blurrily_cluster_merge_t* old_merges, size_t n_old_merges,
+                                         const uint32_t* new_refs, size_t n_new, uint32_t min_permille,
+                                         uint32_t* labels_old, uint32_t* labels_new,
+                                         blurrily_cluster_merge_t* merges, uint32_t* n_merges,
+                                         uint32_t* n_clusters, uint64_t* n_edges);
+
 /* Cluster core tree: the dendrogram of blurrily_storage_cluster_cores' cores, for a caller who does not know the floor
  * in advance.  Uniting the ends of the merges with permille >= f, for any f >= min_permille,
  * gives every reference with core_permille >= f (BLURRILY_NO_CORE aside) the label blurrily_storage_cluster_cores
