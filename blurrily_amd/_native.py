@@ -165,6 +165,10 @@ _ENTRIES = {
                                                      C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32),
                                                      C.POINTER(C.c_uint32), C.POINTER(C.c_uint64),
                                                      C.POINTER(C.c_uint64)]),
+    # the dendrogram within caller-given blocks: the forest of the edges whose ends carry one block key
+    "blurrily_storage_cluster_tree_within": (C.c_int, [_vp, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p,
+                                                       C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                                       C.POINTER(C.c_uint64)]),
 }
 EXPORTED_SYMBOLS = tuple(_ENTRIES)
 

@@ -358,4 +358,30 @@ struct ClusterCoreTreeSweepArgs {
 };
 int launch_cluster_core_tree_sweep(const ClusterCoreTreeSweepArgs& a, hipStream_t stream);
 
+// Cluster tree within blocks (cluster_tree_within_kernels.hip): the cluster tree over the edges
+// whose ends carry one block key.  The rounds are the cluster tree's, merge and flatten as they are; a block's edges are
+// offered to best[] by one of two kernels, as cluster_within serves a block by one of two.
+// cluster_within_kernel's direct form with the tree's ending: a pair that passes the floor and whose ends lie in
+// different components of comp[] raises best[] of both to its key; nothing is united (w.parent is not used).  Round 1
+// counts the edges into w.totals->edges; from round 2 on a needle or a member whose component is closed takes no part,
+// and a tile with no needle left does nothing.
+struct ClusterTreeWithinArgs {
+  ClusterWithinArgs   w;
+  const uint32_t*     comp;      // [n_nodes] each number's component: its root when the round began
+  const uint8_t*      closed;    // [n_nodes] by component: no edge leaves it
+  unsigned long long* best;      // [n_nodes] by component
+  uint32_t            round;     // from 1
+};
+int launch_cluster_tree_within(const ClusterTreeWithinArgs& a, hipStream_t stream);
+
+// cluster_tree_sweep_kernel's sweep with cluster_within_sweep_kernel's needles and key test: needle b / tasks of the
+// launch is number needles[t.s.q_base + b / tasks], and a candidate node under another key than the needle's is passed
+// over before the edge is counted and before comp[] is read.
+struct ClusterTreeWithinSweepArgs {
+  ClusterTreeSweepArgs t;        // (t.s.q_base and t.s.n count in needles; t.s.parent is not used)
+  const uint32_t*      needles;  // the swept blocks' numbers
+  const uint32_t*      block_of; // [n_nodes] each number's key
+};
+int launch_cluster_tree_within_sweep(const ClusterTreeWithinSweepArgs& a, hipStream_t stream);
+
 }  // namespace blurrily

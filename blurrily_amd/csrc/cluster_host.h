@@ -1,7 +1,9 @@
 // cluster_host.h -- the host-side call sequence the clustering entries share (cluster.hip, cluster_levels.hip,
-// cluster_centres.hip, cluster_cores.hip, cluster_extend.hip, cluster_within.hip, cluster_tree.hip, cluster_tree_extend.hip, cluster_core_tree.hip): the node numbering and
-// ClusterCall, which owns a call's device scratch, runs what every entry does in front of its sweeps, fills the sweeps'
-// common arguments per image and chunk, and reads the totals back.  The device code is each entry's own.
+// cluster_centres.hip, cluster_cores.hip, cluster_extend.hip, cluster_within.hip, cluster_tree.hip,
+// cluster_tree_extend.hip, cluster_core_tree.hip, cluster_tree_within.hip): the node numbering,
+// the block plan of the two within entries, the cluster tree's round bound and record order, and ClusterCall, which
+// owns a call's device scratch, runs what every entry does in front of its sweeps, fills the sweeps' common arguments
+// per image and chunk, and reads the totals back.  The device code is each entry's own.
 #pragma once
 #include <algorithm>
 #include <vector>
@@ -52,6 +54,45 @@ inline bool number_nodes_keyed(const uint32_t* references, const uint32_t* keys,
   return true;
 }
 
+// The listed members of a block up to which "scope_strategy" 0 scores the block directly.  Direct work grows with the
+// square of a block, the sweep's with the map: on configs[2]'s haystack at 700 per mille, one block of 10^5 consecutive
+// references takes the direct kernel 16 ms against the sweep's 170 ms, one of 10^6 1.96 s against 1.72 s
+// (profiles/cluster_within_geonames.json).  This is the largest size measured at which direct was no slower.
+// "scope_strategy" 1 sweeps every block, 2 scores every block directly.
+// The tree within blocks takes the same cap: its rounds multiply both kernels' work alike, so there is no reason to
+// expect another crossover -- but nobody has measured the crossover for the tree, only one block of 10^5 under either
+// kernel: 31 ms direct against 275 ms swept (profiles/cluster_tree_within_geonames.json).
+constexpr size_t kClusterWithinDirectMax = 100000;
+
+// The block plan of blurrily_storage_cluster_within and blurrily_storage_cluster_tree_within, from
+// each number's key: `order`, the numbers block after block, ascending inside a block; every block given to one of the
+// two kernels -- the direct kernel's tiles of up to kClusterWithinTile places for a block of at most
+// kClusterWithinDirectMax listed members ("scope_strategy" 2: for any block; a block of one has no pair to score and
+// gets no tile), the sweep's needle list for a larger one ("scope_strategy" 1: for every block); the tiles that pass
+// over the most members first, so that the longest workgroups do not start last (equal ones in the plan's order).
+struct ClusterWithinPlan {
+  std::vector<uint32_t>          order;
+  std::vector<ClusterWithinTile> tiles;
+  std::vector<uint32_t>          swept;
+  // On the device, after upload(): null where the plan has nothing for the kernel that would read it.
+  ClusterWithinTile* d_tiles = nullptr;
+  uint32_t *d_order = nullptr, *d_swept = nullptr, *d_block_of = nullptr;
+};
+// -1 with EINVAL: more tiles than a launch takes.  Needs no GPU.
+int plan_within_blocks(const std::vector<uint32_t>& key_of, uint32_t scope_strategy, ClusterWithinPlan& plan);
+
+// The cluster tree's rounds.  Every round that merges at least halves the components that still have an edge leaving
+// them: 28 rounds serve 2^27 nodes, and one more finds nothing.
+constexpr uint32_t kTreeMaxRounds = 40;
+
+// The order of a tree's records: height descending, then the lower reference, then the higher.
+inline void sort_tree_records(std::vector<ClusterTreeMerge>& records) {
+  std::sort(records.begin(), records.end(), [](const ClusterTreeMerge& x, const ClusterTreeMerge& y) {
+    if (x.permille != y.permille) return x.permille > y.permille;
+    return x.a != y.a ? x.a < y.a : x.b < y.b;
+  });
+}
+
 // One call of a clustering entry, from the entry's checks to its return.
 struct ClusterCall {
   ClusterCall(trigram_map m, hipStream_t stream) : m(m), stream(stream) {}
@@ -76,6 +117,10 @@ struct ClusterCall {
   // uniq and inv of n elements; both are taken over)
   int begin(std::vector<uint32_t>&& numbering, std::vector<uint32_t>&& element_number, size_t n, uint32_t forests,
             size_t totals_bytes);
+
+  // A block plan onto the device, after begin(): the tiles with `order` if there are tiles, the swept numbers with
+  // every number's key (key_of, nu of them) if a block is swept.
+  int upload(ClusterWithinPlan& plan, const std::vector<uint32_t>& key_of);
 
   // `needles` needles (of the numbering, or of an entry's own list) over every image, in chunks: the sweep arguments
   // all entries share, handed to launch(const ClusterSweepArgs&), which adds the entry's own and launches.

@@ -4,6 +4,61 @@
 namespace blurrily {
 namespace detail {
 
+int plan_within_blocks(const std::vector<uint32_t>& key_of, uint32_t scope_strategy, ClusterWithinPlan& plan) {
+  // the numbers block after block, ascending inside a block (keys that ascend with the numbers already are)
+  const size_t nu = key_of.size();
+  std::vector<uint32_t>& order = plan.order;
+  order.resize(nu);
+  if (std::is_sorted(key_of.begin(), key_of.end())) {
+    for (size_t u = 0; u < nu; ++u) order[u] = uint32_t(u);
+  } else {
+    std::vector<uint64_t> keyed(nu);
+    for (size_t u = 0; u < nu; ++u) keyed[u] = (uint64_t(key_of[u]) << 32) | u;
+    std::sort(keyed.begin(), keyed.end());
+    for (size_t u = 0; u < nu; ++u) order[u] = uint32_t(keyed[u]);
+  }
+  std::vector<ClusterWithinTile>& tiles = plan.tiles;
+  for (size_t b = 0; b < nu;) {
+    size_t e = b + 1;
+    while (e < nu && key_of[order[e]] == key_of[order[b]]) ++e;
+    const bool direct = scope_strategy == 2 || (scope_strategy == 0 && e - b <= kClusterWithinDirectMax);
+    if (!direct) {
+      plan.swept.insert(plan.swept.end(), order.begin() + b, order.begin() + e);
+    } else if (e - b > 1) {                                   // (a block of one has no pair to score)
+      for (size_t f = b; f < e; f += kClusterWithinTile)
+        tiles.push_back({uint32_t(b), uint32_t(f), uint32_t(std::min<size_t>(kClusterWithinTile, e - f))});
+    }
+    b = e;
+  }
+  // the tiles that pass over the most members first: the longest workgroups do not start last
+  // (equal ones in the plan's order)
+  if (tiles.size() > 0x7FFFFFFFull) { errno = EINVAL; return -1; }
+  std::vector<uint64_t> by_scan(tiles.size());
+  for (size_t t = 0; t < tiles.size(); ++t)
+    by_scan[t] = (uint64_t(~(tiles[t].first + tiles[t].count - tiles[t].begin)) << 32) | t;
+  std::sort(by_scan.begin(), by_scan.end());
+  std::vector<ClusterWithinTile> sorted(tiles.size());
+  for (size_t t = 0; t < tiles.size(); ++t) sorted[t] = tiles[uint32_t(by_scan[t])];
+  tiles.swap(sorted);
+  return 0;
+}
+
+int ClusterCall::upload(ClusterWithinPlan& plan, const std::vector<uint32_t>& key_of) {
+  const std::vector<ClusterWithinTile>& tiles = plan.tiles;
+  if (more(plan.d_tiles, tiles.size() * sizeof(ClusterWithinTile)) < 0 || more(plan.d_swept, plan.swept.size() * 4) < 0 ||
+      (!tiles.empty() && more(plan.d_order, nu * 4) < 0) || (!plan.swept.empty() && more(plan.d_block_of, nu * 4) < 0))
+    return -1;
+  if (plan.d_tiles) {
+    BLURRILY_HIP_TRY(hipMemcpyAsync(plan.d_tiles, tiles.data(), tiles.size() * sizeof(ClusterWithinTile), hipMemcpyHostToDevice, stream));
+    BLURRILY_HIP_TRY(hipMemcpyAsync(plan.d_order, plan.order.data(), nu * 4, hipMemcpyHostToDevice, stream));
+  }
+  if (plan.d_swept) {
+    BLURRILY_HIP_TRY(hipMemcpyAsync(plan.d_swept, plan.swept.data(), plan.swept.size() * 4, hipMemcpyHostToDevice, stream));
+    BLURRILY_HIP_TRY(hipMemcpyAsync(plan.d_block_of, key_of.data(), nu * 4, hipMemcpyHostToDevice, stream));
+  }
+  return 0;
+}
+
 ClusterCall::~ClusterCall() {
   for (void* p : buffers) (void)hipFree(p);
 }

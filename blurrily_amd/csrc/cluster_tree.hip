@@ -17,10 +17,6 @@ static_assert(kTreeMaxNodes == BLURRILY_CLUSTER_TREE_MAX, "the header's cap is t
 static_assert(sizeof(ClusterTreeMerge) == sizeof(blurrily_cluster_merge_t) && sizeof(ClusterTreeMerge) == 12,
               "the kernels' record is the header's");
 
-// Every round that merges at least halves the components that still have an edge leaving them: 28 rounds serve 2^27
-// nodes, and one more finds nothing.
-constexpr uint32_t kTreeMaxRounds = 40;
-
 extern "C" int blurrily_storage_cluster_tree(trigram_map m, const uint32_t* references, size_t n, uint32_t min_permille,
                                              uint32_t* labels, blurrily_cluster_merge_t* merges, uint32_t* n_merges,
                                              uint32_t* n_clusters, uint64_t* n_edges) {
@@ -74,11 +70,7 @@ extern "C" int blurrily_storage_cluster_tree(trigram_map m, const uint32_t* refe
     BLURRILY_HIP_TRY(hipMemcpyAsync(got.data(), r.merges, found * sizeof(ClusterTreeMerge), hipMemcpyDeviceToHost, stream));
   BLURRILY_HIP_TRY(hipMemcpyAsync(labels, c.d_labels, n * 4, hipMemcpyDeviceToHost, stream));
   if (c.wait(&totals) < 0) return -1;
-  // the order of the records: height descending, then the lower reference, then the higher
-  std::sort(got.begin(), got.end(), [](const ClusterTreeMerge& x, const ClusterTreeMerge& y) {
-    if (x.permille != y.permille) return x.permille > y.permille;
-    return x.a != y.a ? x.a < y.a : x.b < y.b;
-  });
+  sort_tree_records(got);
   for (uint32_t i = 0; i < found; ++i) merges[i] = {got[i].a, got[i].b, got[i].permille};
   if (n_merges) *n_merges = found;
   if (n_clusters) *n_clusters = totals.clusters;

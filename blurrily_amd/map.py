@@ -1021,6 +1021,50 @@ class RawMap:
         held = cut != _native.NO_CLUSTER
         return np.where(is_core | ~held, cut, refs), is_core
 
+    def cluster_tree_within(self, references, blocks, min_permille):
+        """``cluster_tree`` within blocks (blurrily_storage_cluster_tree_within): ``blocks[i]`` is a 32-bit key for
+        ``references[i]``, and only references under one key are ever joined.  One call serves all blocks.  Returns
+        ``(labels, merges, n_clusters, n_edges)``: labels[n] uint32, n_clusters and n_edges as ``cluster_within`` gives
+        them at ``min_permille``, and merges[k, 3] uint32 as ``cluster_tree`` gives them -- what one ``cluster_tree``
+        call per block gives, the records merged into one list in the tree's order.  ``cut_tree`` gives
+        ``cluster_within``'s labels at any higher floor without another call, ``merge_profile`` takes the records as
+        they are, and ``tree_by_block`` splits them by key."""
+        self._check_open()
+        mp = _permille(min_permille)
+        refs, keys = self._refs(references), self._refs(blocks)
+        if len(keys) != len(refs):
+            raise ValueError(f"{len(keys)} block keys for {len(refs)} references")
+        n = len(refs)
+        labels = np.zeros(n, dtype=np.uint32)
+        merges = np.zeros((n, 3), dtype=np.uint32)
+        n_merges, n_clusters, n_edges = C.c_uint32(0), C.c_uint32(0), C.c_uint64(0)
+        ptr = lambda a: a.ctypes.data if n else None
+        _check(self._lib.blurrily_storage_cluster_tree_within(self._h, ptr(refs), ptr(keys), n, mp, ptr(labels),
+                                                              ptr(merges), C.byref(n_merges), C.byref(n_clusters),
+                                                              C.byref(n_edges)))
+        return labels, merges[:int(n_merges.value)].copy(), int(n_clusters.value), int(n_edges.value)
+
+    @staticmethod
+    def tree_by_block(merges, references, blocks):
+        """A ``cluster_tree_within`` result split by block, for the caller who stores a tree per block:
+        ``{key: merges rows}``, uint32[k, 3] each, in the tree's order (the order the records come in).  Only keys with
+        a record appear.  ValueError for a record whose ends carry two keys or name a reference that is not listed.
+        Needs no map and no GPU."""
+        rows = RawMap._records(merges, "merges")
+        refs, keys = np.asarray(references, dtype=np.uint32), np.asarray(blocks, dtype=np.uint32)
+        if refs.ndim != 1 or keys.shape != refs.shape:
+            raise ValueError("references and blocks must be one-dimensional and of one length")
+        if not len(rows):
+            return {}
+        listed, at = np.unique(refs, return_index=True)
+        ends = np.searchsorted(listed, rows[:, :2])
+        if len(listed) == 0 or (listed[np.minimum(ends, len(listed) - 1)] != rows[:, :2]).any():
+            raise ValueError("a record names a reference that is not listed")
+        key = keys[at][ends]
+        if (key[:, 0] != key[:, 1]).any():
+            raise ValueError("a record joins references under two keys")
+        return {int(k): rows[key[:, 0] == k] for k in np.unique(key[:, 0]).tolist()}
+
     @staticmethod
     def merge_profile(merges, nodes=None):
         """What a caller slides the cut by: per distinct height of a ``cluster_tree`` result, highest first,

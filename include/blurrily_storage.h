@@ -576,7 +576,8 @@ int blurrily_storage_cluster_within(trigram_map haystack, const uint32_t* refere
  * references, labels or merges NULL with n > 0, n above BLURRILY_CLUSTER_TREE_MAX: the device orders edges by one
  * 64-bit word that holds the height and both ends in 27 bits each); ENODEV without a usable GPU; EIO if a bounded loop
  * of the device's union-find or the bound on the rounds ran out.  The labels and merges are written only on success.
- * Not built: a tree within blocks or scopes, a _device variant, other linkages, a protocol verb. */
+ * Not built: a tree within scopes, a _device variant, other linkages, a protocol verb.  (Within blocks:
+ * blurrily_storage_cluster_tree_within below.) */
 #define BLURRILY_CLUSTER_TREE_MAX 0x8000000u
 typedef struct { uint32_t a, b, permille; } blurrily_cluster_merge_t;
 int blurrily_storage_cluster_tree(trigram_map haystack, const uint32_t* references, size_t n, uint32_t min_permille,
@@ -662,6 +663,38 @@ int blurrily_storage_cluster_core_tree(trigram_map haystack, const uint32_t* ref
                                        uint32_t* labels, uint32_t* core_permille,
                                        blurrily_cluster_merge_t* merges, uint32_t* n_merges,
                                        uint32_t* n_clusters, uint64_t* n_edges, uint64_t* n_core_edges);
+
+/* Cluster tree within blocks: the single-linkage dendrogram inside caller-given blocks, one call for all blocks -- for
+ * the caller who blocks by country, tenant or postcode and does not know the floor in advance.
+ * blocks[i] is an opaque 32-bit key for references[i].  Nodes, T, R, m, the edge test, the height
+ * h = floor(1000 * m / (T + R - m)), the total order, the records' form and order, BLURRILY_NO_CLUSTER, repeats (under one
+ * key), a shuffled list, absent references, unlisted bridges, deletes, pending puts, a reference put again,
+ * "devices" > 1 and the cap BLURRILY_CLUSTER_TREE_MAX: exactly as for blurrily_storage_cluster_within and
+ * blurrily_storage_cluster_tree.
+ *   Edges:  blurrily_storage_cluster's edges at min_permille whose two ends carry the same key.
+ *   Merges: the maximum spanning forest of those edges under blurrily_storage_cluster_tree's total order (height
+ *           descending, lower reference ascending, higher reference ascending), which is unique.
+ *           merges[0 .. *n_merges) are its edges {a, b, permille} with a < b, sorted by that order; merges needs room
+ *           for n records.  No record joins two keys.  n_merges == nodes - n_clusters, always.
+ *   Labels: labels, n_clusters and n_edges are byte for byte blurrily_storage_cluster_within's at min_permille.
+ * Uniting the ends of the merges with permille >= f, for any f >= min_permille, gives exactly the labels of
+ * blurrily_storage_cluster_within at floor f.  The result equals one blurrily_storage_cluster_tree call per block: the
+ * records of those calls merged into one list under the total order, the labels put back in place, the counts
+ * summed.  With all keys equal it is blurrily_storage_cluster_tree, byte for byte; with all keys distinct there is no
+ * record and every held reference is its own label.  All outputs depend on the map's contents, the set of (reference,
+ * key) pairs and min_permille only; two runs give identical bytes.  A small block is scored member against member from
+ * the device's copy of its members' trigrams once per Boruvka round, a large one sweeps the map once per round; option
+ * "scope_strategy" chooses as for blurrily_storage_cluster_within.  n_merges, n_clusters and n_edges may each be NULL.
+ * n == 0: success, nothing written but the counts given (0).
+ * 0, or -1 with errno: EINVAL before anything needs a GPU and with nothing written (haystack NULL, min_permille > 1000,
+ * references, blocks, labels or merges NULL with n > 0, n above BLURRILY_CLUSTER_TREE_MAX, a reference listed more than
+ * once with different keys); ENODEV without a usable GPU; EIO if a bounded loop of the device's union-find or the bound
+ * on the rounds ran out.  The labels and merges are written only on success.
+ * Not built: the core tree and tree extend within blocks, a _device variant, a protocol verb. */
+int blurrily_storage_cluster_tree_within(trigram_map haystack, const uint32_t* references, const uint32_t* blocks,
+                                         size_t n, uint32_t min_permille, uint32_t* labels,
+                                         blurrily_cluster_merge_t* merges, uint32_t* n_merges,
+                                         uint32_t* n_clusters, uint64_t* n_edges);
 
 /* Tokeniser (ext/blurrily/tokeniser.h:34, tokeniser.c:59-119): `output` needs
  * strlen(input)+1 slots; returns the number of distinct codes, ascending. */
