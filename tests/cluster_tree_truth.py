@@ -99,6 +99,46 @@ def boruvka(truth, listed, floor, least=None):
     return chosen, rounds
 
 
+def boruvka_rounds(truth, listed, floor, least=None):
+    """boruvka() that also tells which edge was picked in which round and what the components were after each:
+    ({(a, b, permille) in references: round, counted from 1}, the rounds that merged something, [after round k, k = 1 ..:
+    every index's component as an index into truth.refs, the lowest of the component])."""
+    lo, hi, h = edges(truth, listed, floor, least)
+    assert len(truth.refs) <= MASK
+    key = (h.astype(np.uint64) << np.uint64(2 * BITS)) | ((MASK - lo).astype(np.uint64) << np.uint64(BITS)) | \
+        (MASK - hi).astype(np.uint64)
+    comp = np.arange(len(truth.refs), dtype=np.int64)
+    picked_in, after = {}, []
+    while True:
+        out = comp[lo] != comp[hi]
+        lo, hi, key = lo[out], hi[out], key[out]
+        if len(lo) == 0:
+            break
+        best = np.zeros(len(comp), dtype=np.uint64)
+        np.maximum.at(best, comp[lo], key)
+        np.maximum.at(best, comp[hi], key)
+        picked = np.unique(best[best != 0])
+        pl = MASK - ((picked >> np.uint64(BITS)) & np.uint64(MASK)).astype(np.int64)
+        ph = MASK - (picked & np.uint64(MASK)).astype(np.int64)
+        pk = (picked >> np.uint64(2 * BITS)).astype(np.int64)
+        for e in zip(truth.refs[pl].tolist(), truth.refs[ph].tolist(), pk.tolist()):
+            assert e not in picked_in                         # (an edge is picked in one round only)
+            picked_in[e] = len(after) + 1
+        low = comp.copy()                                     # the picked edges united: the lowest index spreads
+        while True:
+            nxt = low.copy()
+            m = np.minimum(low[comp[pl]], low[comp[ph]])
+            np.minimum.at(nxt, comp[pl], m)
+            np.minimum.at(nxt, comp[ph], m)
+            nxt = nxt[nxt]
+            if np.array_equal(nxt, low):
+                break
+            low = nxt
+        comp = low[comp]
+        after.append(comp.copy())
+    return picked_in, len(after), after
+
+
 def cut(records, listed_labels, listed, floor):
     """The labels of `listed` after uniting the records with permille >= floor, by a plain union-find (the check of
     RawMap.cut_tree that shares no code with it).  listed_labels tell which references are held."""
