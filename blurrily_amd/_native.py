@@ -169,6 +169,12 @@ _ENTRIES = {
     "blurrily_storage_cluster_tree_within": (C.c_int, [_vp, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p,
                                                        C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
                                                        C.POINTER(C.c_uint64)]),
+    # the edges themselves, each pair once, as sorted {a, b, permille} records: capacity protocol, n_edges required
+    "blurrily_storage_cluster_edges": (C.c_int, [_vp, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_uint64,
+                                                 C.POINTER(C.c_uint64)]),
+    # ... of the graph within caller-given blocks
+    "blurrily_storage_cluster_edges_within": (C.c_int, [_vp, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32,
+                                                        C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
 }
 EXPORTED_SYMBOLS = tuple(_ENTRIES)
 

@@ -14,6 +14,7 @@
 #include <cstdint>
 
 #include "device_index.h"
+#include "segsort.h"
 
 namespace blurrily {
 
@@ -383,5 +384,65 @@ struct ClusterTreeWithinSweepArgs {
   const uint32_t*      block_of; // [n_nodes] each number's key
 };
 int launch_cluster_tree_within_sweep(const ClusterTreeWithinSweepArgs& a, hipStream_t stream);
+
+// Cluster edges (cluster_edges_kernels.hip): the edges themselves, each once, where every other
+// entry forgets them.  A sweep that finds an edge appends its key, the cluster tree's total order as one word that is
+// sorted ASCENDING: (1000 - h) << 54 | lo << 27 | hi, lo < hi the two numbers (kTreeNumberBits each).  Keys are distinct:
+// an edge is found once.
+struct ClusterEdgeKey {
+  unsigned long long k;
+};
+// Where a call's launches append, all of them through one cursor: a wave adds its lanes' edges to *cursor once and
+// stores the keys whose slot lies below `room`.  The cursor counts on past the room, so its final value is the edge
+// count whatever was stored (room == 0: nothing is, keys may be null).
+struct ClusterEdgesOut {
+  unsigned long long* cursor;    // [1] zero when the call begins
+  ClusterEdgeKey*     keys;      // [room]
+  unsigned long long  room;
+};
+// cluster_sweep_kernel's sweep with the append for an ending.  needles == nullptr: needle b / tasks of the launch is
+// number s.q_base + b / tasks, as cluster_sweep_kernel's.  Otherwise it is needles[s.q_base + b / tasks] and a candidate
+// under another key of block_of[] is passed over before the edge is counted, as cluster_within_sweep_kernel's.
+struct ClusterEdgesSweepArgs {
+  ClusterSweepArgs s;            // (s.parent and s.totals are not used)
+  const uint32_t*  needles;      // the swept blocks' numbers, or null
+  const uint32_t*  block_of;     // [n_nodes] each number's key (null with needles)
+  ClusterEdgesOut  out;
+};
+int launch_cluster_edges_sweep(const ClusterEdgesSweepArgs& a, hipStream_t stream);
+// cluster_within_kernel's direct form with the same ending (w.parent and w.totals are not used).
+struct ClusterEdgesWithinArgs {
+  ClusterWithinArgs w;
+  ClusterEdgesOut   out;
+};
+int launch_cluster_edges_within(const ClusterEdgesWithinArgs& a, hipStream_t stream);
+
+// Sorting the keys ascending, one segment (segsort.h): cluster_edges_tiles_kernel, a bitonic sort in LDS per tile, and
+// the shared merge passes.
+constexpr uint32_t kClusterEdgesTile = 4096;
+int launch_cluster_edges_tiles(const SegTile* tiles, uint32_t n_tiles, const ClusterEdgeKey* in, ClusterEdgeKey* out,
+                               hipStream_t stream);
+int launch_cluster_edges_merge(const SegMergeArgs<ClusterEdgeKey>& a, hipStream_t stream);
+template <>
+struct SegKey<ClusterEdgeKey> {
+  static constexpr uint32_t kTile = kClusterEdgesTile;
+  static int tiles(const SegTile* t, uint32_t n, const ClusterEdgeKey* in, ClusterEdgeKey* out, hipStream_t s) {
+    return launch_cluster_edges_tiles(t, n, in, out, s);
+  }
+  static int merge(const SegMergeArgs<ClusterEdgeKey>& a, hipStream_t s) { return launch_cluster_edges_merge(a, s); }
+#ifdef __HIPCC__
+  __device__ static bool less(ClusterEdgeKey a, ClusterEdgeKey b) { return a.k < b.k; }
+#endif
+};
+
+// Key i to record i: {refs[lo], refs[hi], 1000 - (key >> 54)}.
+struct ClusterEdgesRowsArgs {
+  const ClusterEdgeKey* keys;    // [n_keys] sorted
+  const uint32_t*       refs;    // [n_nodes] ascending
+  uint32_t              n_keys;
+  uint32_t              n_nodes;
+  ClusterTreeMerge*     rows;    // [n_keys]
+};
+int launch_cluster_edges_rows(const ClusterEdgesRowsArgs& a, hipStream_t stream);
 
 }  // namespace blurrily

@@ -1,6 +1,6 @@
 // cluster_host.h -- the host-side call sequence the clustering entries share (cluster.hip, cluster_levels.hip,
 // cluster_centres.hip, cluster_cores.hip, cluster_extend.hip, cluster_within.hip, cluster_tree.hip,
-// cluster_tree_extend.hip, cluster_core_tree.hip, cluster_tree_within.hip): the node numbering,
+// cluster_tree_extend.hip, cluster_core_tree.hip, cluster_tree_within.hip, cluster_edges.hip): the node numbering,
 // the block plan of the two within entries, the cluster tree's round bound and record order, and ClusterCall, which
 // owns a call's device scratch, runs what every entry does in front of its sweeps, fills the sweeps' common arguments
 // per image and chunk, and reads the totals back.  The device code is each entry's own.

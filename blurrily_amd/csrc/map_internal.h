@@ -166,6 +166,9 @@ struct trigram_map_t {
   // finds take 193 against 122 us -- profiles/scope_geonames.json)
   uint32_t    scope_strategy = 0;
   uint64_t    scope_direct_max = 150000;
+  // cluster edges: option "cluster_edges_max", the records one call may emit -- the bound on its
+  // device scratch, 28 bytes a record (two rows of 8-byte keys for the sort, the 12-byte records): 7 GiB at the default
+  uint64_t    cluster_edges_max = uint64_t(1) << 28;
   blurrily::detail::HostPage h_scope;   // [kScopePageBytes in | kScopePageBytes out]
   unsigned char* d_scope = nullptr;     // the same memory as the device addresses it
   // a scope per needle: the call's plan on the device (scope table, workgroup order, the groups'

@@ -73,7 +73,8 @@ const Option kMapOptions[] = {
     {"mid_max", 0, kMidMaxNeedles, PLAIN(one.mid_max), false},
     {"latency_tasks", 0, 16, PLAIN(latency_tasks), false},
     {"scope_strategy", 0, 2, PLAIN(scope_strategy), false}, // (scoped finds only: nothing to measure again)
-    {"scope_direct_max", 0, 1ll << 40, PLAIN(scope_direct_max), false}};
+    {"scope_direct_max", 0, 1ll << 40, PLAIN(scope_direct_max), false},
+    {"cluster_edges_max", 1, 1ll << 31, PLAIN(cluster_edges_max), false}};   // (records one cluster_edges call may emit)
 
 #undef UP_TO_U32
 #undef PLAIN

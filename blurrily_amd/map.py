@@ -1065,11 +1065,89 @@ class RawMap:
             raise ValueError("a record joins references under two keys")
         return {int(k): rows[key[:, 0] == k] for k in np.unique(key[:, 0]).tolist()}
 
+    def _cluster_edges_call(self, references, min_permille, blocks):
+        """What the two edge methods share: ``(call(rows, cap, n_edges), n)`` for the unblocked symbol
+        (``blocks`` None) or the blocked one."""
+        self._check_open()
+        mp = _permille(min_permille)
+        refs = self._refs(references)
+        n = len(refs)
+        ptr = lambda a: a.ctypes.data if n else None
+        if blocks is None:
+            return (lambda rows, cap, n_edges: self._lib.blurrily_storage_cluster_edges(
+                self._h, ptr(refs), n, mp, rows, cap, n_edges)), n
+        keys = self._refs(blocks)
+        if len(keys) != n:
+            raise ValueError(f"{len(keys)} block keys for {n} references")
+        return (lambda rows, cap, n_edges: self._lib.blurrily_storage_cluster_edges_within(
+            self._h, ptr(refs), ptr(keys), n, mp, rows, cap, n_edges)), n
+
+    def cluster_edges(self, references, min_permille, blocks=None, capacity=None):
+        """The edges of ``cluster``'s graph themselves (blurrily_storage_cluster_edges), or with ``blocks`` of
+        ``cluster_within``'s (blurrily_storage_cluster_edges_within): edges[E, 3] uint32, one row ``[a, b, permille]``
+        per pair of listed references at or above ``min_permille``, a < b, permille the similarity in whole per mille
+        rounded down, sorted as ``cluster_tree``'s merges are (height descending, then a, then b).  E is ``cluster``'s
+        n_edges.  The first call has room for ``capacity`` records (default ``max(1024, 8 n)``); if there are more, one
+        more call is made with the room the first reported.  OSError EOVERFLOW when the edges outnumber option
+        "cluster_edges_max": raise the floor, block or split the list.  ``tree_by_block``, ``cut_tree`` (with
+        ``cluster``'s labels) and ``merge_profile`` take the records as they are; ``adjacency`` turns them into
+        neighbour lists."""
+        call, n = self._cluster_edges_call(references, min_permille, blocks)
+        total = C.c_uint64(0)
+        first = max(1024, 8 * n) if capacity is None else int(capacity)
+        if not 0 <= first < 1 << 64:
+            raise OverflowError(f"capacity {capacity!r} out of range of uint64_t")
+        rows = _call_growing(lambda rows, cap: call(rows, cap, C.byref(total)), first, lambda: int(total.value), row=(3,))
+        return rows[:int(total.value)]
+
+    def cluster_edge_count(self, references, min_permille, blocks=None):
+        """How many records ``cluster_edges`` would return, without sorting or fetching them: no buffer is handed."""
+        call, _ = self._cluster_edges_call(references, min_permille, blocks)
+        total = C.c_uint64(0)
+        _check(call(None, 0, C.byref(total)))
+        return int(total.value)
+
+    @staticmethod
+    def adjacency(edges, references):
+        """``cluster_edges`` records as neighbour lists, what a caller's own graph code starts from:
+        ``(row_off uint64[n + 1], neighbour uint32[2 E], permille uint32[2 E])``, one row per element of ``references``
+        -- element i's neighbours are ``neighbour[row_off[i]:row_off[i + 1]]`` with their similarities beside them, in
+        the records' order.  A repeated reference gets the same row each time it is listed (so the rows add up to more
+        than 2 E then); one that no record names gets an empty row.  ValueError for a record that names a reference
+        which is not listed.  Needs no map and no GPU."""
+        rows = RawMap._records(edges, "edges")
+        refs = np.asarray(references, dtype=np.uint32)
+        if refs.ndim != 1:
+            raise ValueError("references must be one-dimensional")
+        listed = np.unique(refs)
+        ends = np.searchsorted(listed, rows[:, :2])
+        if len(rows) and (len(listed) == 0 or (listed[np.minimum(ends, len(listed) - 1)] != rows[:, :2]).any()):
+            raise ValueError("a record names a reference that is not listed")
+        # every record twice, once from each end, kept in the records' order per end
+        src = np.concatenate([ends[:, 0], ends[:, 1]]) if len(rows) else np.zeros(0, dtype=np.int64)
+        dst = np.concatenate([rows[:, 1], rows[:, 0]])
+        sim = np.concatenate([rows[:, 2], rows[:, 2]])
+        at = np.concatenate([np.arange(len(rows)), np.arange(len(rows))])
+        order = np.lexsort((at, src))
+        dst, sim = dst[order], sim[order]
+        start = np.zeros(len(listed) + 1, dtype=np.int64)
+        np.cumsum(np.bincount(src, minlength=len(listed)), out=start[1:])
+        if len(listed) == len(refs) and (listed == refs).all():    # (the list is its own numbering: nothing to gather)
+            return start.astype(np.uint64), dst.astype(np.uint32), sim.astype(np.uint32)
+        node = np.searchsorted(listed, refs)
+        size = start[node + 1] - start[node]
+        row_off = np.zeros(len(refs) + 1, dtype=np.int64)
+        np.cumsum(size, out=row_off[1:])
+        pick = np.repeat(start[node] - row_off[:-1], size) + np.arange(row_off[-1])
+        return row_off.astype(np.uint64), dst[pick].astype(np.uint32), sim[pick].astype(np.uint32)
+
     @staticmethod
     def merge_profile(merges, nodes=None):
         """What a caller slides the cut by: per distinct height of a ``cluster_tree`` result, highest first,
         ``{permille, merges, n_clusters}`` -- the merges at or above it and the clusters a cut there leaves among
-        ``nodes`` references (default: the references the merges name, so singletons are left out)."""
+        ``nodes`` references (default: the references the merges name, so singletons are left out).  (It counts
+        records: for ``cluster_edges`` records, which are no forest, ``merges`` is the edges at or above each height
+        and ``n_clusters`` means nothing.)"""
         merges = np.asarray(merges, dtype=np.uint32).reshape(-1, 3)
         if nodes is None:
             nodes = len(np.unique(merges[:, :2]))

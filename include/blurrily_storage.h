@@ -696,6 +696,43 @@ int blurrily_storage_cluster_tree_within(trigram_map haystack, const uint32_t* r
                                          blurrily_cluster_merge_t* merges, uint32_t* n_merges,
                                          uint32_t* n_clusters, uint64_t* n_edges);
 
+/* Cluster edges: the edges of blurrily_storage_cluster's graph themselves, each pair once, with its similarity -- what
+ * feeds a second-stage matcher, a review queue or a clustering of the caller's own, and what every other cluster result
+ * can be checked against.  Nodes, T, R, m, the edge test
+ * 1000 * m >= min_permille * (T_a + T_b - m), repeats in the list, a shuffled list, absent references, unlisted
+ * references (never an end, never a bridge), deletes, pending puts, a reference put again and "devices" > 1: exactly as
+ * for blurrily_storage_cluster.  blurrily_storage_cluster_edges_within is the same over
+ * blurrily_storage_cluster_within's graph: blocks[i] is an opaque 32-bit key for references[i], and an edge needs both
+ * ends under one key ("scope_strategy" chooses the kernel per block as it does there).
+ *   Records: one {a, b, permille} per edge, a < b as references, permille = floor(1000 * m / (T_a + T_b - m)) in 64-bit
+ *            integers: blurrily_storage_cluster_tree's height, so permille >= min_permille always.
+ *   Order:   blurrily_storage_cluster_tree's total order -- permille descending, a ascending, b ascending.  Each edge
+ *            appears once, so the records are distinct under it.  blurrily_storage_cluster_tree's merges at the same
+ *            floor are a subsequence of them.
+ *   Count:   *n_edges (required) is the graph's edge count, byte for byte the n_edges of blurrily_storage_cluster
+ *            (blurrily_storage_cluster_within) at that floor, on success, on ERANGE and on EOVERFLOW.
+ * The capacity protocol is blurrily_storage_find_batch_above's: edges == NULL counts only (capacity is ignored, nothing
+ * is sorted or emitted); otherwise edges has room for `capacity` records, and capacity < *n_edges is ERANGE with edges
+ * untouched -- call again with the room *n_edges names.  Option "cluster_edges_max" (default 2^28 records, 1 .. 2^31)
+ * bounds the device scratch of one call, 28 bytes a record (7 GiB at the default): the call keeps room for
+ * min(capacity, cluster_edges_max) records on the device, and a count that fits capacity but not that room is EOVERFLOW
+ * with edges untouched.  Then raise the floor, cut the list into blocks (blurrily_storage_cluster_edges_within), split
+ * the list, or raise the option if the device has the memory.  The output depends on the map's contents, the list as a
+ * set (with its keys) and min_permille only; two runs give identical bytes.  n == 0: success, *n_edges = 0.
+ * 0, or -1 with errno: EINVAL before anything needs a GPU and with nothing written (haystack NULL, min_permille > 1000,
+ * references NULL with n > 0, n_edges NULL, n above BLURRILY_CLUSTER_TREE_MAX -- the device orders edges by one 64-bit
+ * word that holds both ends in 27 bits each -- and for the blocked form blocks NULL with n > 0 or a reference listed
+ * more than once with different keys); ENODEV without a usable GPU; EIO for a device error word.  The records are
+ * written only on success.
+ * Not built: the edges with a new end only (an extend form), scopes, _device variants, protocol verbs. */
+int blurrily_storage_cluster_edges(trigram_map haystack, const uint32_t* references, size_t n,
+                                   uint32_t min_permille, blurrily_cluster_merge_t* edges,
+                                   uint64_t capacity, uint64_t* n_edges);
+int blurrily_storage_cluster_edges_within(trigram_map haystack, const uint32_t* references,
+                                          const uint32_t* blocks, size_t n, uint32_t min_permille,
+                                          blurrily_cluster_merge_t* edges, uint64_t capacity,
+                                          uint64_t* n_edges);
+
 /* Tokeniser (ext/blurrily/tokeniser.h:34, tokeniser.c:59-119): `output` needs
  * strlen(input)+1 slots; returns the number of distinct codes, ascending. */
 int blurrily_tokeniser_parse_string(const char* input, uint16_t* output);
