@@ -13,6 +13,7 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "cluster_plan.h"
 #include "device_index.h"
 #include "segsort.h"
 
@@ -198,13 +199,7 @@ int launch_cluster_extend_sweep(const ClusterExtendSweepArgs& a, hipStream_t str
 // The direct kernel reads no image: a tile is up to kClusterWithinTile consecutive places of `order` (the numbers
 // sorted by (key, number)) inside one block, and its workgroup scores the tile's needles against the block's members
 // in front of the tile's last place, from the extraction's codes alone.  An edge is found from its end at the higher
-// place only.
-constexpr uint32_t kClusterWithinTile = 16;
-struct ClusterWithinTile {
-  uint32_t begin;                // the block's first place in `order`
-  uint32_t first;                // the tile's first place
-  uint32_t count;                // its places: 1 .. kClusterWithinTile, all of one block
-};
+// place only.  (ClusterWithinTile and kClusterWithinTile: cluster_plan.h.)
 struct ClusterWithinArgs {
   const ClusterWithinTile* tiles;   // [n_tiles]
   const uint32_t* order;         // [n_order] numbers, block after block, ascending inside a block
@@ -251,10 +246,7 @@ struct ClusterTreeSweepArgs {
 };
 int launch_cluster_tree_sweep(const ClusterTreeSweepArgs& a, hipStream_t stream);
 
-// One chosen edge, as the caller gets it (blurrily_cluster_merge_t of include/blurrily_storage.h).
-struct ClusterTreeMerge { uint32_t a, b, permille; };
-
-// After a round's sweeps.  Merge: number i with best[i] != 0 unites its edge's ends in parent[], and the thread that
+// After a round's sweeps (ClusterTreeMerge, one chosen edge as the caller gets it: cluster_plan.h).  Merge: number i with best[i] != 0 unites its edge's ends in parent[], and the thread that
 // made the hook appends {refs[lo], refs[hi], h} to merges[] at (*n_merges)++; a root with best[i] == 0 is closed;
 // best[i] = 0 again.  Flatten, across a launch boundary: comp[i] = root of i.
 struct ClusterTreeRoundArgs {

@@ -2,11 +2,8 @@
 // dendrogram of blurrily_storage_cluster_cores' cores at every floor from one call.  The call sequence is ClusterCall's
 // (cluster_host.h) with one forest.  First the core heights, by histogram refinement: a sweep over every image and
 // chunk and a settle per step, max(1, ceil(log_kCoreBuckets(1001 - min_permille))) steps, none with min_degree == 0.
-// Then cluster_tree.hip's rounds with cluster_core_tree_kernels.hip's sweep in place of the tree's: the merge, the
-// flatten, the four bytes read back per round and the bound on the rounds are that file's.
-#include <algorithm>
-#include <vector>
-
+// Then the cluster tree's rounds (TreeRounds, cluster_host.h) with cluster_core_tree_kernels.hip's sweep for a round's
+// offer in place of the tree's.
 #include "map_internal.h"
 #include "cluster.h"
 #include "cluster_host.h"
@@ -16,8 +13,6 @@ using namespace blurrily::detail;
 
 static_assert(kNoCore == BLURRILY_NO_CORE, "the header's word for no core height is the kernels'");
 static_assert(sizeof(ClusterTreeMerge) == sizeof(blurrily_cluster_merge_t), "the kernels' record is the header's");
-
-constexpr uint32_t kCoreTreeMaxRounds = 40;                   // (cluster_tree.hip's kTreeMaxRounds, and its argument)
 
 extern "C" int blurrily_storage_cluster_core_tree(trigram_map m, const uint32_t* references, size_t n,
                                                   uint32_t min_permille, uint32_t min_degree, uint32_t* labels,
@@ -64,53 +59,31 @@ extern "C" int blurrily_storage_cluster_core_tree(trigram_map m, const uint32_t*
     }
   }
 
-  // the forest: cluster_tree.hip's rounds
-  ClusterTreeRoundArgs r{};
-  uint32_t* d_counters = nullptr;                             // [0]: the merges so far
-  if (c.more(r.best, nu * 8, true) < 0 || c.more(r.comp, nu * 4) < 0 || c.more(r.closed, nu, true) < 0 ||
-      c.more(r.merges, nu * sizeof(ClusterTreeMerge)) < 0 || c.more(d_counters, 16, true) < 0)
-    return -1;
-  r.parent = c.d_parent; r.refs = c.d_refs; r.n_nodes = uint32_t(nu); r.n_merges = d_counters; r.totals = &d_totals->t;
-  if (launch_cluster_tree_flatten(r, stream) < 0) return -1;  // (every number its own component)
-
-  uint32_t found = 0;
-  bool done = false;
-  for (uint32_t round = 1; round <= kCoreTreeMaxRounds && !done; ++round) {
-    auto launch = [&](const ClusterSweepArgs& a) {
+  // the forest: the cluster tree's rounds over the edges between two numbers with a core height
+  TreeRounds t;
+  if (t.begin(c, &d_totals->t) < 0) return -1;
+  const ClusterTreeRoundArgs& r = t.r;
+  const auto offer = [&](uint32_t round) {
+    return c.sweep(nu, min_permille, nullptr, [&](const ClusterSweepArgs& a) {
       return launch_cluster_core_tree_sweep({ClusterTreeSweepArgs{a, r.comp, r.closed, r.best, round}, d_core,
                                              min_degree == 0u, d_totals}, stream);
-    };
-    if (c.sweep(nu, min_permille, nullptr, launch) < 0) return -1;
-    if (launch_cluster_tree_merge(r, stream) < 0 || launch_cluster_tree_flatten(r, stream) < 0) return -1;
-    uint32_t now = 0;
-    BLURRILY_HIP_TRY(hipMemcpyAsync(&now, d_counters, 4, hipMemcpyDeviceToHost, stream));
-    BLURRILY_HIP_TRY(hipStreamSynchronize(stream));
-    done = now == found;
-    found = now;
-  }
-  if (!done || found >= nu) { errno = EIO; return -1; }       // (the round bound ran out; a forest has fewer edges than nodes)
+    });
+  };
+  if (t.run(offer) < 0) return -1;
 
   // a number without a core height was hooked by nothing: its label is its own reference
   if (launch_cluster_label(c.label_args(), stream) < 0) return -1;
   ClusterCoresTotals totals{};
-  if (c.read_totals(&totals) < 0) return -1;
-  std::vector<ClusterTreeMerge> got(found);
   std::vector<uint32_t> core(nu);
-  if (found)
-    BLURRILY_HIP_TRY(hipMemcpyAsync(got.data(), r.merges, found * sizeof(ClusterTreeMerge), hipMemcpyDeviceToHost, stream));
+  if (c.read_totals(&totals) < 0 || t.read_records() < 0) return -1;
   BLURRILY_HIP_TRY(hipMemcpyAsync(core.data(), d_core, nu * 4, hipMemcpyDeviceToHost, stream));
   BLURRILY_HIP_TRY(hipMemcpyAsync(labels, c.d_labels, n * 4, hipMemcpyDeviceToHost, stream));
   if (c.wait(&totals.t) < 0) return -1;
-  // the order of the records: height descending, then the lower reference, then the higher
-  std::sort(got.begin(), got.end(), [](const ClusterTreeMerge& x, const ClusterTreeMerge& y) {
-    if (x.permille != y.permille) return x.permille > y.permille;
-    return x.a != y.a ? x.a < y.a : x.b < y.b;
-  });
-  for (uint32_t i = 0; i < found; ++i) merges[i] = {got[i].a, got[i].b, got[i].permille};
+  t.deliver(merges);
   for (size_t i = 0; i < n; ++i) core_permille[i] = core[c.inv.empty() ? i : c.inv[i]];
   const size_t cores = size_t(std::count_if(core.begin(), core.end(), [](uint32_t h) { return h != kNoCore; }));
-  if (n_merges) *n_merges = found;
-  if (n_clusters) *n_clusters = uint32_t(cores - found);      // (a forest: its components are its nodes minus its edges)
+  if (n_merges) *n_merges = t.found;
+  if (n_clusters) *n_clusters = uint32_t(cores - t.found);    // (a forest: its components are its nodes minus its edges)
   if (n_edges) *n_edges = totals.t.edges;
   if (n_core_edges) *n_core_edges = totals.core_edges;
   return 0;

@@ -2,11 +2,11 @@
 // blurrily_storage.h): the edges of blurrily_storage_cluster's graph, or of
 // blurrily_storage_cluster_within's, each once, as {a, b, permille} records in the cluster tree's order.  The call
 // sequence is ClusterCall's (cluster_host.h) -- for the blocked form over a numbering made here, before a GPU is asked
-// for, and with cluster_within's plan -- with one forest, which nothing reads (the node tables are filled per forest),
-// and with ClusterTotals::edges as the call's cursor: every sweep launch of the call appends through it
-// (cluster_edges_kernels.hip), and what it holds after the last one is the edge count, in every mode.  An emitting call
-// then sorts the keys (segsort.h, one segment) and turns them into records; a count-only call, or one whose count does
-// not fit, launches neither.
+// for, and with cluster_within's plan (ClusterCall::begin_blocked) -- with one forest, which nothing reads (the node
+// tables are filled per forest), and with ClusterTotals::edges as the call's cursor: every sweep launch of the call
+// appends through it (cluster_edges_kernels.hip), and what it holds after the last one is the edge count, in every
+// mode.  An emitting call then sorts the keys (segsort.h, one segment) and turns them into records; a count-only call,
+// or one whose count does not fit, launches neither.
 #include "map_internal.h"
 #include "cluster.h"
 #include "cluster_host.h"
@@ -31,15 +31,11 @@ int cluster_edges_run(trigram_map m, const uint32_t* references, size_t n, bool 
   NameScope names(&m->last_kernels);
   m->last_kernels.clear();
 
-  ClusterWithinPlan plan;
-  if (blocked && plan_within_blocks(key_of, m->scope_strategy, plan) < 0) return -1;
-
   ClusterCall c(m, stream);
-  if ((blocked ? c.begin(std::move(uniq), std::move(inv), n, 1, sizeof(ClusterTotals))
+  if ((blocked ? c.begin_blocked(std::move(uniq), std::move(inv), key_of, n)
                : c.begin(references, n, 1, sizeof(ClusterTotals))) < 0)
     return -1;
   ClusterTotals* d_totals = static_cast<ClusterTotals*>(c.d_totals);
-  if (blocked && c.upload(plan, key_of) < 0) return -1;
 
   // the room: what the caller can take, as far as the option allows (count only: none)
   ClusterEdgesOut out{&d_totals->edges, nullptr, edges ? std::min<uint64_t>(capacity, m->cluster_edges_max) : 0u};
@@ -52,13 +48,11 @@ int cluster_edges_run(trigram_map m, const uint32_t* references, size_t n, bool 
       return -1;
   } else {
     // the large blocks over the images, the small ones from the extraction's codes, through the one cursor
-    if (c.sweep(plan.swept.size(), min_permille, d_totals, [&](const ClusterSweepArgs& a) {
-          return launch_cluster_edges_sweep({a, plan.d_swept, plan.d_block_of, out}, stream);
+    if (c.sweep(c.plan.swept.size(), min_permille, d_totals, [&](const ClusterSweepArgs& a) {
+          return launch_cluster_edges_sweep({a, c.d_swept, c.d_block_of, out}, stream);
         }) < 0)
       return -1;
-    const ClusterWithinArgs wa{plan.d_tiles, plan.d_order, uint32_t(plan.tiles.size()), uint32_t(c.nu), c.x.needles.codes,
-                               c.x.needles.qoff, c.x.needles.ntri, uint32_t(c.nu), min_permille, nullptr, nullptr};
-    if (launch_cluster_edges_within({wa, out}, stream) < 0) return -1;
+    if (launch_cluster_edges_within({c.within_args(min_permille, nullptr, nullptr), out}, stream) < 0) return -1;
   }
   ClusterTotals totals{};
   if (c.read_totals(&totals) < 0 || c.wait(&totals) < 0) return -1;

@@ -1,9 +1,9 @@
 // cluster_extend.hip -- blurrily_storage_cluster_extend (include/blurrily_storage.h): the clusters
 // of old and new references together, from the labels the caller holds for the old ones.  The call sequence is
 // ClusterCall's (cluster_host.h) over the concatenation old ++ new, with two things more on the device -- a bit per
-// number for "new" and the list of the new numbers -- a seed launch in front of the sweeps, and the sweeps over the
-// new numbers alone.  The seeds and the sweep are cluster_extend_kernels.hip's, the node tables and the labels
-// cluster_kernels.hip's kernels as they are.
+// number for "new" and the list of the new numbers (mark_new, cluster_plan.h) -- a seed launch in front of the sweeps,
+// and the sweeps over the new numbers alone.  The seeds and the sweep are cluster_extend_kernels.hip's, the node tables
+// and the labels cluster_kernels.hip's kernels as they are.
 #include "map_internal.h"
 #include "cluster.h"
 #include "cluster_host.h"
@@ -39,16 +39,8 @@ extern "C" int blurrily_storage_cluster_extend(trigram_map m, const uint32_t* ol
     if (c.begin(all.data(), n, 1, sizeof(ClusterTotals)) < 0) return -1;
   }
   const size_t nu = c.nu;
-  const std::vector<uint32_t>& inv = c.inv;
-  std::vector<uint32_t> is_new((nu + 31) / 32, 0u), new_nodes(inv.empty() ? n_new : 0);
-  if (inv.empty()) {
-    for (size_t j = 0; j < n_new; ++j) new_nodes[j] = uint32_t(n_old + j);
-    for (uint32_t u : new_nodes) is_new[u >> 5] |= 1u << (u & 31u);
-  } else {
-    for (size_t j = 0; j < n_new; ++j) is_new[inv[n_old + j] >> 5] |= 1u << (inv[n_old + j] & 31u);
-    for (size_t u = 0; u < nu; ++u)
-      if ((is_new[u >> 5] >> (u & 31u)) & 1u) new_nodes.push_back(uint32_t(u));
-  }
+  std::vector<uint32_t> is_new, new_nodes;
+  mark_new(c.inv, n_old, n_new, nu, is_new, new_nodes);
   const size_t nn = new_nodes.size();
 
   ClusterTotals* d_totals = static_cast<ClusterTotals*>(c.d_totals);

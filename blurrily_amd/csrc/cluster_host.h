@@ -1,97 +1,23 @@
 // cluster_host.h -- the host-side call sequence the clustering entries share (cluster.hip, cluster_levels.hip,
 // cluster_centres.hip, cluster_cores.hip, cluster_extend.hip, cluster_within.hip, cluster_tree.hip,
-// cluster_tree_extend.hip, cluster_core_tree.hip, cluster_tree_within.hip, cluster_edges.hip): the node numbering,
-// the block plan of the two within entries, the cluster tree's round bound and record order, and ClusterCall, which
-// owns a call's device scratch, runs what every entry does in front of its sweeps, fills the sweeps' common arguments
-// per image and chunk, and reads the totals back.  The device code is each entry's own.
+// cluster_tree_extend.hip, cluster_core_tree.hip, cluster_tree_within.hip, cluster_edges.hip; DESIGN.md sections 25
+// and 40): ClusterCall, which owns a call's device scratch, runs what every entry does in front of its sweeps -- for the
+// three blocked entries the block plan too --, fills the sweeps' common arguments per image and chunk, and reads the
+// totals back; and TreeRounds, the Boruvka rounds of the four tree entries around the entry's own offer of edges.  The
+// arithmetic that needs no GPU (the numbering, the plan, the new numbers, the record order) is cluster_plan.h's.  The
+// device code is each entry's own.
 #pragma once
 #include <algorithm>
 #include <vector>
 
 #include "cluster.h"
+#include "cluster_plan.h"
 #include "map_internal.h"
 
 namespace blurrily {
 namespace detail __attribute__((visibility("hidden"))) {
 
 constexpr size_t kClusterChunkNeedles = size_t(1) << 20;   // needles per sweep launch (nothing else bounds a chunk)
-
-// The caller's references ascending without repeats (the node numbering), and each element's number.  A list that is
-// strictly ascending already is its own numbering: inv stays empty.
-inline void number_nodes(const uint32_t* references, size_t n, std::vector<uint32_t>& uniq, std::vector<uint32_t>& inv) {
-  bool ascending = true;
-  for (size_t i = 1; i < n && ascending; ++i) ascending = references[i - 1] < references[i];
-  if (ascending) { uniq.assign(references, references + n); return; }
-  std::vector<uint64_t> keyed(n);
-  for (size_t i = 0; i < n; ++i) keyed[i] = (uint64_t(references[i]) << 32) | i;
-  std::sort(keyed.begin(), keyed.end());
-  inv.resize(n);
-  for (size_t i = 0; i < n; ++i) {
-    const uint32_t ref = uint32_t(keyed[i] >> 32);
-    if (uniq.empty() || uniq.back() != ref) uniq.push_back(ref);
-    inv[uint32_t(keyed[i])] = uint32_t(uniq.size() - 1);
-  }
-}
-
-// The same numbering for references that carry a key each (blurrily_storage_cluster_within's blocks): key_of[u] is number
-// u's.  False, with nothing to rely on in the outputs: a reference is listed more than once under different keys.  A
-// strictly ascending list names every reference once, so it cannot be, and is its own numbering as above.
-inline bool number_nodes_keyed(const uint32_t* references, const uint32_t* keys, size_t n, std::vector<uint32_t>& uniq,
-                               std::vector<uint32_t>& inv, std::vector<uint32_t>& key_of) {
-  bool ascending = true;
-  for (size_t i = 1; i < n && ascending; ++i) ascending = references[i - 1] < references[i];
-  if (ascending) { uniq.assign(references, references + n); key_of.assign(keys, keys + n); return true; }
-  std::vector<uint64_t> keyed(n);
-  for (size_t i = 0; i < n; ++i) keyed[i] = (uint64_t(references[i]) << 32) | i;
-  std::sort(keyed.begin(), keyed.end());
-  inv.resize(n);
-  for (size_t i = 0; i < n; ++i) {
-    const uint32_t ref = uint32_t(keyed[i] >> 32), key = keys[uint32_t(keyed[i])];
-    if (uniq.empty() || uniq.back() != ref) { uniq.push_back(ref); key_of.push_back(key); }
-    else if (key_of.back() != key) return false;
-    inv[uint32_t(keyed[i])] = uint32_t(uniq.size() - 1);
-  }
-  return true;
-}
-
-// The listed members of a block up to which "scope_strategy" 0 scores the block directly.  Direct work grows with the
-// square of a block, the sweep's with the map: on configs[2]'s haystack at 700 per mille, one block of 10^5 consecutive
-// references takes the direct kernel 16 ms against the sweep's 170 ms, one of 10^6 1.96 s against 1.72 s
-// (profiles/cluster_within_geonames.json).  This is the largest size measured at which direct was no slower.
-// "scope_strategy" 1 sweeps every block, 2 scores every block directly.
-// The tree within blocks takes the same cap: its rounds multiply both kernels' work alike, so there is no reason to
-// expect another crossover -- but nobody has measured the crossover for the tree, only one block of 10^5 under either
-// kernel: 31 ms direct against 275 ms swept (profiles/cluster_tree_within_geonames.json).
-constexpr size_t kClusterWithinDirectMax = 100000;
-
-// The block plan of blurrily_storage_cluster_within and blurrily_storage_cluster_tree_within, from
-// each number's key: `order`, the numbers block after block, ascending inside a block; every block given to one of the
-// two kernels -- the direct kernel's tiles of up to kClusterWithinTile places for a block of at most
-// kClusterWithinDirectMax listed members ("scope_strategy" 2: for any block; a block of one has no pair to score and
-// gets no tile), the sweep's needle list for a larger one ("scope_strategy" 1: for every block); the tiles that pass
-// over the most members first, so that the longest workgroups do not start last (equal ones in the plan's order).
-struct ClusterWithinPlan {
-  std::vector<uint32_t>          order;
-  std::vector<ClusterWithinTile> tiles;
-  std::vector<uint32_t>          swept;
-  // On the device, after upload(): null where the plan has nothing for the kernel that would read it.
-  ClusterWithinTile* d_tiles = nullptr;
-  uint32_t *d_order = nullptr, *d_swept = nullptr, *d_block_of = nullptr;
-};
-// -1 with EINVAL: more tiles than a launch takes.  Needs no GPU.
-int plan_within_blocks(const std::vector<uint32_t>& key_of, uint32_t scope_strategy, ClusterWithinPlan& plan);
-
-// The cluster tree's rounds.  Every round that merges at least halves the components that still have an edge leaving
-// them: 28 rounds serve 2^27 nodes, and one more finds nothing.
-constexpr uint32_t kTreeMaxRounds = 40;
-
-// The order of a tree's records: height descending, then the lower reference, then the higher.
-inline void sort_tree_records(std::vector<ClusterTreeMerge>& records) {
-  std::sort(records.begin(), records.end(), [](const ClusterTreeMerge& x, const ClusterTreeMerge& y) {
-    if (x.permille != y.permille) return x.permille > y.permille;
-    return x.a != y.a ? x.a < y.a : x.b < y.b;
-  });
-}
 
 // One call of a clustering entry, from the entry's checks to its return.
 struct ClusterCall {
@@ -118,9 +44,14 @@ struct ClusterCall {
   int begin(std::vector<uint32_t>&& numbering, std::vector<uint32_t>&& element_number, size_t n, uint32_t forests,
             size_t totals_bytes);
 
-  // A block plan onto the device, after begin(): the tiles with `order` if there are tiles, the swept numbers with
-  // every number's key (key_of, nu of them) if a block is swept.
-  int upload(ClusterWithinPlan& plan, const std::vector<uint32_t>& key_of);
+  // The beginning of a blocked entry, one forest and one ClusterTotals: the block plan from number_nodes_keyed's
+  // key_of under the map's "scope_strategy", begin() with that numbering, and the plan onto the device -- the tiles
+  // with `order` if there are tiles, the swept numbers with every number's key if a block is swept.
+  int begin_blocked(std::vector<uint32_t>&& numbering, std::vector<uint32_t>&& element_number,
+                    const std::vector<uint32_t>& key_of, size_t n);
+  // ... and the direct kernel's arguments over the plan's tiles (an entry whose kernel unites nothing or counts
+  // elsewhere passes null).
+  ClusterWithinArgs within_args(uint32_t min_permille, uint32_t* parent, ClusterTotals* totals) const;
 
   // `needles` needles (of the numbering, or of an entry's own list) over every image, in chunks: the sweep arguments
   // all entries share, handed to launch(const ClusterSweepArgs&), which adds the entry's own and launches.
@@ -161,6 +92,9 @@ struct ClusterCall {
   uint32_t*   d_parent = nullptr;                            // forest k: words [k * nu, k * nu + nu)
   uint32_t*   d_labels = nullptr;                            // forest k: words [k * n, k * n + n), as the caller's
   void*       d_totals = nullptr;                            // totals_bytes, as the entry's kernels type them
+  ClusterWithinPlan plan;                                    // after begin_blocked(); on the device, null where the
+  ClusterWithinTile* d_tiles = nullptr;                      // plan has nothing for the kernel that would read it
+  uint32_t *d_order = nullptr, *d_swept = nullptr, *d_block_of = nullptr;
 
  private:
   int alloc(void** p, size_t bytes, bool zeroed);
@@ -171,6 +105,43 @@ struct ClusterCall {
   SimilarTable  tab[2];
   std::vector<uint32_t> uniq;                                // the numbering's references (the upload's source: kept to the end)
   std::vector<void*> buffers;
+};
+
+// The cluster tree's rounds for the four tree entries: the rounds' buffers, and per round the
+// entry's offer to best[], the merge, the flatten and four bytes read back, the merges so far.  A round that adds none
+// was the last.
+struct TreeRounds {
+  // The buffers on top of c's (after its begin), the merge's and the flatten's arguments -- an error word goes to
+  // *d_totals -- and the first flatten: every number its own component.
+  int begin(ClusterCall& c, ClusterTotals* d_totals);
+
+  // offer(round), from 1, enqueues whatever raises best[] this round from r.comp and r.closed (< 0: it failed).
+  // EIO: kTreeMaxRounds ran out, or there are not fewer records than numbers, which no forest has.
+  template <class Offer>
+  int run(Offer&& offer) {
+    bool done = false;
+    for (uint32_t round = 1; round <= kTreeMaxRounds && !done; ++round) {
+      uint32_t now = 0;
+      if (offer(round) < 0 || merge_and_count(now) < 0) return -1;
+      done = now == found;
+      found = now;
+    }
+    if (!done || found >= r.n_nodes) { errno = EIO; return -1; }
+    return 0;
+  }
+
+  // The ending: the `found` records on their way to the host (none: nothing is enqueued), and, after the entry's wait
+  // for the stream, into merges[] in sort_tree_records' order.
+  int read_records();
+  void deliver(blurrily_cluster_merge_t* merges);
+
+  ClusterTreeRoundArgs r{};
+  uint32_t found = 0;                                        // the merges so far
+
+ private:
+  int merge_and_count(uint32_t& now);
+  hipStream_t stream = nullptr;
+  std::vector<ClusterTreeMerge> got;
 };
 
 }  // namespace detail

@@ -1,62 +1,33 @@
-// cluster_host.hip -- ClusterCall (cluster_host.h): what the clustering entries do alike, once.
+// cluster_host.hip -- ClusterCall and TreeRounds (cluster_host.h; DESIGN.md sections 25 and 40): what the clustering
+// entries do alike, once.
 #include "cluster_host.h"
 
 namespace blurrily {
 namespace detail {
 
-int plan_within_blocks(const std::vector<uint32_t>& key_of, uint32_t scope_strategy, ClusterWithinPlan& plan) {
-  // the numbers block after block, ascending inside a block (keys that ascend with the numbers already are)
-  const size_t nu = key_of.size();
-  std::vector<uint32_t>& order = plan.order;
-  order.resize(nu);
-  if (std::is_sorted(key_of.begin(), key_of.end())) {
-    for (size_t u = 0; u < nu; ++u) order[u] = uint32_t(u);
-  } else {
-    std::vector<uint64_t> keyed(nu);
-    for (size_t u = 0; u < nu; ++u) keyed[u] = (uint64_t(key_of[u]) << 32) | u;
-    std::sort(keyed.begin(), keyed.end());
-    for (size_t u = 0; u < nu; ++u) order[u] = uint32_t(keyed[u]);
+int ClusterCall::begin_blocked(std::vector<uint32_t>&& numbering, std::vector<uint32_t>&& element_number,
+                               const std::vector<uint32_t>& key_of, size_t n_listed) {
+  if (plan_within_blocks(key_of, m->scope_strategy, plan) < 0 ||
+      begin(std::move(numbering), std::move(element_number), n_listed, 1, sizeof(ClusterTotals)) < 0)
+    return -1;
+  const std::vector<ClusterWithinTile>& tiles = plan.tiles;
+  if (more(d_tiles, tiles.size() * sizeof(ClusterWithinTile)) < 0 || more(d_swept, plan.swept.size() * 4) < 0 ||
+      (!tiles.empty() && more(d_order, nu * 4) < 0) || (!plan.swept.empty() && more(d_block_of, nu * 4) < 0))
+    return -1;
+  if (d_tiles) {
+    BLURRILY_HIP_TRY(hipMemcpyAsync(d_tiles, tiles.data(), tiles.size() * sizeof(ClusterWithinTile), hipMemcpyHostToDevice, stream));
+    BLURRILY_HIP_TRY(hipMemcpyAsync(d_order, plan.order.data(), nu * 4, hipMemcpyHostToDevice, stream));
   }
-  std::vector<ClusterWithinTile>& tiles = plan.tiles;
-  for (size_t b = 0; b < nu;) {
-    size_t e = b + 1;
-    while (e < nu && key_of[order[e]] == key_of[order[b]]) ++e;
-    const bool direct = scope_strategy == 2 || (scope_strategy == 0 && e - b <= kClusterWithinDirectMax);
-    if (!direct) {
-      plan.swept.insert(plan.swept.end(), order.begin() + b, order.begin() + e);
-    } else if (e - b > 1) {                                   // (a block of one has no pair to score)
-      for (size_t f = b; f < e; f += kClusterWithinTile)
-        tiles.push_back({uint32_t(b), uint32_t(f), uint32_t(std::min<size_t>(kClusterWithinTile, e - f))});
-    }
-    b = e;
+  if (d_swept) {
+    BLURRILY_HIP_TRY(hipMemcpyAsync(d_swept, plan.swept.data(), plan.swept.size() * 4, hipMemcpyHostToDevice, stream));
+    BLURRILY_HIP_TRY(hipMemcpyAsync(d_block_of, key_of.data(), nu * 4, hipMemcpyHostToDevice, stream));
   }
-  // the tiles that pass over the most members first: the longest workgroups do not start last
-  // (equal ones in the plan's order)
-  if (tiles.size() > 0x7FFFFFFFull) { errno = EINVAL; return -1; }
-  std::vector<uint64_t> by_scan(tiles.size());
-  for (size_t t = 0; t < tiles.size(); ++t)
-    by_scan[t] = (uint64_t(~(tiles[t].first + tiles[t].count - tiles[t].begin)) << 32) | t;
-  std::sort(by_scan.begin(), by_scan.end());
-  std::vector<ClusterWithinTile> sorted(tiles.size());
-  for (size_t t = 0; t < tiles.size(); ++t) sorted[t] = tiles[uint32_t(by_scan[t])];
-  tiles.swap(sorted);
   return 0;
 }
 
-int ClusterCall::upload(ClusterWithinPlan& plan, const std::vector<uint32_t>& key_of) {
-  const std::vector<ClusterWithinTile>& tiles = plan.tiles;
-  if (more(plan.d_tiles, tiles.size() * sizeof(ClusterWithinTile)) < 0 || more(plan.d_swept, plan.swept.size() * 4) < 0 ||
-      (!tiles.empty() && more(plan.d_order, nu * 4) < 0) || (!plan.swept.empty() && more(plan.d_block_of, nu * 4) < 0))
-    return -1;
-  if (plan.d_tiles) {
-    BLURRILY_HIP_TRY(hipMemcpyAsync(plan.d_tiles, tiles.data(), tiles.size() * sizeof(ClusterWithinTile), hipMemcpyHostToDevice, stream));
-    BLURRILY_HIP_TRY(hipMemcpyAsync(plan.d_order, plan.order.data(), nu * 4, hipMemcpyHostToDevice, stream));
-  }
-  if (plan.d_swept) {
-    BLURRILY_HIP_TRY(hipMemcpyAsync(plan.d_swept, plan.swept.data(), plan.swept.size() * 4, hipMemcpyHostToDevice, stream));
-    BLURRILY_HIP_TRY(hipMemcpyAsync(plan.d_block_of, key_of.data(), nu * 4, hipMemcpyHostToDevice, stream));
-  }
-  return 0;
+ClusterWithinArgs ClusterCall::within_args(uint32_t min_permille, uint32_t* parent, ClusterTotals* totals) const {
+  return {d_tiles, d_order, uint32_t(plan.tiles.size()), uint32_t(nu), x.needles.codes, x.needles.qoff, x.needles.ntri,
+          uint32_t(nu), min_permille, parent, totals};
 }
 
 ClusterCall::~ClusterCall() {
@@ -124,6 +95,35 @@ int ClusterCall::wait(const ClusterTotals* t) {
   for (uint32_t k = 0; k < forests; ++k)
     if (t[k].error) { errno = EIO; return -1; }
   return 0;
+}
+
+int TreeRounds::begin(ClusterCall& c, ClusterTotals* d_totals) {
+  const size_t nu = c.nu;
+  stream = c.stream;
+  if (c.more(r.best, nu * 8, true) < 0 || c.more(r.comp, nu * 4) < 0 || c.more(r.closed, nu, true) < 0 ||
+      c.more(r.merges, nu * sizeof(ClusterTreeMerge)) < 0 || c.more(r.n_merges, 16, true) < 0)
+    return -1;
+  r.parent = c.d_parent; r.refs = c.d_refs; r.n_nodes = uint32_t(nu); r.totals = d_totals;
+  return launch_cluster_tree_flatten(r, stream);
+}
+
+int TreeRounds::merge_and_count(uint32_t& now) {
+  if (launch_cluster_tree_merge(r, stream) < 0 || launch_cluster_tree_flatten(r, stream) < 0) return -1;
+  BLURRILY_HIP_TRY(hipMemcpyAsync(&now, r.n_merges, 4, hipMemcpyDeviceToHost, stream));
+  BLURRILY_HIP_TRY(hipStreamSynchronize(stream));
+  return 0;
+}
+
+int TreeRounds::read_records() {
+  got = std::vector<ClusterTreeMerge>(found);
+  if (found)
+    BLURRILY_HIP_TRY(hipMemcpyAsync(got.data(), r.merges, found * sizeof(ClusterTreeMerge), hipMemcpyDeviceToHost, stream));
+  return 0;
+}
+
+void TreeRounds::deliver(blurrily_cluster_merge_t* merges) {
+  sort_tree_records(got);
+  for (uint32_t i = 0; i < found; ++i) merges[i] = {got[i].a, got[i].b, got[i].permille};
 }
 
 }  // namespace detail

@@ -1,11 +1,9 @@
 // cluster_tree.hip -- blurrily_storage_cluster_tree (include/blurrily_storage.h): the maximum
 // spanning forest of blurrily_storage_cluster's edges with heights in whole per mille -- the single-linkage dendrogram --
-// by Boruvka rounds on the device.  The call sequence is ClusterCall's (cluster_host.h) with one forest; a round is one
-// sweep over every image and chunk (cluster_tree_kernels.hip's, which chooses the best edge leaving each component),
-// the merge, the flatten and four bytes read back: the merges so far.  A round that adds none was the last.
-#include <algorithm>
-#include <vector>
-
+// by Boruvka rounds on the device.  The call sequence is ClusterCall's (cluster_host.h) with one forest, the rounds are
+// TreeRounds' (the same header: the merge, the flatten and four bytes read back per round, the merges so far; a round
+// that adds none was the last), and what a round offers is one sweep over every image and chunk
+// (cluster_tree_kernels.hip's, which chooses the best edge leaving each component).
 #include "map_internal.h"
 #include "cluster.h"
 #include "cluster_host.h"
@@ -37,42 +35,23 @@ extern "C" int blurrily_storage_cluster_tree(trigram_map m, const uint32_t* refe
   ClusterCall c(m, stream);
   if (c.begin(references, n, 1, sizeof(ClusterTotals)) < 0) return -1;
   ClusterTotals* d_totals = static_cast<ClusterTotals*>(c.d_totals);
-  const size_t nu = c.nu;
-  ClusterTreeRoundArgs r{};
-  uint32_t* d_counters = nullptr;                             // [0]: the merges so far
-  if (c.more(r.best, nu * 8, true) < 0 || c.more(r.comp, nu * 4) < 0 || c.more(r.closed, nu, true) < 0 ||
-      c.more(r.merges, nu * sizeof(ClusterTreeMerge)) < 0 || c.more(d_counters, 16, true) < 0)
-    return -1;
-  r.parent = c.d_parent; r.refs = c.d_refs; r.n_nodes = uint32_t(nu); r.n_merges = d_counters; r.totals = d_totals;
-  if (launch_cluster_tree_flatten(r, stream) < 0) return -1;  // (every number its own component)
-
-  uint32_t found = 0;
-  bool done = false;
-  for (uint32_t round = 1; round <= kTreeMaxRounds && !done; ++round) {
-    auto launch = [&](const ClusterSweepArgs& a) {
+  TreeRounds t;
+  if (t.begin(c, d_totals) < 0) return -1;
+  const ClusterTreeRoundArgs& r = t.r;
+  const auto offer = [&](uint32_t round) {
+    return c.sweep(c.nu, min_permille, d_totals, [&](const ClusterSweepArgs& a) {
       return launch_cluster_tree_sweep(ClusterTreeSweepArgs{a, r.comp, r.closed, r.best, round}, stream);
-    };
-    if (c.sweep(nu, min_permille, d_totals, launch) < 0) return -1;
-    if (launch_cluster_tree_merge(r, stream) < 0 || launch_cluster_tree_flatten(r, stream) < 0) return -1;
-    uint32_t now = 0;
-    BLURRILY_HIP_TRY(hipMemcpyAsync(&now, d_counters, 4, hipMemcpyDeviceToHost, stream));
-    BLURRILY_HIP_TRY(hipStreamSynchronize(stream));
-    done = now == found;
-    found = now;
-  }
-  if (!done || found >= nu) { errno = EIO; return -1; }       // (the round bound ran out; a forest has fewer edges than nodes)
+    });
+  };
+  if (t.run(offer) < 0) return -1;
 
   if (launch_cluster_label(c.label_args(), stream) < 0) return -1;
   ClusterTotals totals{};
-  if (c.read_totals(&totals) < 0) return -1;
-  std::vector<ClusterTreeMerge> got(found);
-  if (found)
-    BLURRILY_HIP_TRY(hipMemcpyAsync(got.data(), r.merges, found * sizeof(ClusterTreeMerge), hipMemcpyDeviceToHost, stream));
+  if (c.read_totals(&totals) < 0 || t.read_records() < 0) return -1;
   BLURRILY_HIP_TRY(hipMemcpyAsync(labels, c.d_labels, n * 4, hipMemcpyDeviceToHost, stream));
   if (c.wait(&totals) < 0) return -1;
-  sort_tree_records(got);
-  for (uint32_t i = 0; i < found; ++i) merges[i] = {got[i].a, got[i].b, got[i].permille};
-  if (n_merges) *n_merges = found;
+  t.deliver(merges);
+  if (n_merges) *n_merges = t.found;
   if (n_clusters) *n_clusters = totals.clusters;
   if (n_edges) *n_edges = totals.edges;
   return 0;

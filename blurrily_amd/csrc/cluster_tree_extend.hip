@@ -1,13 +1,10 @@
 // cluster_tree_extend.hip -- blurrily_storage_cluster_tree_extend (include/blurrily_storage.h): the
 // cluster tree of old and new references together, from the records the caller holds for the old ones.  The call
 // sequence is ClusterCall's (cluster_host.h) over the concatenation old ++ new with one forest; the bit per number for
-// "new" and the list of the new numbers are cluster_extend.hip's, the rounds' buffers cluster_tree.hip's.  The old
-// records are uploaded once and resolved to keys in a launch in front of the rounds; a round is the new nodes' sweeps
-// over every image and chunk, the records' offer, cluster_tree_kernels.hip's merge and flatten as they are, and four
-// bytes read back.  No old reference is ever a needle.
-#include <algorithm>
-#include <vector>
-
+// "new" and the list of the new numbers are mark_new's (cluster_plan.h), as cluster_extend.hip's are, the rounds
+// TreeRounds' (cluster_host.h).  The old records are uploaded once and resolved to keys in a launch in front of the
+// rounds; what a round offers is the new nodes' sweeps over every image and chunk, then the records' offer.  No old
+// reference is ever a needle.
 #include "map_internal.h"
 #include "cluster.h"
 #include "cluster_host.h"
@@ -16,9 +13,6 @@ using namespace blurrily;
 using namespace blurrily::detail;
 
 static_assert(sizeof(ClusterTreeMerge) == sizeof(blurrily_cluster_merge_t), "the kernels' record is the header's");
-
-// (cluster_tree.hip's bound and its reason: every merging round at least halves the components that an edge leaves)
-constexpr uint32_t kTreeExtendMaxRounds = 40;
 
 extern "C" int blurrily_storage_cluster_tree_extend(trigram_map m, const uint32_t* old_refs, size_t n_old,
                                                     const blurrily_cluster_merge_t* old_merges, size_t n_old_merges,
@@ -45,7 +39,7 @@ extern "C" int blurrily_storage_cluster_tree_extend(trigram_map m, const uint32_
   NameScope names(&m->last_kernels);
   m->last_kernels.clear();
 
-  // the beginning over old ++ new, and which numbers are new (cluster_extend.hip's)
+  // the beginning over old ++ new, and which numbers are new
   ClusterCall c(m, stream);
   {
     std::vector<uint32_t> all(n);
@@ -54,16 +48,8 @@ extern "C" int blurrily_storage_cluster_tree_extend(trigram_map m, const uint32_
     if (c.begin(all.data(), n, 1, sizeof(ClusterTotals)) < 0) return -1;
   }
   const size_t nu = c.nu;
-  const std::vector<uint32_t>& inv = c.inv;
-  std::vector<uint32_t> is_new((nu + 31) / 32, 0u), new_nodes(inv.empty() ? n_new : 0);
-  if (inv.empty()) {
-    for (size_t j = 0; j < n_new; ++j) new_nodes[j] = uint32_t(n_old + j);
-    for (uint32_t u : new_nodes) is_new[u >> 5] |= 1u << (u & 31u);
-  } else {
-    for (size_t j = 0; j < n_new; ++j) is_new[inv[n_old + j] >> 5] |= 1u << (inv[n_old + j] & 31u);
-    for (size_t u = 0; u < nu; ++u)
-      if ((is_new[u >> 5] >> (u & 31u)) & 1u) new_nodes.push_back(uint32_t(u));
-  }
+  std::vector<uint32_t> is_new, new_nodes;
+  mark_new(c.inv, n_old, n_new, nu, is_new, new_nodes);
   const size_t nn = new_nodes.size();
 
   ClusterTotals* d_totals = static_cast<ClusterTotals*>(c.d_totals);
@@ -78,56 +64,35 @@ extern "C" int blurrily_storage_cluster_tree_extend(trigram_map m, const uint32_
   if (n_old_merges)
     BLURRILY_HIP_TRY(hipMemcpyAsync(d_records, old_merges, n_old_merges * sizeof(ClusterTreeMerge), hipMemcpyHostToDevice, stream));
 
-  // the rounds' buffers (cluster_tree.hip's)
-  ClusterTreeRoundArgs r{};
-  uint32_t* d_counters = nullptr;                             // [0]: the merges so far
-  if (c.more(r.best, nu * 8, true) < 0 || c.more(r.comp, nu * 4) < 0 || c.more(r.closed, nu, true) < 0 ||
-      c.more(r.merges, nu * sizeof(ClusterTreeMerge)) < 0 || c.more(d_counters, 16, true) < 0)
-    return -1;
-  r.parent = c.d_parent; r.refs = c.d_refs; r.n_nodes = uint32_t(nu); r.n_merges = d_counters; r.totals = d_totals;
-  if (launch_cluster_tree_flatten(r, stream) < 0) return -1;  // (every number its own component)
+  TreeRounds t;
+  if (t.begin(c, d_totals) < 0) return -1;
+  const ClusterTreeRoundArgs& r = t.r;
 
   // the old records as keys: which of them are candidates at all
   const ClusterTreeExtendRecordsArgs ra{d_records, uint32_t(n_old_merges), c.d_refs, c.x.needles.ntri, d_is_new, uint32_t(nu),
                                         min_permille, d_keys, r.comp, r.best};
   if (launch_cluster_tree_extend_resolve(ra, stream) < 0) return -1;
 
-  uint32_t found = 0;
-  bool done = false;
-  for (uint32_t round = 1; round <= kTreeExtendMaxRounds && !done; ++round) {
-    // the new nodes over every window of both images (windows_per_workgroup by their number, not the numbering's)
-    auto launch = [&](const ClusterSweepArgs& a) {
+  // a round's offer: the new nodes over every window of both images (windows_per_workgroup by their number, not the
+  // numbering's), then the old records
+  const auto offer = [&](uint32_t round) {
+    const auto launch = [&](const ClusterSweepArgs& a) {
       return launch_cluster_tree_extend_sweep({ClusterTreeSweepArgs{a, r.comp, r.closed, r.best, round}, d_new_nodes, d_is_new},
                                               stream);
     };
-    if (c.sweep(nn, min_permille, d_totals, launch) < 0) return -1;
-    if (launch_cluster_tree_extend_offer(ra, stream) < 0) return -1;
-    if (launch_cluster_tree_merge(r, stream) < 0 || launch_cluster_tree_flatten(r, stream) < 0) return -1;
-    uint32_t now = 0;
-    BLURRILY_HIP_TRY(hipMemcpyAsync(&now, d_counters, 4, hipMemcpyDeviceToHost, stream));
-    BLURRILY_HIP_TRY(hipStreamSynchronize(stream));
-    done = now == found;
-    found = now;
-  }
-  if (!done || found >= nu) { errno = EIO; return -1; }       // (the round bound ran out; a forest has fewer edges than nodes)
+    return c.sweep(nn, min_permille, d_totals, launch) < 0 ? -1 : launch_cluster_tree_extend_offer(ra, stream);
+  };
+  if (t.run(offer) < 0) return -1;
 
   if (launch_cluster_label(c.label_args(), stream) < 0) return -1;
   ClusterTotals totals{};
-  if (c.read_totals(&totals) < 0) return -1;
-  std::vector<ClusterTreeMerge> got(found);
-  if (found)
-    BLURRILY_HIP_TRY(hipMemcpyAsync(got.data(), r.merges, found * sizeof(ClusterTreeMerge), hipMemcpyDeviceToHost, stream));
+  if (c.read_totals(&totals) < 0 || t.read_records() < 0) return -1;
   if (c.wait(&totals) < 0) return -1;                         // (the labels and records are copied out only on success)
   if (n_old) BLURRILY_HIP_TRY(hipMemcpyAsync(labels_old, c.d_labels, n_old * 4, hipMemcpyDeviceToHost, stream));
   if (n_new) BLURRILY_HIP_TRY(hipMemcpyAsync(labels_new, c.d_labels + n_old, n_new * 4, hipMemcpyDeviceToHost, stream));
   BLURRILY_HIP_TRY(hipStreamSynchronize(stream));
-  // the order of the records: height descending, then the lower reference, then the higher
-  std::sort(got.begin(), got.end(), [](const ClusterTreeMerge& x, const ClusterTreeMerge& y) {
-    if (x.permille != y.permille) return x.permille > y.permille;
-    return x.a != y.a ? x.a < y.a : x.b < y.b;
-  });
-  for (uint32_t i = 0; i < found; ++i) merges[i] = {got[i].a, got[i].b, got[i].permille};
-  if (n_merges) *n_merges = found;
+  t.deliver(merges);
+  if (n_merges) *n_merges = t.found;
   if (n_clusters) *n_clusters = totals.clusters;
   if (n_edges) *n_edges = totals.edges;
   return 0;

@@ -1,8 +1,8 @@
 // cluster_within.hip -- blurrily_storage_cluster_within (include/blurrily_storage.h):
 // blurrily_storage_cluster's components within caller-given blocks, one call for all blocks.  The call sequence is
 // ClusterCall's (cluster_host.h) over a numbering made here, before a GPU is asked for, because the numbering is where a
-// reference listed under two keys shows.  On top of it: each number's key on the device, and the plan
-// (cluster_host.h's plan_within_blocks, which blurrily_storage_cluster_tree_within shares) -- the numbers
+// reference listed under two keys shows.  On top of it, from ClusterCall::begin_blocked, which the other two blocked
+// entries share: each number's key on the device, and the plan (cluster_plan.h's plan_within_blocks) -- the numbers
 // sorted by (key, number), every block given to one of two kernels (cluster_within_kernels.hip): the direct kernel's
 // tiles for a block of at most kClusterWithinDirectMax listed members, the sweep's needle list for a larger one.  Both
 // unite in the one forest; the node tables and the labels are cluster_kernels.hip's kernels as they are.
@@ -35,24 +35,17 @@ extern "C" int blurrily_storage_cluster_within(trigram_map m, const uint32_t* re
   m->last_kernels.clear();
 
   // the plan: the numbers block after block, every block the direct kernel's or the sweep's
-  const size_t nu = uniq.size();
-  ClusterWithinPlan plan;
-  if (plan_within_blocks(key_of, m->scope_strategy, plan) < 0) return -1;
-
   ClusterCall c(m, stream);
-  if (c.begin(std::move(uniq), std::move(inv), n, 1, sizeof(ClusterTotals)) < 0) return -1;
+  if (c.begin_blocked(std::move(uniq), std::move(inv), key_of, n) < 0) return -1;
   ClusterTotals* d_totals = static_cast<ClusterTotals*>(c.d_totals);
-  if (c.upload(plan, key_of) < 0) return -1;
 
   // the large blocks over the images (windows_per_workgroup by their members' number, not the numbering's) ...
-  if (c.sweep(plan.swept.size(), min_permille, d_totals, [&](const ClusterSweepArgs& a) {
-        return launch_cluster_within_sweep({a, plan.d_swept, plan.d_block_of}, stream);
+  if (c.sweep(c.plan.swept.size(), min_permille, d_totals, [&](const ClusterSweepArgs& a) {
+        return launch_cluster_within_sweep({a, c.d_swept, c.d_block_of}, stream);
       }) < 0)
     return -1;
   // ... and the small ones from the extraction's codes, into the same forest
-  ClusterWithinArgs wa{plan.d_tiles, plan.d_order, uint32_t(plan.tiles.size()), uint32_t(nu), c.x.needles.codes,
-                       c.x.needles.qoff, c.x.needles.ntri, uint32_t(nu), min_permille, c.d_parent, d_totals};
-  if (launch_cluster_within(wa, stream) < 0) return -1;
+  if (launch_cluster_within(c.within_args(min_permille, c.d_parent, d_totals), stream) < 0) return -1;
 
   if (launch_cluster_label(c.label_args(), stream) < 0) return -1;
   ClusterTotals totals{};

@@ -373,7 +373,7 @@ def test_blocks_of_every_size_around_the_tile_and_the_workgroup_equal_keys_and_d
 
 
 def test_auto_sweeps_a_block_above_the_direct_cap_and_scores_the_others_through_the_same_cursor():
-    cap = 100000                                              # cluster_host.h: kClusterWithinDirectMax
+    cap = 100000                                              # cluster_plan.h: kClusterWithinDirectMax
     n = 2 * cap + 301
     hay, off = W.geonames(n, 2000, 41)
     m = _map_of({i + 1: s for i, s in enumerate(W.unpack(hay, off))})

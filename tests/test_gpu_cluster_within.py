@@ -321,7 +321,7 @@ def test_the_calls_around_a_cluster_within_call_are_unchanged_and_the_kernels_ar
 
 
 def test_auto_sweeps_a_block_above_the_direct_cap_and_scores_the_others_into_the_same_forest():
-    cap = 100000                                              # cluster_within.hip: kClusterWithinDirectMax
+    cap = 100000                                              # cluster_plan.h: kClusterWithinDirectMax
     n = 2 * cap + 301
     hay, off = W.geonames(n, 2000, 41)
     m = _map_of({i + 1: s for i, s in enumerate(W.unpack(hay, off))})
