@@ -175,6 +175,12 @@ _ENTRIES = {
     # ... of the graph within caller-given blocks
     "blurrily_storage_cluster_edges_within": (C.c_int, [_vp, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32,
                                                         C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
+    # ... over two lists: only the edges with a new end (the second list's), from a sweep of the new ones alone
+    "blurrily_storage_cluster_edges_extend": (C.c_int, [_vp, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint32,
+                                                        C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
+    # ... only the edges with one end in each list (record linkage), from a sweep of the smaller side
+    "blurrily_storage_cluster_edges_between": (C.c_int, [_vp, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint32,
+                                                         C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
 }
 EXPORTED_SYMBOLS = tuple(_ENTRIES)
 

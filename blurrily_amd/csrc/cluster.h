@@ -437,4 +437,19 @@ struct ClusterEdgesRowsArgs {
 };
 int launch_cluster_edges_rows(const ClusterEdgesRowsArgs& a, hipStream_t stream);
 
+// The edges with a new end, or with an end on each side (cluster_edges_extend_kernels.hip):
+// cluster_extend_sweep_kernel's range -- needle b / tasks of the launch is node needles[s.q_base + b / tasks], it sweeps
+// EVERY window of the image, whichever image it lives in, and a candidate that is the needle is skipped -- with
+// cluster_edges_sweep_kernel's append for an ending.  side is a bit per number (mark_new's: the new numbers, or the
+// right ones); every needle of a call lies on ONE side.  A candidate on the needle's side is passed over when
+// `between` is set, and otherwise when it lies at a higher position than the needle (such an edge is its higher end's).
+struct ClusterEdgesExtendSweepArgs {
+  ClusterSweepArgs s;            // (s.q_base and s.n count in needles; s.parent and s.totals are not used)
+  const uint32_t*  needles;      // the swept side's numbers
+  const uint32_t*  side;         // [(n_nodes + 31) / 32]
+  uint32_t         between;      // non-zero: only edges across the sides
+  ClusterEdgesOut  out;
+};
+int launch_cluster_edges_extend_sweep(const ClusterEdgesExtendSweepArgs& a, hipStream_t stream);
+
 }  // namespace blurrily

@@ -6,7 +6,8 @@
 // tables are filled per forest), and with ClusterTotals::edges as the call's cursor: every sweep launch of the call
 // appends through it (cluster_edges_kernels.hip), and what it holds after the last one is the edge count, in every
 // mode.  An emitting call then sorts the keys (segsort.h, one segment) and turns them into records; a count-only call,
-// or one whose count does not fit, launches neither.
+// or one whose count does not fit, launches neither (ClusterCall::deliver_edges, which cluster_edges_extend.hip ends
+// with too).
 #include "map_internal.h"
 #include "cluster.h"
 #include "cluster_host.h"
@@ -54,31 +55,7 @@ int cluster_edges_run(trigram_map m, const uint32_t* references, size_t n, bool 
       return -1;
     if (launch_cluster_edges_within({c.within_args(min_permille, nullptr, nullptr), out}, stream) < 0) return -1;
   }
-  ClusterTotals totals{};
-  if (c.read_totals(&totals) < 0 || c.wait(&totals) < 0) return -1;
-  const uint64_t E = totals.edges;
-  *n_edges = E;
-  if (!edges) return 0;                                       // count only
-  if (capacity < E) { errno = ERANGE; return -1; }
-  if (E > out.room) { errno = EOVERFLOW; return -1; }          // (the option's bound: not every key was stored)
-  if (E == 0) return 0;
-
-  const ClusterEdgeKey* sorted = out.keys;
-  DeviceBuffer tables;
-  if (E >= 2) {
-    ClusterEdgeKey* d_sorted = nullptr;
-    if (c.more(d_sorted, E * sizeof(ClusterEdgeKey)) < 0) return -1;
-    const uint32_t off[2] = {0u, uint32_t(E)};                // (E <= room <= 2^31)
-    if (segmented_sort(out.keys, d_sorted, off, 1, 2, false, tables, stream) < 0) return -1;
-    sorted = d_sorted;
-  }
-  ClusterTreeMerge* d_rows = nullptr;
-  if (c.more(d_rows, E * sizeof(ClusterTreeMerge)) < 0) return -1;
-  if (launch_cluster_edges_rows({sorted, c.d_refs, uint32_t(E), uint32_t(c.nu), d_rows}, stream) < 0) return -1;
-  BLURRILY_HIP_TRY(hipStreamSynchronize(stream));             // (the records are copied out only on success)
-  BLURRILY_HIP_TRY(hipMemcpyAsync(edges, d_rows, E * sizeof(ClusterTreeMerge), hipMemcpyDeviceToHost, stream));
-  BLURRILY_HIP_TRY(hipStreamSynchronize(stream));
-  return 0;
+  return c.deliver_edges(out, edges, capacity, n_edges);      // (the count, ERANGE or EOVERFLOW, the sort, the records)
 }
 
 }  // namespace

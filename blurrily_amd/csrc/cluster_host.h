@@ -1,7 +1,7 @@
 // cluster_host.h -- the host-side call sequence the clustering entries share (cluster.hip, cluster_levels.hip,
 // cluster_centres.hip, cluster_cores.hip, cluster_extend.hip, cluster_within.hip, cluster_tree.hip,
-// cluster_tree_extend.hip, cluster_core_tree.hip, cluster_tree_within.hip, cluster_edges.hip; DESIGN.md sections 25
-// and 40): ClusterCall, which owns a call's device scratch, runs what every entry does in front of its sweeps -- for the
+// cluster_tree_extend.hip, cluster_core_tree.hip, cluster_tree_within.hip, cluster_edges.hip, cluster_edges_extend.hip;
+// DESIGN.md sections 25 and 40): ClusterCall, which owns a call's device scratch, runs what every entry does in front of its sweeps -- for the
 // three blocked entries the block plan too --, fills the sweeps' common arguments per image and chunk, and reads the
 // totals back; and TreeRounds, the Boruvka rounds of the four tree entries around the entry's own offer of edges.  The
 // arithmetic that needs no GPU (the numbering, the plan, the new numbers, the record order) is cluster_plan.h's.  The
@@ -80,6 +80,11 @@ struct ClusterCall {
   // EIO if one of the forests' totals, t[0 .. forests), reports that a bounded loop ran out.
   int read_totals(void* host);
   int wait(const ClusterTotals* t);
+  // The ending of the entries whose sweeps append edge keys through ClusterTotals::edges (cluster_edges.hip,
+  // cluster_edges_extend.hip; one forest): the totals, the count into *n_edges in every mode, ERANGE against the
+  // caller's capacity or EOVERFLOW against out.room, and for an emitting call the keys sorted (segsort.h, one segment),
+  // turned into records and copied to edges[] -- only on success.
+  int deliver_edges(const ClusterEdgesOut& out, blurrily_cluster_merge_t* edges, uint64_t capacity, uint64_t* n_edges);
 
   trigram_map m;
   hipStream_t stream;

@@ -97,6 +97,35 @@ int ClusterCall::wait(const ClusterTotals* t) {
   return 0;
 }
 
+int ClusterCall::deliver_edges(const ClusterEdgesOut& out, blurrily_cluster_merge_t* edges, uint64_t capacity,
+                               uint64_t* n_edges) {
+  ClusterTotals totals{};
+  if (read_totals(&totals) < 0 || wait(&totals) < 0) return -1;
+  const uint64_t E = totals.edges;
+  *n_edges = E;
+  if (!edges) return 0;                                       // count only
+  if (capacity < E) { errno = ERANGE; return -1; }
+  if (E > out.room) { errno = EOVERFLOW; return -1; }          // (the option's bound: not every key was stored)
+  if (E == 0) return 0;
+
+  const ClusterEdgeKey* sorted = out.keys;
+  DeviceBuffer tables;
+  if (E >= 2) {
+    ClusterEdgeKey* d_sorted = nullptr;
+    if (more(d_sorted, E * sizeof(ClusterEdgeKey)) < 0) return -1;
+    const uint32_t off[2] = {0u, uint32_t(E)};                // (E <= room <= 2^31)
+    if (segmented_sort(out.keys, d_sorted, off, 1, 2, false, tables, stream) < 0) return -1;
+    sorted = d_sorted;
+  }
+  ClusterTreeMerge* d_rows = nullptr;
+  if (more(d_rows, E * sizeof(ClusterTreeMerge)) < 0) return -1;
+  if (launch_cluster_edges_rows({sorted, d_refs, uint32_t(E), uint32_t(nu), d_rows}, stream) < 0) return -1;
+  BLURRILY_HIP_TRY(hipStreamSynchronize(stream));             // (the records are copied out only on success)
+  BLURRILY_HIP_TRY(hipMemcpyAsync(edges, d_rows, E * sizeof(ClusterTreeMerge), hipMemcpyDeviceToHost, stream));
+  BLURRILY_HIP_TRY(hipStreamSynchronize(stream));
+  return 0;
+}
+
 int TreeRounds::begin(ClusterCall& c, ClusterTotals* d_totals) {
   const size_t nu = c.nu;
   stream = c.stream;

@@ -141,6 +141,20 @@ inline void mark_new(const std::vector<uint32_t>& inv, size_t n_old, size_t n_ne
   }
 }
 
+// Which side of blurrily_storage_cluster_edges_between sweeps: the edges with an end on each side
+// are the same set whichever side holds the needles, and a sweep costs per needle, so the side with fewer numbers does
+// (a tie: the right).  is_right and right_nodes are mark_new's over left ++ right -- a number both lists name is on the
+// right only.  True: the right side sweeps (right_nodes are the needles, left_nodes is left empty).  False: the left
+// side does, and left_nodes becomes its numbers, ascending.
+inline bool choose_between_side(const std::vector<uint32_t>& is_right, size_t n_right_nodes, size_t nu,
+                                std::vector<uint32_t>& left_nodes) {
+  left_nodes.clear();
+  if (n_right_nodes <= nu - n_right_nodes) return true;
+  for (size_t u = 0; u < nu; ++u)
+    if (!((is_right[u >> 5] >> (u & 31u)) & 1u)) left_nodes.push_back(uint32_t(u));
+  return false;
+}
+
 // The cluster tree's rounds.  Every round that merges at least halves the components that still have an edge leaving
 // them: 28 rounds serve 2^27 nodes, and one more finds nothing.
 constexpr uint32_t kTreeMaxRounds = 40;

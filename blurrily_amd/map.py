@@ -1107,9 +1107,85 @@ class RawMap:
         _check(call(None, 0, C.byref(total)))
         return int(total.value)
 
+    def _cluster_edges_two_call(self, symbol, first, second, min_permille):
+        """What the extend and between methods share: ``(call(rows, cap, n_edges), n)`` over two lists."""
+        self._check_open()
+        mp = _permille(min_permille)
+        one, two = self._refs(first), self._refs(second)
+        ptr = lambda a: a.ctypes.data if len(a) else None
+        fn = getattr(self._lib, symbol)
+        return (lambda rows, cap, n_edges: fn(self._h, ptr(one), len(one), ptr(two), len(two), mp, rows, cap,
+                                              n_edges)), len(one) + len(two)
+
+    def _cluster_edges_two(self, symbol, first, second, min_permille, capacity):
+        call, n = self._cluster_edges_two_call(symbol, first, second, min_permille)
+        total = C.c_uint64(0)
+        start = max(1024, 8 * n) if capacity is None else int(capacity)
+        if not 0 <= start < 1 << 64:
+            raise OverflowError(f"capacity {capacity!r} out of range of uint64_t")
+        rows = _call_growing(lambda rows, cap: call(rows, cap, C.byref(total)), start, lambda: int(total.value), row=(3,))
+        return rows[:int(total.value)]
+
+    def _cluster_edge_count_two(self, symbol, first, second, min_permille):
+        call, _ = self._cluster_edges_two_call(symbol, first, second, min_permille)
+        total = C.c_uint64(0)
+        _check(call(None, 0, C.byref(total)))
+        return int(total.value)
+
+    def cluster_edges_extend(self, old_refs, new_refs, min_permille, capacity=None):
+        """The ``cluster_edges`` records over both lists that have at least one end in ``new_refs``, each once
+        (blurrily_storage_cluster_edges_extend): only the new references sweep the map.  A reference both lists name
+        is new.  ``merge_edges(cluster_edges(old minus new), this)`` is ``cluster_edges(old and new)`` byte for byte:
+        how an edge list is kept current after a put.  E is ``cluster_extend``'s n_edges.  Records, order, ``capacity``
+        and EOVERFLOW are ``cluster_edges``'; ``adjacency``, ``cut_tree`` and ``merge_profile`` take the records as
+        they are."""
+        return self._cluster_edges_two("blurrily_storage_cluster_edges_extend", old_refs, new_refs, min_permille, capacity)
+
+    def cluster_edge_count_extend(self, old_refs, new_refs, min_permille):
+        """How many records ``cluster_edges_extend`` would return: no buffer is handed, nothing is sorted."""
+        return self._cluster_edge_count_two("blurrily_storage_cluster_edges_extend", old_refs, new_refs, min_permille)
+
+    def cluster_edges_between(self, left, right, min_permille, capacity=None):
+        """Record linkage: the ``cluster_edges`` records with exactly one end in ``left`` and one in ``right``
+        (blurrily_storage_cluster_edges_between).  A reference both lists name is on the right only.  The side with
+        fewer distinct references sweeps the map, whichever way round the lists are given, and for disjoint lists
+        both ways round give identical bytes.  ``cluster_edges_extend(l, r)`` is this merged with ``cluster_edges(r)``.
+        Records, order, ``capacity`` and EOVERFLOW are ``cluster_edges``'.  ``adjacency(records, left + right)`` takes
+        them as they are: a left row's first neighbour is its best link (the records come best first); ``cut_tree``
+        and ``merge_profile`` take them too."""
+        return self._cluster_edges_two("blurrily_storage_cluster_edges_between", left, right, min_permille, capacity)
+
+    def cluster_edge_count_between(self, left, right, min_permille):
+        """How many records ``cluster_edges_between`` would return: no buffer is handed, nothing is sorted."""
+        return self._cluster_edge_count_two("blurrily_storage_cluster_edges_between", left, right, min_permille)
+
+    @staticmethod
+    def merge_edges(*record_lists):
+        """Edge record lists, each in ``cluster_edges``' total order (permille descending, then a, then b), as one
+        list in that order: uint32[E, 3].  How a caller keeps an edge list current:
+        ``merge_edges(held, cluster_edges_extend(old, new, floor))``.  ValueError for a list that is not in order or
+        for a record present twice, in one list or in two.  Needs no map and no GPU."""
+        lists = [RawMap._records(rows, "edges") for rows in record_lists]
+        for rows in lists:
+            if len(rows) > 1:
+                prev, nxt = rows[:-1], rows[1:]
+                eq = lambda c: prev[:, c] == nxt[:, c]
+                before = (prev[:, 2] > nxt[:, 2]) | (eq(2) & ((prev[:, 0] < nxt[:, 0]) | (eq(0) & (prev[:, 1] < nxt[:, 1]))))
+                if not before.all():
+                    raise ValueError("a record list is not in order (permille descending, then a, then b), or holds "
+                                     "a record twice")
+        if not sum(len(rows) for rows in lists):
+            return np.zeros((0, 3), dtype=np.uint32)
+        rows = np.concatenate(lists)
+        rows = np.ascontiguousarray(rows[np.lexsort((rows[:, 1], rows[:, 0], -rows[:, 2].astype(np.int64)))])
+        if len(rows) > 1 and (rows[1:] == rows[:-1]).all(axis=1).any():
+            raise ValueError("a record is present twice")
+        return rows
+
     @staticmethod
     def adjacency(edges, references):
-        """``cluster_edges`` records as neighbour lists, what a caller's own graph code starts from:
+        """``cluster_edges`` records (``cluster_edges_extend``'s and ``cluster_edges_between``'s too: of a left row's
+        neighbours the first is its best link) as neighbour lists, what a caller's own graph code starts from:
         ``(row_off uint64[n + 1], neighbour uint32[2 E], permille uint32[2 E])``, one row per element of ``references``
         -- element i's neighbours are ``neighbour[row_off[i]:row_off[i + 1]]`` with their similarities beside them, in
         the records' order.  A repeated reference gets the same row each time it is listed (so the rows add up to more

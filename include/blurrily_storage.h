@@ -724,7 +724,7 @@ int blurrily_storage_cluster_tree_within(trigram_map haystack, const uint32_t* r
  * word that holds both ends in 27 bits each -- and for the blocked form blocks NULL with n > 0 or a reference listed
  * more than once with different keys); ENODEV without a usable GPU; EIO for a device error word.  The records are
  * written only on success.
- * Not built: the edges with a new end only (an extend form), scopes, _device variants, protocol verbs. */
+ * Not built: scopes, _device variants, protocol verbs. */
 int blurrily_storage_cluster_edges(trigram_map haystack, const uint32_t* references, size_t n,
                                    uint32_t min_permille, blurrily_cluster_merge_t* edges,
                                    uint64_t capacity, uint64_t* n_edges);
@@ -732,6 +732,36 @@ int blurrily_storage_cluster_edges_within(trigram_map haystack, const uint32_t* 
                                           const uint32_t* blocks, size_t n, uint32_t min_permille,
                                           blurrily_cluster_merge_t* edges, uint64_t capacity,
                                           uint64_t* n_edges);
+
+/* Cluster edges extend and between: blurrily_storage_cluster_edges over two lists, cut down to the edges a caller who
+ * already holds some of them is missing.  Only one side sweeps the map, so the cost follows that
+ * side, not the lists together.  Nodes, T, R, m, the edge test, repeats, shuffled lists, absent references, unlisted
+ * references (never an end), deletes, pending puts, a reference put again and "devices" > 1: exactly as for
+ * blurrily_storage_cluster.  Old and new are blurrily_storage_cluster_extend's: a reference the second list names is NEW
+ * (on the RIGHT), whatever the first list says of it.  Records, their permille, their total order, the capacity
+ * protocol (edges == NULL counts only; ERANGE leaves edges untouched and fills *n_edges; EOVERFLOW against
+ * min(capacity, "cluster_edges_max")) and the required n_edges are blurrily_storage_cluster_edges'.
+ *   _extend:  the edges of blurrily_storage_cluster over both lists that have at least one new end, each once.
+ *             *n_edges is byte for byte blurrily_storage_cluster_extend's n_edges for the same lists and floor.  The
+ *             records of blurrily_storage_cluster_edges over the old references that are not new, and of this call,
+ *             merged under the total order, are byte for byte blurrily_storage_cluster_edges over both lists: how a
+ *             caller keeps an edge list current after a put.  n_old == 0 gives blurrily_storage_cluster_edges(new_refs);
+ *             n_new == 0 gives success with no edge.
+ *   _between: the edges with exactly one end on each side -- record linkage: which rows of one list match which of
+ *             another.  _extend(L, R) is _between(L, R) merged with blurrily_storage_cluster_edges(R).  For disjoint
+ *             lists _between(L, R) and _between(R, L) are identical bytes.  Either n being 0 gives no edge.  The side
+ *             with fewer distinct listed references sweeps (a tie: the right), whichever way round the lists are named.
+ * The output depends on the map's contents, the two lists as sets and min_permille only; two runs give identical bytes.
+ * 0, or -1 with errno: EINVAL before anything needs a GPU and with nothing written (haystack NULL, min_permille > 1000,
+ * a list NULL with its n > 0, n_edges NULL, the two n together above BLURRILY_CLUSTER_TREE_MAX); ENODEV without a
+ * usable GPU; ERANGE and EOVERFLOW as above; EIO for a device error word.  The records are written only on success.
+ * Not built: blocks or scopes on either entry, _device variants, protocol verbs, Ruby methods. */
+int blurrily_storage_cluster_edges_extend(trigram_map haystack, const uint32_t* old_refs, size_t n_old,
+                                          const uint32_t* new_refs, size_t n_new, uint32_t min_permille,
+                                          blurrily_cluster_merge_t* edges, uint64_t capacity, uint64_t* n_edges);
+int blurrily_storage_cluster_edges_between(trigram_map haystack, const uint32_t* left_refs, size_t n_left,
+                                           const uint32_t* right_refs, size_t n_right, uint32_t min_permille,
+                                           blurrily_cluster_merge_t* edges, uint64_t capacity, uint64_t* n_edges);
 
 /* Tokeniser (ext/blurrily/tokeniser.h:34, tokeniser.c:59-119): `output` needs
  * strlen(input)+1 slots; returns the number of distinct codes, ascending. */
