@@ -181,6 +181,10 @@ _ENTRIES = {
     # ... only the edges with one end in each list (record linkage), from a sweep of the smaller side
     "blurrily_storage_cluster_edges_between": (C.c_int, [_vp, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint32,
                                                          C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
+    # cluster_cores within caller-given blocks: a degree counts the edges whose ends carry one block key
+    "blurrily_storage_cluster_cores_within": (C.c_int, [_vp, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32,
+                                                        C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32),
+                                                        C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
 }
 EXPORTED_SYMBOLS = tuple(_ENTRIES)
 

@@ -452,4 +452,31 @@ struct ClusterEdgesExtendSweepArgs {
 };
 int launch_cluster_edges_extend_sweep(const ClusterEdgesExtendSweepArgs& a, hipStream_t stream);
 
+// Cluster cores within blocks (cluster_cores_within_kernels.hip): cluster cores over the edges
+// whose ends carry one block key, so a degree counts those edges only.  The two passes are cluster cores' -- degree
+// mode, then across a launch boundary unite mode -- and in each a block is served by one of two kernels, as
+// cluster_within serves it, both adding into the one degree[], anchor[], forest and totals.
+// cluster_within_kernel's direct form with cluster cores' two endings.  Degree mode adds every pair that passes to the
+// degree of both its ends and to totals->t.edges and touches no parent; unite mode reads the final degrees, unites the
+// pairs of two cores in w.parent (counted in totals->core_edges) and raises anchor[] of a pair's end that is no core to
+// the key of the end that is one.  (w.totals is not used.)
+struct ClusterCoresWithinArgs {
+  ClusterWithinArgs   w;
+  uint32_t*           degree;    // [n_nodes] zeroed by the caller; degree mode adds, unite mode reads
+  unsigned long long* anchor;    // [n_nodes] zeroed by the caller; unite mode raises
+  uint32_t            min_degree;
+  ClusterCoresTotals* totals;
+};
+int launch_cluster_cores_within(const ClusterCoresWithinArgs& a, bool unite, hipStream_t stream);
+
+// cluster_cores_sweep_kernel's sweep with cluster_within_sweep_kernel's needles and key test: needle b / tasks of the
+// launch is number needles[c.s.q_base + b / tasks], and a candidate node under another key than the needle's is passed
+// over before anything is counted or raised.
+struct ClusterCoresWithinSweepArgs {
+  ClusterCoresSweepArgs c;       // (c.s.q_base and c.s.n count in needles)
+  const uint32_t*       needles; // the swept blocks' numbers
+  const uint32_t*       block_of;   // [n_nodes] each number's key
+};
+int launch_cluster_cores_within_sweep(const ClusterCoresWithinSweepArgs& a, bool unite, hipStream_t stream);
+
 }  // namespace blurrily

@@ -1,8 +1,8 @@
 // cluster_host.h -- the host-side call sequence the clustering entries share (cluster.hip, cluster_levels.hip,
-// cluster_centres.hip, cluster_cores.hip, cluster_extend.hip, cluster_within.hip, cluster_tree.hip,
+// cluster_centres.hip, cluster_cores.hip, cluster_extend.hip, cluster_within.hip, cluster_cores_within.hip, cluster_tree.hip,
 // cluster_tree_extend.hip, cluster_core_tree.hip, cluster_tree_within.hip, cluster_edges.hip, cluster_edges_extend.hip;
 // DESIGN.md sections 25 and 40): ClusterCall, which owns a call's device scratch, runs what every entry does in front of its sweeps -- for the
-// three blocked entries the block plan too --, fills the sweeps' common arguments per image and chunk, and reads the
+// blocked entries the block plan too --, fills the sweeps' common arguments per image and chunk, and reads the
 // totals back; and TreeRounds, the Boruvka rounds of the four tree entries around the entry's own offer of edges.  The
 // arithmetic that needs no GPU (the numbering, the plan, the new numbers, the record order) is cluster_plan.h's.  The
 // device code is each entry's own.
@@ -44,11 +44,12 @@ struct ClusterCall {
   int begin(std::vector<uint32_t>&& numbering, std::vector<uint32_t>&& element_number, size_t n, uint32_t forests,
             size_t totals_bytes);
 
-  // The beginning of a blocked entry, one forest and one ClusterTotals: the block plan from number_nodes_keyed's
-  // key_of under the map's "scope_strategy", begin() with that numbering, and the plan onto the device -- the tiles
-  // with `order` if there are tiles, the swept numbers with every number's key if a block is swept.
+  // The beginning of a blocked entry, one forest and one ClusterTotals (or the larger record an entry's kernels add
+  // into, of totals_bytes): the block plan from number_nodes_keyed's key_of under the map's "scope_strategy", begin()
+  // with that numbering, and the plan onto the device -- the tiles with `order` if there are tiles, the swept numbers
+  // with every number's key if a block is swept.
   int begin_blocked(std::vector<uint32_t>&& numbering, std::vector<uint32_t>&& element_number,
-                    const std::vector<uint32_t>& key_of, size_t n);
+                    const std::vector<uint32_t>& key_of, size_t n, size_t totals_bytes = sizeof(ClusterTotals));
   // ... and the direct kernel's arguments over the plan's tiles (an entry whose kernel unites nothing or counts
   // elsewhere passes null).
   ClusterWithinArgs within_args(uint32_t min_permille, uint32_t* parent, ClusterTotals* totals) const;

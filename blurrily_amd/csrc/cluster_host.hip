@@ -6,9 +6,9 @@ namespace blurrily {
 namespace detail {
 
 int ClusterCall::begin_blocked(std::vector<uint32_t>&& numbering, std::vector<uint32_t>&& element_number,
-                               const std::vector<uint32_t>& key_of, size_t n_listed) {
+                               const std::vector<uint32_t>& key_of, size_t n_listed, size_t n_totals_bytes) {
   if (plan_within_blocks(key_of, m->scope_strategy, plan) < 0 ||
-      begin(std::move(numbering), std::move(element_number), n_listed, 1, sizeof(ClusterTotals)) < 0)
+      begin(std::move(numbering), std::move(element_number), n_listed, 1, n_totals_bytes) < 0)
     return -1;
   const std::vector<ClusterWithinTile>& tiles = plan.tiles;
   if (more(d_tiles, tiles.size() * sizeof(ClusterWithinTile)) < 0 || more(d_swept, plan.swept.size() * 4) < 0 ||

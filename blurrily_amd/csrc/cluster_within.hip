@@ -1,7 +1,7 @@
 // cluster_within.hip -- blurrily_storage_cluster_within (include/blurrily_storage.h):
 // blurrily_storage_cluster's components within caller-given blocks, one call for all blocks.  The call sequence is
 // ClusterCall's (cluster_host.h) over a numbering made here, before a GPU is asked for, because the numbering is where a
-// reference listed under two keys shows.  On top of it, from ClusterCall::begin_blocked, which the other two blocked
+// reference listed under two keys shows.  On top of it, from ClusterCall::begin_blocked, which the other blocked
 // entries share: each number's key on the device, and the plan (cluster_plan.h's plan_within_blocks) -- the numbers
 // sorted by (key, number), every block given to one of two kernels (cluster_within_kernels.hip): the direct kernel's
 // tiles for a block of at most kClusterWithinDirectMax listed members, the sweep's needle list for a larger one.  Both

@@ -865,6 +865,42 @@ class RawMap:
         _, starts, sizes = np.unique(labels[order], return_index=True, return_counts=True)
         return [refs[order[s:s + k]].tolist() for s, k in zip(starts.tolist(), sizes.tolist()) if k >= 2]
 
+    def cluster_cores_within(self, references, blocks, min_permille, min_degree):
+        """``cluster_cores`` within blocks (blurrily_storage_cluster_cores_within): ``blocks[i]`` is a 32-bit key for
+        ``references[i]``, an edge needs both ends under one key, and a degree counts those edges only, so a core, a
+        border's anchor and a cluster never reach across a key.  One call serves all blocks.  Returns (labels[n]
+        uint32, degrees[n] uint32, kinds[n] uint8, the number of clusters, the number of within-block edges, the edges
+        between cores) as ``cluster_cores`` gives them: what one ``cluster_cores`` call per block gives, put back in
+        place, the counts summed."""
+        self._check_open()
+        mp = _permille(min_permille)
+        md = _u32(min_degree, "min_degree")
+        refs, keys = self._refs(references), self._refs(blocks)
+        if len(keys) != len(refs):
+            raise ValueError(f"{len(keys)} block keys for {len(refs)} references")
+        n = len(refs)
+        labels, degrees = (np.zeros(n, dtype=np.uint32) for _ in range(2))
+        kinds = np.zeros(n, dtype=np.uint8)
+        n_clusters, n_edges, n_core_edges = C.c_uint32(0), C.c_uint64(0), C.c_uint64(0)
+        ptr = lambda a: a.ctypes.data if n else None
+        _check(self._lib.blurrily_storage_cluster_cores_within(self._h, ptr(refs), ptr(keys), n, mp, md, ptr(labels),
+                                                               ptr(degrees), ptr(kinds), C.byref(n_clusters),
+                                                               C.byref(n_edges), C.byref(n_core_edges)))
+        return labels, degrees, kinds, int(n_clusters.value), int(n_edges.value), int(n_core_edges.value)
+
+    def dense_duplicates_within(self, references, blocks, min_permille, min_degree):
+        """The clusters of ``cluster_cores_within``, as ``dense_duplicates`` gives them: a list of lists of references,
+        cores and borders, each ascending, ordered by label; noise is left out.  Numpy over one call."""
+        refs = self._refs(references)
+        labels, _, kinds, _, _, _ = self.cluster_cores_within(refs, blocks, min_permille, min_degree)
+        refs, at = np.unique(refs, return_index=True)           # (a reference listed twice is one node)
+        labels, kinds = labels[at], kinds[at]
+        member = kinds >= _native.KIND_BORDER
+        refs, labels = refs[member], labels[member]
+        order = np.argsort(labels, kind="stable")               # (refs ascending within a label)
+        _, starts, sizes = np.unique(labels[order], return_index=True, return_counts=True)
+        return [refs[order[s:s + k]].tolist() for s, k in zip(starts.tolist(), sizes.tolist())]
+
     def cluster_tree(self, references, min_permille):
         """The single-linkage dendrogram of ``cluster`` at per-mille resolution (blurrily_storage_cluster_tree): the
         maximum spanning forest of the edges at or above ``min_permille``, an edge's height being its similarity in

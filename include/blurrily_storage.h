@@ -491,7 +491,8 @@ int blurrily_storage_cluster_centres(trigram_map haystack, const uint32_t* refer
  * nothing written but the three counts (0).  With "devices" > 1 the primary device alone serves the call.
  * 0, or -1 with errno: EINVAL before anything needs a GPU and with nothing written (haystack NULL, min_permille > 1000,
  * references or labels NULL with n > 0, n above 0xFFFFFFF0); ENODEV without a usable GPU; EIO if a bounded loop of the
- * device ran out. */
+ * device ran out.  Not built: a _device variant, a protocol verb.  (Within blocks:
+ * blurrily_storage_cluster_cores_within.) */
 #define BLURRILY_KIND_NONE   0
 #define BLURRILY_KIND_NOISE  1
 #define BLURRILY_KIND_BORDER 2
@@ -551,7 +552,8 @@ int blurrily_storage_cluster_extend(trigram_map haystack, const uint32_t* old_re
  * 0, or -1 with errno: EINVAL before anything needs a GPU and with nothing written (haystack NULL, min_permille > 1000,
  * references, blocks or labels NULL with n > 0, n above 0xFFFFFFF0, a reference listed more than once with different
  * keys); ENODEV without a usable GPU; EIO if a bounded loop of the device's union-find ran out.  The labels are written
- * only on success.  Not built: levels, centres, cores and extend within blocks, a _device variant, a protocol verb. */
+ * only on success.  Not built: levels, centres and extend within blocks, a _device variant, a protocol verb.  (Cores
+ * within blocks: blurrily_storage_cluster_cores_within.) */
 int blurrily_storage_cluster_within(trigram_map haystack, const uint32_t* references, const uint32_t* blocks, size_t n,
                                     uint32_t min_permille, uint32_t* labels, uint32_t* n_clusters, uint64_t* n_edges);
 
@@ -762,6 +764,39 @@ int blurrily_storage_cluster_edges_extend(trigram_map haystack, const uint32_t* 
 int blurrily_storage_cluster_edges_between(trigram_map haystack, const uint32_t* left_refs, size_t n_left,
                                            const uint32_t* right_refs, size_t n_right, uint32_t min_permille,
                                            blurrily_cluster_merge_t* edges, uint64_t capacity, uint64_t* n_edges);
+
+/* Cluster cores within blocks: blurrily_storage_cluster_cores' density clusters inside caller-given blocks, one call
+ * for all blocks -- the second look of a job that has blocked its records and found that single linkage chains
+ * look-alikes together.  blocks[i] is an opaque 32-bit key for references[i].  Nodes, T, R, m,
+ * the edge test, BLURRILY_NO_CLUSTER, repeats (under one key), a shuffled list, absent references, unlisted bridges,
+ * deletes, pending puts, a reference put again, "devices" > 1 and "scope_strategy" (0 chooses per block, 1 sweeps
+ * every block, 2 scores every block directly): exactly as for blurrily_storage_cluster_within.  Core, cluster, border,
+ * anchor (the core neighbour of the highest degree, the smallest reference among equals), noise, the BLURRILY_KIND_*
+ * values and the meaning of the three counts: exactly as for blurrily_storage_cluster_cores.
+ *   Edges:   blurrily_storage_cluster_within's: an edge needs both ends under one key.
+ *   Degrees: a degree counts those edges only.  So a core, a border's anchor and a cluster never reach across a key.
+ * With all keys equal every output is byte for byte blurrily_storage_cluster_cores'.  With min_degree 0 every node is a
+ * core, labels, n_clusters and n_edges are byte for byte blurrily_storage_cluster_within's, and n_core_edges == n_edges.
+ * With all keys distinct every held reference is its own label with degree 0 -- noise for min_degree >= 1, a core for
+ * 0 -- and the three counts are 0, except that n_clusters is the number of nodes when min_degree is 0.  In general the
+ * result equals one blurrily_storage_cluster_cores call per block: labels, degrees and kinds put back in place, the
+ * three counts summed.  degrees equals the degrees read off blurrily_storage_cluster_edges_within's records at the same
+ * floor.  All outputs depend on the map's contents, the set of (reference, key) pairs, min_permille and min_degree
+ * only; two runs give identical bytes under each strategy, and the three strategies give identical bytes.  Each block
+ * is served twice, first for the degrees and then for the unions and anchors: a small one is scored member against
+ * member from the device's copy of its members' trigrams, a large one sweeps the map.
+ * degrees, kinds, n_clusters, n_edges and n_core_edges may each be NULL.  n == 0: success, nothing written but the
+ * counts given (0).
+ * 0, or -1 with errno: EINVAL before anything needs a GPU and with nothing written (haystack NULL, min_permille > 1000,
+ * references, blocks or labels NULL with n > 0, n above 0xFFFFFFF0, a reference listed more than once with different
+ * keys; any min_degree is valid); ENODEV without a usable GPU; EIO if a bounded loop of the device ran out.  The outputs
+ * are written only on success.
+ * Not built: the core tree within blocks, levels, centres and extend within blocks, a _device variant, a protocol verb,
+ * a Ruby method. */
+int blurrily_storage_cluster_cores_within(trigram_map haystack, const uint32_t* references, const uint32_t* blocks,
+                                          size_t n, uint32_t min_permille, uint32_t min_degree,
+                                          uint32_t* labels, uint32_t* degrees, uint8_t* kinds,
+                                          uint32_t* n_clusters, uint64_t* n_edges, uint64_t* n_core_edges);
 
 /* Tokeniser (ext/blurrily/tokeniser.h:34, tokeniser.c:59-119): `output` needs
  * strlen(input)+1 slots; returns the number of distinct codes, ascending. */
