@@ -185,6 +185,11 @@ _ENTRIES = {
     "blurrily_storage_cluster_cores_within": (C.c_int, [_vp, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32,
                                                         C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32),
                                                         C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    # the core tree within caller-given blocks: core heights and the forest over the edges under one block key
+    "blurrily_storage_cluster_core_tree_within": (C.c_int, [_vp, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32,
+                                                            C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                            C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                                            C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
 }
 EXPORTED_SYMBOLS = tuple(_ENTRIES)
 

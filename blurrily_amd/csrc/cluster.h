@@ -479,4 +479,48 @@ struct ClusterCoresWithinSweepArgs {
 };
 int launch_cluster_cores_within_sweep(const ClusterCoresWithinSweepArgs& a, bool unite, hipStream_t stream);
 
+// Cluster core tree within blocks (cluster_core_tree_within_kernels.hip): the cluster core tree
+// over the edges whose ends carry one block key, so a core height ranks those edges only.  The height passes and the
+// rounds are the core tree's -- settle, merge and flatten as they are -- and in each a block is served by one of two
+// kernels, as cluster_within serves it, both adding into the one hist[], best[] and totals.  Each kernel has the core
+// tree's two endings, and one record of arguments serves both: the height ending reads core, hist, span, width and
+// count_edges (the first pass: the pairs that pass are added to totals->t.edges), the tree ending core, comp, closed,
+// best, round and count_edges (no height pass ran: round 1 adds its edges to totals->t.edges as well as to
+// totals->core_edges).
+// cluster_within_kernel's direct form with those endings (w.parent and w.totals are not used).
+struct ClusterCoreTreeWithinArgs {
+  ClusterWithinArgs   w;
+  const uint32_t*     core;      // [n_nodes] the brackets' lower ends, or (tree) the core heights; kNoCore: none
+  uint32_t*           hist;      // height: [n_nodes * kCoreBuckets] zero when the pass begins
+  uint32_t            span;      // height: heights in a bracket
+  uint32_t            width;     // height: heights in a counter, ceil(span / kCoreBuckets)
+  uint32_t            count_edges;
+  const uint32_t*     comp;      // tree: [n_nodes] each number's component, its root when the round began
+  const uint8_t*      closed;    // tree: [n_nodes] by component: no edge leaves it
+  unsigned long long* best;      // tree: [n_nodes] by component
+  uint32_t            round;     // tree: from 1
+  ClusterCoresTotals* totals;
+};
+int launch_cluster_core_tree_within(const ClusterCoreTreeWithinArgs& a, bool tree, hipStream_t stream);
+
+// cluster_core_tree_kernels.hip's sweep with cluster_within_sweep_kernel's needles and key test: needle b / tasks of the
+// launch is number needles[s.q_base + b / tasks], and a candidate node under another key than the needle's is passed
+// over before anything is counted, added or offered.
+struct ClusterCoreTreeWithinSweepArgs {
+  ClusterSweepArgs    s;         // (s.q_base and s.n count in needles; s.parent and s.totals are not used)
+  const uint32_t*     needles;   // the swept blocks' numbers
+  const uint32_t*     block_of;  // [n_nodes] each number's key
+  const uint32_t*     core;      // as above, and so the rest
+  uint32_t*           hist;
+  uint32_t            span;
+  uint32_t            width;
+  uint32_t            count_edges;
+  const uint32_t*     comp;
+  const uint8_t*      closed;
+  unsigned long long* best;
+  uint32_t            round;
+  ClusterCoresTotals* totals;
+};
+int launch_cluster_core_tree_within_sweep(const ClusterCoreTreeWithinSweepArgs& a, bool tree, hipStream_t stream);
+
 }  // namespace blurrily

@@ -46,18 +46,12 @@ extern "C" int blurrily_storage_cluster_core_tree(trigram_map m, const uint32_t*
   ClusterCoreHeightSettleArgs settle{d_core, d_above, d_hist, c.x.needles.ntri, uint32_t(nu), min_permille, min_degree,
                                      0, 0, d_totals};
   if (launch_cluster_core_height_settle(settle, stream) < 0) return -1;
-  if (min_degree) {
-    for (uint32_t span = 1001u - min_permille;; span = settle.width) {
-      settle.width = (span + kCoreBuckets - 1u) / kCoreBuckets;
-      settle.pass += 1;
-      auto launch = [&](const ClusterSweepArgs& a) {
-        return launch_cluster_core_height_sweep({a, d_core, d_hist, span, settle.width, settle.pass == 1u, d_totals}, stream);
-      };
-      if (c.sweep(nu, min_permille, nullptr, launch) < 0) return -1;
-      if (launch_cluster_core_height_settle(settle, stream) < 0) return -1;   // (reads the counters the sweep has finished)
-      if (settle.width == 1) break;                           // the brackets are one height wide
-    }
-  }
+  const auto pass = [&](uint32_t span, uint32_t width, bool first) {
+    return c.sweep(nu, min_permille, nullptr, [&](const ClusterSweepArgs& a) {
+      return launch_cluster_core_height_sweep({a, d_core, d_hist, span, width, first, d_totals}, stream);
+    });
+  };
+  if (min_degree && core_height_passes(settle, stream, pass) < 0) return -1;
 
   // the forest: the cluster tree's rounds over the edges between two numbers with a core height
   TreeRounds t;

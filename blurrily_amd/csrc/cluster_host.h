@@ -1,9 +1,11 @@
 // cluster_host.h -- the host-side call sequence the clustering entries share (cluster.hip, cluster_levels.hip,
 // cluster_centres.hip, cluster_cores.hip, cluster_extend.hip, cluster_within.hip, cluster_cores_within.hip, cluster_tree.hip,
-// cluster_tree_extend.hip, cluster_core_tree.hip, cluster_tree_within.hip, cluster_edges.hip, cluster_edges_extend.hip;
+// cluster_tree_extend.hip, cluster_core_tree.hip, cluster_tree_within.hip, cluster_core_tree_within.hip, cluster_edges.hip,
+// cluster_edges_extend.hip;
 // DESIGN.md sections 25 and 40): ClusterCall, which owns a call's device scratch, runs what every entry does in front of its sweeps -- for the
 // blocked entries the block plan too --, fills the sweeps' common arguments per image and chunk, and reads the
-// totals back; and TreeRounds, the Boruvka rounds of the four tree entries around the entry's own offer of edges.  The
+// totals back; TreeRounds, the Boruvka rounds of the five tree entries around the entry's own offer of edges; and
+// core_height_passes, the bracket loop of the two core tree entries around the entry's own pass over the edges.  The
 // arithmetic that needs no GPU (the numbering, the plan, the new numbers, the record order) is cluster_plan.h's.  The
 // device code is each entry's own.
 #pragma once
@@ -113,7 +115,7 @@ struct ClusterCall {
   std::vector<void*> buffers;
 };
 
-// The cluster tree's rounds for the four tree entries: the rounds' buffers, and per round the
+// The cluster tree's rounds for the five tree entries: the rounds' buffers, and per round the
 // entry's offer to best[], the merge, the flatten and four bytes read back, the merges so far.  A round that adds none
 // was the last.
 struct TreeRounds {
@@ -149,6 +151,22 @@ struct TreeRounds {
   hipStream_t stream = nullptr;
   std::vector<ClusterTreeMerge> got;
 };
+
+// The core heights' bracket loop for the two core tree entries, after the settle of pass 0 and
+// only with min_degree != 0: per pass the next width and pass number into `settle`, the entry's one pass over the edges
+// -- pass(span, width, first) enqueues whatever adds every edge to hist[] (< 0: it failed) -- and the settle, which
+// reads the counters that pass has finished.  max(1, ceil(log_kCoreBuckets(1001 - min_permille))) passes: the one that
+// leaves brackets one height wide is the last.
+template <class Pass>
+int core_height_passes(ClusterCoreHeightSettleArgs& settle, hipStream_t stream, Pass&& pass) {
+  for (uint32_t span = 1001u - settle.min_permille;; span = settle.width) {
+    settle.width = (span + kCoreBuckets - 1u) / kCoreBuckets;
+    settle.pass += 1;
+    if (pass(span, settle.width, settle.pass == 1u) < 0) return -1;
+    if (launch_cluster_core_height_settle(settle, stream) < 0) return -1;
+    if (settle.width == 1) return 0;                          // the brackets are one height wide
+  }
+}
 
 }  // namespace detail
 }  // namespace blurrily

@@ -24,7 +24,7 @@ from . import _native
 from . import cluster_records as _cluster_records
 from ._marshal import (_as_bytes, _batch_limit, _blocks, _call_growing, _check, _find_limit, _held_offsets, _lists,
                        _match_lists, _match_rows, _members_of, _needles, _pack, _permille, _ptr, _records, _refs,
-                       _similar_lists, _similar_rows, _slices, _u32)
+                       _refs_with_keys, _similar_lists, _similar_rows, _slices, _u32)
 from .defaults import LIMIT_DEFAULT
 from .map_clusters import ClusterMethods as _ClusterMethods
 
@@ -761,6 +761,17 @@ class Map(RawMap):
         ascending without repeats -- what ``cut_core_tree`` takes, the counts left out."""
         refs = np.unique(_refs(references))
         return (refs,) + super().cluster_core_tree(refs, min_permille, min_degree)[:3]
+
+    def dense_tree_within(self, references, blocks, min_permille, min_degree):
+        """``cluster_core_tree_within`` over the (reference, key) pairs as a set: ``(refs, keys, labels, core_permille,
+        merges)``, refs ascending without repeats, each with its key -- what ``cut_core_tree`` and ``tree_by_block``
+        take, the counts left out.  ValueError for a reference that carries two keys."""
+        refs, keys = _refs_with_keys(references, blocks)
+        refs, at, number = np.unique(refs, return_index=True, return_inverse=True)
+        if (keys[at][number.reshape(-1)] != keys).any():
+            raise ValueError("a reference is listed under two block keys")
+        keys = keys[at]
+        return (refs, keys) + super().cluster_core_tree_within(refs, keys, min_permille, min_degree)[:3]
 
     def find_batch_by_reference(self, references, limit=LIMIT_DEFAULT):
         """``[self.find_by_reference(r, limit) for r in references]`` in one GPU batch."""

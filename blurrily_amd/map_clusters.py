@@ -287,6 +287,27 @@ class ClusterMethods:
                                                               _ptr(merges), *_byrefs(counts)))
         return (labels,) + _merged(merges, counts)
 
+    def cluster_core_tree_within(self, references, blocks, min_permille, min_degree):
+        """``cluster_core_tree`` within blocks (blurrily_storage_cluster_core_tree_within): ``blocks[i]`` is a 32-bit key
+        for ``references[i]``, an edge needs both ends under one key, and a core height ranks those edges only, so no
+        record joins two keys.  One call serves all blocks.  Returns ``(labels, core_permille, merges, n_clusters,
+        n_edges, n_core_edges)`` as ``cluster_core_tree`` gives them, the counts being ``cluster_cores_within``'s at
+        ``(min_permille, min_degree)`` -- what one ``cluster_core_tree`` call per block gives, the records merged into
+        one list in the tree's order.  ``cut_core_tree`` gives ``cluster_cores_within``'s cores and their labels at any
+        higher floor without another call, ``merge_profile`` takes the records as they are, and ``tree_by_block``
+        splits them by key."""
+        self._check_open()
+        mp = _permille(min_permille)
+        md = _u32(min_degree, "min_degree")
+        refs, keys = _refs_with_keys(references, blocks)
+        n = len(refs)
+        labels, core_permille = (np.zeros(n, dtype=np.uint32) for _ in range(2))
+        merges, counts = _merges(n), _counters(32, 32, 64, 64)  # (n_merges, n_clusters, n_edges, n_core_edges)
+        _check(self._lib.blurrily_storage_cluster_core_tree_within(self._h, _ptr(refs), _ptr(keys), n, mp, md,
+                                                                   _ptr(labels), _ptr(core_permille), _ptr(merges),
+                                                                   *_byrefs(counts)))
+        return (labels, core_permille) + _merged(merges, counts)
+
     def _cluster_edges_call(self, references, min_permille, blocks):
         """What the two edge methods share: ``(call(rows, cap, n_edges), n)`` for the unblocked symbol
         (``blocks`` None) or the blocked one."""

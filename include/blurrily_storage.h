@@ -657,8 +657,8 @@ int blurrily_storage_cluster_tree_extend(trigram_map haystack, const uint32_t* o
  * references, labels, core_permille or merges NULL with n > 0, n above BLURRILY_CLUSTER_TREE_MAX; any min_degree is
  * valid); ENODEV without a usable GPU; EIO if a bounded loop of the device or the bound on the rounds ran out.  labels,
  * core_permille and merges are written only on success.
- * Not built: the borders' anchors at a cut (they need the degree at that floor), a tree within blocks, a _device
- * variant, a protocol verb. */
+ * Not built: the borders' anchors at a cut (they need the degree at that floor), a _device variant, a protocol verb.
+ * (Within blocks: blurrily_storage_cluster_core_tree_within below.) */
 #define BLURRILY_NO_CORE 0xFFFFFFFFu
 int blurrily_storage_cluster_core_tree(trigram_map haystack, const uint32_t* references, size_t n,
                                        uint32_t min_permille, uint32_t min_degree,
@@ -692,7 +692,8 @@ int blurrily_storage_cluster_core_tree(trigram_map haystack, const uint32_t* ref
  * references, blocks, labels or merges NULL with n > 0, n above BLURRILY_CLUSTER_TREE_MAX, a reference listed more than
  * once with different keys); ENODEV without a usable GPU; EIO if a bounded loop of the device's union-find or the bound
  * on the rounds ran out.  The labels and merges are written only on success.
- * Not built: the core tree and tree extend within blocks, a _device variant, a protocol verb. */
+ * Not built: tree extend within blocks, a _device variant, a protocol verb.  (The core tree within blocks:
+ * blurrily_storage_cluster_core_tree_within below.) */
 int blurrily_storage_cluster_tree_within(trigram_map haystack, const uint32_t* references, const uint32_t* blocks,
                                          size_t n, uint32_t min_permille, uint32_t* labels,
                                          blurrily_cluster_merge_t* merges, uint32_t* n_merges,
@@ -791,12 +792,50 @@ int blurrily_storage_cluster_edges_between(trigram_map haystack, const uint32_t*
  * references, blocks or labels NULL with n > 0, n above 0xFFFFFFF0, a reference listed more than once with different
  * keys; any min_degree is valid); ENODEV without a usable GPU; EIO if a bounded loop of the device ran out.  The outputs
  * are written only on success.
- * Not built: the core tree within blocks, levels, centres and extend within blocks, a _device variant, a protocol verb,
- * a Ruby method. */
+ * Not built: levels, centres and extend within blocks, a _device variant, a protocol verb, a Ruby method.  (The core
+ * tree within blocks: blurrily_storage_cluster_core_tree_within below.) */
 int blurrily_storage_cluster_cores_within(trigram_map haystack, const uint32_t* references, const uint32_t* blocks,
                                           size_t n, uint32_t min_permille, uint32_t min_degree,
                                           uint32_t* labels, uint32_t* degrees, uint8_t* kinds,
                                           uint32_t* n_clusters, uint64_t* n_edges, uint64_t* n_core_edges);
+
+/* Cluster core tree within blocks: the dendrogram of blurrily_storage_cluster_cores_within's cores inside caller-given
+ * blocks, one call for all blocks -- for the job that blocks its records, has found that single linkage chains
+ * look-alikes together, and does not know the floor in advance.  blocks[i] is an opaque 32-bit
+ * key for references[i].  Nodes, T, R, m, the edge test, the height h, core heights, tree edges, the capped height
+ * H = min(h, c(a), c(b)), the total order, the records' form and order, BLURRILY_NO_CLUSTER and BLURRILY_NO_CORE:
+ * exactly as for blurrily_storage_cluster_core_tree.  Repeats (under one key), a shuffled list, absent references,
+ * unlisted bridges, deletes, pending puts, a reference put again, "devices" > 1, "scope_strategy" and the cap
+ * BLURRILY_CLUSTER_TREE_MAX: exactly as for blurrily_storage_cluster_tree_within.
+ *   Edges:  blurrily_storage_cluster_within's: an edge needs both ends under one key.
+ *   Core height: the min_degree-th largest h among those edges only, so no core height, tree edge or record reaches
+ *           across a key.
+ *   Counts: n_edges is blurrily_storage_cluster_within's; n_clusters and n_core_edges are
+ *           blurrily_storage_cluster_cores_within's at (min_permille, min_degree); n_merges == the nodes with a core
+ *           height - n_clusters.  Each of the four may be NULL.
+ * Uniting the ends of the merges with permille >= f, for any f >= min_permille, gives every reference with
+ * core_permille >= f the label blurrily_storage_cluster_cores_within gives it at (f, min_degree), and the cores of that
+ * call are exactly those references.  The result equals one blurrily_storage_cluster_core_tree call per block: the
+ * records merged into one list under the total order, labels and core heights put back in place, the counts summed.
+ * With all keys equal it is blurrily_storage_cluster_core_tree, byte for byte.  With min_degree 0 or 1 merges and labels
+ * are blurrily_storage_cluster_tree_within's; with 0 the counts are too, and every node's core_permille is 1000.  With
+ * all keys distinct and min_degree >= 1 there is no record, every core_permille is BLURRILY_NO_CORE and every held
+ * reference is its own label.  All outputs depend on the map's contents, the set of (reference, key) pairs,
+ * min_permille and min_degree only; two runs give identical bytes, and so do the three strategies.  Each block is
+ * served at most twice for the core heights (not at all with min_degree == 0) and once per Boruvka round: a small one
+ * is scored member against member from the device's copy of its members' trigrams, a large one sweeps the map.
+ * n == 0: success, nothing written but the counts given (0).
+ * 0, or -1 with errno: EINVAL before anything needs a GPU and with nothing written (haystack NULL, min_permille > 1000,
+ * references, blocks, labels, core_permille or merges NULL with n > 0, n above BLURRILY_CLUSTER_TREE_MAX, a reference
+ * listed more than once with different keys; any min_degree is valid); ENODEV without a usable GPU; EIO if a bounded
+ * loop of the device or the bound on the rounds ran out.  labels, core_permille and merges are written only on success.
+ * Not built: extend forms of the core tree, scopes on any tree, the borders' anchors at a cut, levels or centres
+ * within blocks, a _device variant, a protocol verb, a Ruby method. */
+int blurrily_storage_cluster_core_tree_within(trigram_map haystack, const uint32_t* references, const uint32_t* blocks,
+                                              size_t n, uint32_t min_permille, uint32_t min_degree,
+                                              uint32_t* labels, uint32_t* core_permille,
+                                              blurrily_cluster_merge_t* merges, uint32_t* n_merges,
+                                              uint32_t* n_clusters, uint64_t* n_edges, uint64_t* n_core_edges);
 
 /* Tokeniser (ext/blurrily/tokeniser.h:34, tokeniser.c:59-119): `output` needs
  * strlen(input)+1 slots; returns the number of distinct codes, ascending. */

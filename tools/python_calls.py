@@ -79,6 +79,7 @@ SPEC = {
                                ">labels_new:u4[n2] >merges:u4[n1+n2,3] & & &",
     P + "cluster_core_tree": "h refs:u4[n] n mp md >labels:u4[n] >core:u4[n] >merges:u4[n,3] & & & &",
     P + "cluster_tree_within": "h refs:u4[n] keys:u4[n] n mp >labels:u4[n] >merges:u4[n,3] & & &",
+    P + "cluster_core_tree_within": "h refs:u4[n] keys:u4[n] n mp md >labels:u4[n] >core:u4[n] >merges:u4[n,3] & & & &",
     P + "cluster_edges": "h refs:u4[n] n mp ~rows:u4[cap,3] cap &",
     P + "cluster_edges_within": "h refs:u4[n] keys:u4[n] n mp ~rows:u4[cap,3] cap &",
     P + "cluster_edges_extend": _TWO, P + "cluster_edges_between": _TWO,
