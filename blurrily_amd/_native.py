@@ -190,6 +190,10 @@ _ENTRIES = {
                                                             C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                                             C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
                                                             C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    # cluster extend within blocks: old labels as seeds, only the new references looked at, inside one block key
+    "blurrily_storage_cluster_extend_within": (C.c_int, [_vp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                                         C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p,
+                                                         C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
 }
 EXPORTED_SYMBOLS = tuple(_ENTRIES)
 

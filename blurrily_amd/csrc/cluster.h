@@ -225,6 +225,48 @@ struct ClusterWithinSweepArgs {
 };
 int launch_cluster_within_sweep(const ClusterWithinSweepArgs& a, hipStream_t stream);
 
+// Cluster extend within blocks (cluster_extend_within_kernels.hip): cluster extend's forest --
+// seeds for the OLD nodes, only the NEW ones looked at -- where a seed and an edge also need both ends under one block
+// key, block_of[u] for number u.  The seeds are cluster_extend_seed_kernel's with that one test more.
+struct ClusterExtendWithinSeedArgs {
+  ClusterExtendSeedArgs s;
+  const uint32_t*       block_of;   // [s.n_nodes] each number's key
+};
+int launch_cluster_extend_within_seed(const ClusterExtendWithinSeedArgs& a, hipStream_t stream);
+
+// The direct kernel: a tile is up to kClusterWithinTile consecutive places of `new_order` (the NEW numbers sorted by
+// (key, number)), all of one block, and its workgroup scores them against every member of the block, places
+// [tile.begin, tile.end) of `order`, from the extraction's codes alone.  An old member is an edge from the needle's
+// side; between two new numbers the edge is the higher number's to find.  (ClusterExtendWithinTile: cluster_plan.h.)
+struct ClusterExtendWithinArgs {
+  const ClusterExtendWithinTile* tiles;   // [n_tiles]
+  const uint32_t* order;         // [n_order] numbers, block after block, ascending inside a block
+  const uint32_t* new_order;     // [n_new_order] the new numbers in that order
+  uint32_t        n_tiles;
+  uint32_t        n_order;
+  uint32_t        n_new_order;
+  const uint16_t* qcodes;        // the extraction's (number u's q_ntri[u] distinct codes at qcodes + qoff[u] + u)
+  const uint64_t* qoff;
+  const uint32_t* q_ntri;        // (0: the map does not hold it, no node)
+  const uint32_t* is_new;        // [(n_nodes + 31) / 32]
+  uint32_t        n_nodes;
+  uint32_t        min_permille;
+  uint32_t*       parent;
+  ClusterTotals*  totals;
+};
+int launch_cluster_extend_within(const ClusterExtendWithinArgs& a, hipStream_t stream);
+
+// cluster_extend_sweep_kernel's sweep for the blocks too large to score directly: needle b / tasks of the launch is
+// number needles[s.q_base + b / tasks], a new number of a swept block, and a candidate node under another key than the
+// needle's is passed over before it is counted.
+struct ClusterExtendWithinSweepArgs {
+  ClusterSweepArgs s;            // (s.q_base and s.n count in needles)
+  const uint32_t*  needles;      // the swept blocks' new numbers
+  const uint32_t*  is_new;       // [(n_nodes + 31) / 32]
+  const uint32_t*  block_of;     // [n_nodes] each number's key
+};
+int launch_cluster_extend_within_sweep(const ClusterExtendWithinSweepArgs& a, hipStream_t stream);
+
 // Cluster tree (cluster_tree_kernels.hip): the maximum spanning forest of the edges, heights in
 // whole per mille, by Boruvka rounds.  A round is one sweep, which chooses instead of uniting, then across launch
 // boundaries the merge and the flatten.

@@ -1,7 +1,7 @@
 // cluster_host.h -- the host-side call sequence the clustering entries share (cluster.hip, cluster_levels.hip,
 // cluster_centres.hip, cluster_cores.hip, cluster_extend.hip, cluster_within.hip, cluster_cores_within.hip, cluster_tree.hip,
 // cluster_tree_extend.hip, cluster_core_tree.hip, cluster_tree_within.hip, cluster_core_tree_within.hip, cluster_edges.hip,
-// cluster_edges_extend.hip;
+// cluster_edges_extend.hip, cluster_extend_within.hip;
 // DESIGN.md sections 25 and 40): ClusterCall, which owns a call's device scratch, runs what every entry does in front of its sweeps -- for the
 // blocked entries the block plan too --, fills the sweeps' common arguments per image and chunk, and reads the
 // totals back; TreeRounds, the Boruvka rounds of the five tree entries around the entry's own offer of edges; and

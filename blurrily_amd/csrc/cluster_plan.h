@@ -19,6 +19,13 @@ struct ClusterWithinTile {
   uint32_t count;                // its places: 1 .. kClusterWithinTile, all of one block
 };
 
+// A tile of the extending blocked entry's direct kernel (cluster.h: ClusterExtendWithinArgs).
+struct ClusterExtendWithinTile {
+  uint32_t begin, end;           // the block's places in `order`: [begin, end)
+  uint32_t first;                // the tile's first place in `new_order`
+  uint32_t count;                // its places there: 1 .. kClusterWithinTile, all NEW numbers of that block
+};
+
 // One chosen edge, as the caller gets it (blurrily_cluster_merge_t of include/blurrily_storage.h).
 struct ClusterTreeMerge { uint32_t a, b, permille; };
 
@@ -139,6 +146,71 @@ inline void mark_new(const std::vector<uint32_t>& inv, size_t n_old, size_t n_ne
     for (size_t u = 0; u < nu; ++u)
       if ((is_new[u >> 5] >> (u & 31u)) & 1u) new_nodes.push_back(uint32_t(u));
   }
+}
+
+// The listed members of a block, old and new together, up to which "scope_strategy" 0 lets
+// blurrily_storage_cluster_extend_within score the block directly.  Per needle the direct kernel here reads the whole
+// block, where cluster_within's reads half of it on average, but only the new numbers are needles, so its work grows
+// with new x block, not with the square of the block -- and with few new numbers it launches few workgroups.  Measured
+// for this entry on one MI355X (profiles/cluster_extend_within_geonames.json: configs[2]'s haystack at 700 per mille,
+// one block with 10^3 new rows, medians of five calls): at 10^5 listed members direct takes 5.61 ms against the
+// sweep's 18.4 ms, at 10^6 53.8 ms against 27.4 ms.  This is the largest measured size at which direct was no slower;
+// it happens to equal kClusterWithinDirectMax, but it is this entry's own measurement, and nothing between the two
+// sizes was measured.
+constexpr size_t kClusterExtendWithinDirectMax = 100000;
+
+// The block plan of blurrily_storage_cluster_extend_within, from each number's key and mark_new's
+// bit per number: `order` as plan_within_blocks makes it, `new_order` the NEW numbers in the same order, and every block
+// that has a new number given to one of two kernels -- the direct kernel's tiles of up to kClusterWithinTile places of
+// new_order for a block of at most kClusterExtendWithinDirectMax listed members ("scope_strategy" 2: for any block), the
+// sweep's needle list, the block's new numbers, for a larger one ("scope_strategy" 1: for every block).  A block without
+// a new number gets neither: its seeds are all there is to it.  Nor does a block of one, which has no pair to score.
+// The tiles that pass over the most members first (equal ones in the plan's order).
+struct ClusterExtendWithinPlan {
+  std::vector<uint32_t>                order, new_order;
+  std::vector<ClusterExtendWithinTile> tiles;
+  std::vector<uint32_t>                swept;
+};
+// -1 with EINVAL: more tiles than a launch takes.
+inline int plan_extend_within_blocks(const std::vector<uint32_t>& key_of, const std::vector<uint32_t>& is_new,
+                                     uint32_t scope_strategy, ClusterExtendWithinPlan& plan) {
+  const size_t nu = key_of.size();
+  std::vector<uint32_t>& order = plan.order;
+  order.resize(nu);
+  if (std::is_sorted(key_of.begin(), key_of.end())) {
+    for (size_t u = 0; u < nu; ++u) order[u] = uint32_t(u);
+  } else {
+    std::vector<uint64_t> keyed(nu);
+    for (size_t u = 0; u < nu; ++u) keyed[u] = (uint64_t(key_of[u]) << 32) | u;
+    std::sort(keyed.begin(), keyed.end());
+    for (size_t u = 0; u < nu; ++u) order[u] = uint32_t(keyed[u]);
+  }
+  std::vector<ClusterExtendWithinTile>& tiles = plan.tiles;
+  for (size_t b = 0; b < nu;) {
+    size_t e = b + 1;
+    while (e < nu && key_of[order[e]] == key_of[order[b]]) ++e;
+    const size_t nb = plan.new_order.size();
+    for (size_t i = b; i < e; ++i)
+      if ((is_new[order[i] >> 5] >> (order[i] & 31u)) & 1u) plan.new_order.push_back(order[i]);
+    const size_t ne = plan.new_order.size();
+    const bool direct = scope_strategy == 2 || (scope_strategy == 0 && e - b <= kClusterExtendWithinDirectMax);
+    if (ne == nb || e - b < 2) {                              // (seeds only, or no pair to score)
+    } else if (!direct) {
+      plan.swept.insert(plan.swept.end(), plan.new_order.begin() + nb, plan.new_order.end());
+    } else {
+      for (size_t f = nb; f < ne; f += kClusterWithinTile)
+        tiles.push_back({uint32_t(b), uint32_t(e), uint32_t(f), uint32_t(std::min<size_t>(kClusterWithinTile, ne - f))});
+    }
+    b = e;
+  }
+  if (tiles.size() > 0x7FFFFFFFull) { errno = EINVAL; return -1; }
+  std::vector<uint64_t> by_scan(tiles.size());
+  for (size_t t = 0; t < tiles.size(); ++t) by_scan[t] = (uint64_t(~(tiles[t].end - tiles[t].begin)) << 32) | t;
+  std::sort(by_scan.begin(), by_scan.end());
+  std::vector<ClusterExtendWithinTile> sorted(tiles.size());
+  for (size_t t = 0; t < tiles.size(); ++t) sorted[t] = tiles[uint32_t(by_scan[t])];
+  tiles.swap(sorted);
+  return 0;
 }
 
 // Which side of blurrily_storage_cluster_edges_between sweeps: the edges with an end on each side

@@ -149,8 +149,8 @@ class ClusterMethods:
         return (labels_old, labels_new) + _ints(counts)
 
     def cluster_changes(self, old_refs, old_labels, labels_old):
-        """What a database update after ``cluster_extend`` needs: (the old references whose label moved, their new
-        labels), in the list's order.  Numpy only."""
+        """What a database update after ``cluster_extend`` or ``cluster_extend_within`` needs: (the old references
+        whose label moved, their new labels), in the list's order.  Numpy only."""
         old, was, now = _refs(old_refs), _refs(old_labels), _refs(labels_old)
         if not len(old) == len(was) == len(now):
             raise ValueError("old_refs, old_labels and labels_old differ in length")
@@ -171,6 +171,29 @@ class ClusterMethods:
         _check(self._lib.blurrily_storage_cluster_within(self._h, _ptr(refs), _ptr(keys), n, mp, _ptr(labels),
                                                          *_byrefs(counts)))
         return (labels,) + _ints(counts)
+
+    def cluster_extend_within(self, old_refs, old_blocks, old_labels, new_refs, new_blocks, min_permille):
+        """``cluster_extend`` within blocks (blurrily_storage_cluster_extend_within): ``old_blocks[i]`` is a 32-bit key
+        for ``old_refs[i]``, ``new_blocks[j]`` for ``new_refs[j]``; a seed and an edge need both ends under one key,
+        and only the new references of a block are scored against it.  With ``old_labels`` from
+        ``cluster_within(old_refs, old_blocks, min_permille)`` on the map as it is now and the lists disjoint, the
+        result is ``cluster_within``'s over both lists with the keys concatenated; a group that lost a member to a
+        delete is re-clustered on its own first (``cluster_within`` over its remaining members).  Returns
+        (labels_old[n_old] uint32, labels_new[n_new] uint32, the number of components, the number of within-block
+        edges with a new end, each once).  ``cluster_changes`` serves the result as it is."""
+        self._check_open()
+        mp = _permille(min_permille)
+        old, old_keys = _refs_with_keys(old_refs, old_blocks)
+        new, new_keys = _refs_with_keys(new_refs, new_blocks)
+        seeds = _refs(old_labels)
+        if len(seeds) != len(old):
+            raise ValueError(f"{len(seeds)} old labels for {len(old)} old references")
+        labels_old, labels_new = np.zeros(len(old), dtype=np.uint32), np.zeros(len(new), dtype=np.uint32)
+        counts = _counters(32, 64)                              # n_clusters, n_edges
+        _check(self._lib.blurrily_storage_cluster_extend_within(self._h, _ptr(old), _ptr(old_keys), _ptr(seeds), len(old),
+                                                                _ptr(new), _ptr(new_keys), len(new), mp,
+                                                                _ptr(labels_old), _ptr(labels_new), *_byrefs(counts)))
+        return (labels_old, labels_new) + _ints(counts)
 
     def duplicates_within(self, references, blocks, min_permille):
         """The within-block clusters of two or more references, as ``duplicates`` gives them: a list of lists of

@@ -552,8 +552,8 @@ int blurrily_storage_cluster_extend(trigram_map haystack, const uint32_t* old_re
  * 0, or -1 with errno: EINVAL before anything needs a GPU and with nothing written (haystack NULL, min_permille > 1000,
  * references, blocks or labels NULL with n > 0, n above 0xFFFFFFF0, a reference listed more than once with different
  * keys); ENODEV without a usable GPU; EIO if a bounded loop of the device's union-find ran out.  The labels are written
- * only on success.  Not built: levels, centres and extend within blocks, a _device variant, a protocol verb.  (Cores
- * within blocks: blurrily_storage_cluster_cores_within.) */
+ * only on success.  Not built: levels and centres within blocks, a _device variant, a protocol verb.  (Cores within
+ * blocks: blurrily_storage_cluster_cores_within; extend within blocks: blurrily_storage_cluster_extend_within.) */
 int blurrily_storage_cluster_within(trigram_map haystack, const uint32_t* references, const uint32_t* blocks, size_t n,
                                     uint32_t min_permille, uint32_t* labels, uint32_t* n_clusters, uint64_t* n_edges);
 
@@ -836,6 +836,52 @@ int blurrily_storage_cluster_core_tree_within(trigram_map haystack, const uint32
                                               uint32_t* labels, uint32_t* core_permille,
                                               blurrily_cluster_merge_t* merges, uint32_t* n_merges,
                                               uint32_t* n_clusters, uint64_t* n_edges, uint64_t* n_core_edges);
+
+/* Cluster extend within blocks: blurrily_storage_cluster_extend inside caller-given blocks -- what a job that blocks its
+ * records and has clustered them with blurrily_storage_cluster_within does after a put, without scoring any block
+ * against itself again and without losing the labels it holds.  old_blocks[i] is an opaque
+ * 32-bit key for old_refs[i], new_blocks[j] for new_refs[j].  T, R, m, J, the edge test, BLURRILY_NO_CLUSTER, deletes,
+ * pending puts and a reference put again: exactly as for blurrily_storage_cluster.
+ *   Nodes:  the distinct references of old_refs and new_refs together that the map holds.  A node named by new_refs is
+ *           NEW, whatever old_refs says of it; every other node is OLD.
+ *   Keys:   a reference may be listed more than once, in one list or across the two, under one key.
+ *   Seeds:  a pair (old_refs[i], old_labels[i]) whose two ends are both old nodes under the same key joins them.  A
+ *           pair with an end that is not held, not listed or new does not exist, and neither does a pair whose ends
+ *           carry different keys (this is no error).  A label need not be a component's smallest reference: any listed
+ *           old reference serves (must-link stars or chains).
+ *   Edges:  blurrily_storage_cluster_within's edges (both ends under one key) that have at least one new end.  Pairs of
+ *           two old nodes are not looked at: the seeds speak for them.
+ *   Label:  the smallest reference among the nodes of a node's component in the graph of seeds plus edges.  A
+ *           component never spans two keys.
+ * labels_old[i] belongs to old_refs[i], labels_new[j] to new_refs[j]; a listed reference the map does not hold gets
+ * BLURRILY_NO_CLUSTER.  n_clusters (may be NULL): the components; n_edges (may be NULL): the edges above, each once --
+ * seeds are not counted.  All outputs depend on the map's contents, the two lists as sets of (reference, key[, label])
+ * and min_permille only: not on the lists' order, the images the references live in, or the order of the device's
+ * unions; the three values of "scope_strategy" give identical bytes.
+ * The contract: when old_labels is what blurrily_storage_cluster_within(old_refs, old_blocks, min_permille) returns on
+ * the map as it is now and the two lists are disjoint, the two label arrays together and n_clusters are byte for byte
+ * what blurrily_storage_cluster_within gives for the two lists in one with the keys concatenated, and n_edges is that
+ * call's minus the old call's.  With all keys equal every output is byte for byte blurrily_storage_cluster_extend's.
+ * n_old == 0: blurrily_storage_cluster_within(new_refs, new_blocks).  n_new == 0: the components of the seeds alone,
+ * n_edges 0.  Both 0: success, nothing written but the two counts (0).
+ * A seed group is taken on trust.  A delete, or a put-again, of a member may have split a group, and the seeds cannot
+ * show that: run blurrily_storage_cluster_within over that one group's remaining members, put its labels into
+ * old_labels, then extend.
+ * Only a block that has a new member is looked at: its new members are scored against every member of the block from
+ * the device's copy of their trigrams (new x block pair scores, not block x block), or, for a large block, sweep the
+ * map as blurrily_storage_cluster_extend's do.  Option "scope_strategy" 1 forces the sweep for every such block, 2 the
+ * direct form, 0 (the default) chooses per block.  With "devices" > 1 the primary device alone serves the call.
+ * 0, or -1 with errno: EINVAL before anything needs a GPU and with nothing written (haystack NULL, min_permille > 1000,
+ * old_refs, old_blocks, old_labels or labels_old NULL with n_old > 0, new_refs, new_blocks or labels_new NULL with
+ * n_new > 0, n_old + n_new above 0xFFFFFFF0, a reference listed more than once with different keys); ENODEV without a
+ * usable GPU; EIO if a bounded loop of the device's union-find ran out.  The labels are written only on success.
+ * Not built: the tree and the edge list extended within blocks, extend forms of cores, centres and levels, a _device
+ * variant, a protocol verb, a Ruby method. */
+int blurrily_storage_cluster_extend_within(trigram_map haystack,
+        const uint32_t* old_refs, const uint32_t* old_blocks, const uint32_t* old_labels, size_t n_old,
+        const uint32_t* new_refs, const uint32_t* new_blocks, size_t n_new,
+        uint32_t min_permille,
+        uint32_t* labels_old, uint32_t* labels_new, uint32_t* n_clusters, uint64_t* n_edges);
 
 /* Tokeniser (ext/blurrily/tokeniser.h:34, tokeniser.c:59-119): `output` needs
  * strlen(input)+1 slots; returns the number of distinct codes, ascending. */

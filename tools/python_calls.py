@@ -73,6 +73,8 @@ SPEC = {
     P + "cluster_cores": "h refs:u4[n] n mp md >labels:u4[n] >degrees:u4[n] >kinds:u1[n] & & &",
     P + "cluster_extend": "h old:u4[n1] seeds:u4[n1] n1 new:u4[n2] n2 mp >labels_old:u4[n1] >labels_new:u4[n2] & &",
     P + "cluster_within": "h refs:u4[n] keys:u4[n] n mp >labels:u4[n] & &",
+    P + "cluster_extend_within": "h old:u4[n1] old_keys:u4[n1] seeds:u4[n1] n1 new:u4[n2] new_keys:u4[n2] n2 mp "
+                                 ">labels_old:u4[n1] >labels_new:u4[n2] & &",
     P + "cluster_cores_within": "h refs:u4[n] keys:u4[n] n mp md >labels:u4[n] >degrees:u4[n] >kinds:u1[n] & & &",
     P + "cluster_tree": "h refs:u4[n] n mp >labels:u4[n] >merges:u4[n,3] & & &",
     P + "cluster_tree_extend": "h old:u4[n1] n1 records:u4[nr,3] nr new:u4[n2] n2 mp >labels_old:u4[n1] "
@@ -224,6 +226,7 @@ U32 = lambda v: np.array(v, dtype=np.uint32)
 BASE = dict(needle="san jose", limit=10, reference=7, weight=2, references=REFS, min_permille=500, min_degree=2,
             min_matches=1, blocks=[1, 1, 2, 1, 2], capacity=None, floors=[300, 600], attached=True, old_refs=[1, 2, 3],
             old_labels=[1, 1, 3], labels_old=[1, 1, 1], new_refs=[8, 9], old_merges=[[1, 2, 700]], left=[1, 2, 3],
+            old_blocks=[1, 1, 2], new_blocks=[1, 2],
             right=[8, 9], scope="held", scopes=["held", "list"], which=[0, None, 1, 1, None], packed=PACKED[0], offsets=PACKED[1],
             needles=["São Paulo", "", "abc", "A b\tC", "é"], refs=U32(REFS), weights=None, path="/nonexistent/blurrily.trigrams",
             key="one_taken", value=1, enabled=True, n=3, labels=[1, 1, 4, 1, 5], merges=[[1, 4, 800], [1, 5, 600]],
@@ -242,7 +245,8 @@ GRID = dict(
     weight=[0, -1, 1 << 32, None], references=_LIST, old_refs=_LIST[:1] + _LIST[6:10], new_refs=_LIST[:4] + _LIST[6:10],
     left=_LIST[:3] + _LIST[8:10], right=_LIST[:3] + _LIST[8:10], old_labels=[[], [1, 1], [1, 1, 1, 1], [1, 1, -1], U32([1, 1, 3])],
     labels_old=[[], [1, 1], U32([1, 2, 3])], min_permille=_PERMILLE, floor=_PERMILLE, min_matches=[0, 5, -1, 1 << 32],
-    min_degree=[0, 1, 0xFFFFFFFF, -1, 1 << 32], blocks=_KEYS + [None], capacity=[None, 0, 3, 2000, 1 << 64, -1],
+    min_degree=[0, 1, 0xFFFFFFFF, -1, 1 << 32], blocks=_KEYS + [None], old_blocks=[[], [1] * 4, [1, 2, -1], U32([1, 1, 2])],
+    new_blocks=[[], [1], [1, 1 << 32], U32([1, 2])], capacity=[None, 0, 3, 2000, 1 << 64, -1],
     floors=[[], [500], [100 * k for k in range(1, 10)], [500, 500], [600, 300], [1001], [0, 1000]], attached=[False],
     old_merges=_MERGES, merges=_MERGES, edges=_MERGES, record_lists=[(), (_MERGES[3],), (_MERGES[8], _MERGES[8])],
     scope=["held", "list", "empty", "array", "foreign", "closed"],
@@ -257,7 +261,7 @@ GRID = dict(
     enabled=[False, 0], n=[0, 1], path=["", b"/nonexistent/bytes"])
 EMPTY = dict(references=[], blocks=[], old_refs=[], old_labels=[], labels_old=[], new_refs=[], old_merges=[], left=[], right=[],
              scopes=[], which=[], packed=b"", offsets=[0], needles=[], refs=U32([]), labels=[], merges=[], core_permille=[],
-             edges=[], record_lists=(), floors=[], scope="empty")
+             edges=[], record_lists=(), floors=[], scope="empty", old_blocks=[], new_blocks=[])
 # put_many trusts its lists to be of one length: a grid over one of them alone would have the library read past the other
 ALONE = {("put_many", "references"), ("put_many", "needles"), ("put_many_packed", "packed")}
 LAST = ("close",)                                                        # (a map is closed after everything else)
