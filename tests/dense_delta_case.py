@@ -5,6 +5,11 @@ files build their maps with one bulk put, so every sweep of theirs runs on the b
 delta-image and tombstone tests put a few strings under the default "dense_min", so their delta image has no bitmap at
 all.  Here the two meet.
 
+The files that run on it: tests/test_gpu_dense_delta_finds.py and tests/test_gpu_dense_delta_plain_find.py (the finds),
+tests/test_gpu_dense_delta_clusters.py (cluster, levels, centres, cores, within, extend),
+tests/test_gpu_dense_delta_trees.py (the four tree entries), tests/test_gpu_dense_delta_edges.py (the edge lists: plain,
+blocked, extend and between) and tests/test_gpu_dense_delta_blocked.py (cores, core tree and extend within blocks).
+
 The mutations, in order (`Host.steps`; one generator, default_rng(83), throughout):
 
   pending phrases   150 of the 70 000 base words are the vocabulary; 3 000 phrases of three vocabulary words each, from
@@ -35,6 +40,7 @@ import numpy as np
 
 import dense_case as D
 import dense_truths as DT
+from cluster_truth import Truth
 
 SEED = 83
 N_VOCAB, N_PHRASES, PHRASE_WORDS = 150, 3000, 3
@@ -267,6 +273,74 @@ def truths(h):
         return kept[name]
 
     return truth
+
+
+class KeepingTruth(Truth):
+    """A cluster_truth.Truth that keeps every list's pairs, not the last one's alone: cluster_edges_extend_truth.Split
+    asks for three lists' (both, the old alone, the new alone) at every floor."""
+
+    def pairs(self, listed, least=0):
+        nodes = np.nonzero(np.isin(self.refs, np.asarray(listed, dtype=np.int64)) & (self.R > 0))[0]
+        key = (nodes.tobytes(), least)
+        if key not in self._kept:
+            self._kept[key] = super().pairs(listed, least)
+        return self._kept[key]
+
+
+def keeping_truth(h):
+    """A KeepingTruth over what is held now, the tokenisation shared with h.truth."""
+    t = KeepingTruth.__new__(KeepingTruth)
+    t.__dict__ = dict(h.truth.__dict__, _pairs={}, _kept={})
+    return t
+
+
+def keys_of(name):
+    """The two key functions of the blocked entries: dense_truths.key_pairs (two blocks of both images, about half a
+    list each) and key_families."""
+    return {"pairs": DT.key_pairs, "families": key_families}[name]
+
+
+def blocked_truth(c, name, keys):
+    """The cluster_tree_within_truth.BlockedTruth of a list of `c` (inputs() with .truth) under a key function, made
+    once: over the list's own truth, the tokenisation shared."""
+    from cluster_core_tree_within_truth import blocked_over
+    kept = c.__dict__.setdefault("_blocked_truths", {})
+    if (name, keys) not in kept:
+        kept[name, keys] = blocked_over(c.truth(name), c.lists[name], keys_of(keys)(c.lists[name]))
+    return kept[name, keys]
+
+
+def by_image(h, listed):
+    """(in_base, in_delta): a list split by the image its references lie in -- the pending puts, the moved rows among
+    them, against the rest.  The deleted, listed among the base's, are no nodes."""
+    listed = np.asarray(listed, dtype=np.uint32)
+    pending = np.isin(listed, np.array(sorted(h.pending), dtype=np.uint32))
+    return listed[~pending], listed[pending]
+
+
+def by_seven(listed):
+    """(old, new): every reference that is a multiple of 7 new, the rest old -- nodes of both images on either side."""
+    listed = np.asarray(listed, dtype=np.uint32)
+    return listed[listed % 7 != 0], listed[listed % 7 == 0]
+
+
+def delta_ends(h, records):
+    """Per record (a, b, permille) of held references: how many of its two ends lie in the delta image."""
+    records = np.asarray(records, dtype=np.uint32).reshape(-1, 3)
+    return np.isin(records[:, :2], np.array(sorted(h.pending), dtype=np.uint32)).sum(axis=1)
+
+
+def kinds(h, records):
+    """(delta-delta, base-delta, base-base) records."""
+    ends = delta_ends(h, records)
+    return tuple(int((ends == k).sum()) for k in (2, 1, 0))
+
+
+def across_in_a_block(h, records, keys):
+    """The records with an end in each image and both ends under one key of the key function `keys`."""
+    records = np.asarray(records, dtype=np.uint32).reshape(-1, 3)
+    one = (delta_ends(h, records) == 1) & (keys_of(keys)(records[:, 0]) == keys_of(keys)(records[:, 1]))
+    return records[one]
 
 
 def fold(m):

@@ -3,25 +3,42 @@ every sweep on a base image with tombstones behind its bitmaps and a delta image
 image, that the needles have more dense slices than a sweep lists and that the bars put L on all three sides of the list
 of 64; that the truth has edges within the delta, from a wide delta node into the upper half of the base's window 0 and
 into its window 1; that each deleted twin would be an edge and a row if it were still held, at the high floors through the
-left-out bitmaps alone; and that a moved row lies elsewhere in the delta than in the base.  The relations are asserted, not
-figures: a re-seeded generator that empties a case fails here, and the remedy is another seed.
+left-out bitmaps alone; and that a moved row lies elsewhere in the delta than in the base.  For the edge lists and the
+newer blocked entries (tests/test_gpu_dense_delta_edges.py, tests/test_gpu_dense_delta_blocked.py): that the records of
+`long` cross the edge sort's tile at floors 200 and 350 and are of every kind (within the delta, across the images,
+within the base) at every floor; that under both key functions an edge across the images lies inside one block; that the
+split by image has edges across and among the new either way round and makes the delta's side the smaller on `short` and
+the base's on `long`; that the split by seven has both images on both sides and same-side edges across them; and that the
+cores within blocks have borders and, at (p*, 5) under the family keys, a core.  The relations are asserted, not
+figures (each is printed beside its relation): a re-seeded generator that empties a case fails here, and the remedy is
+another seed.
 
 Not covered by the map: a delta image of more than one window or with ranks of 32 768 and more (a base of millions of
 references), and the delta's bitmaps as the device counts them (DeviceInfo.n_bitmaps is the base image's)."""
 import numpy as np
 import pytest
 
+import cluster_edges_truth as CE
 import dense_case as D
 import dense_delta_case as C
 import dense_truths as DT
+from cluster_cores_truth import CORE
+from cluster_cores_within_truth import CoresWithinEdges
+from cluster_edges_extend_truth import Split
 from cluster_truth import Truth
+
+
+TILE = 4096                                                    # the edge sort's tile (cluster.h: kClusterEdgesTile)
+LISTS = ("short", "long")
+KEYS = ("pairs", "families")
+MIN_DEGREES = (0, 2, 3, 5)                                     # tests/test_gpu_dense_delta_blocked.py's
 
 
 @pytest.fixture(scope="module")
 def case():
     h = C.host()
     c = C.inputs(h)
-    c.h = h
+    c.h, c.truth = h, C.truths(h)
     return c
 
 
@@ -177,3 +194,95 @@ def test_the_exact_bar_in_the_delta(case):
     for p, n in ((500, C.COPIES - 1), (501, 0)):
         mine = [e for e in _edges(h, g.listed, p) if g.glued in e]
         assert len(mine) == n and all(hi == g.glued for _, hi in mine), p
+
+
+# ---- what tests/test_gpu_dense_delta_edges.py and tests/test_gpu_dense_delta_blocked.py lean on ---------------------------
+
+def _records(case, name, p):
+    return CE.records(case.truth(name), case.lists[name], p, DT.LEAST)
+
+
+def test_the_edge_records_cross_the_sorts_tile_and_are_of_every_kind_at_every_floor(case):
+    count = {}
+    for name in LISTS:
+        for p in case.floors:
+            rows = _records(case, name, p)
+            kinds = C.kinds(case.h, rows)
+            count[name, p] = len(rows)
+            print(f"{name}, floor {p}: {len(rows)} records; delta-delta, base-delta, base-base {kinds}")
+            assert min(kinds) >= 1 and sum(kinds) == len(rows), (name, p, kinds)
+    assert count["long", 200] > 4 * TILE                          # several merge passes of the sort
+    assert TILE < count["long", 350] < 2 * TILE                   # one tile and a few records: the first merge pass
+    assert all(count["short", p] < TILE for p in case.floors)     # and no merge at all
+
+
+@pytest.mark.parametrize("keys", KEYS)
+def test_every_list_and_floor_has_a_base_delta_edge_inside_one_block(case, keys):
+    h = case.h
+    for name in LISTS:
+        blocks = C.keys_of(keys)(case.lists[name])
+        key_of = dict(zip(case.lists[name].tolist(), blocks.tolist()))
+        for p in case.floors:
+            rows = _records(case, name, p)
+            within = rows[[key_of[a] == key_of[b] for a, b, _ in rows.tolist()]]
+            across = C.across_in_a_block(h, rows, keys)
+            print(f"{name}, {keys}, floor {p}: {len(within)} within-block edges, {len(across)} of them base-delta")
+            assert len(across) >= (len(h.moved) if keys == "families" else 1), (name, p)
+    # under `families` a moved row's block is its base family's: a block of both images
+    moved_keys = C.key_families(np.array(h.moved, dtype=np.uint32))
+    assert moved_keys.tolist() == C.key_families(np.array(h.moved_heads, dtype=np.uint32)).tolist()
+
+
+def test_the_split_by_image_has_edges_across_and_among_the_new_either_way_round(case):
+    h, truth = case.h, C.keeping_truth(case.h)
+    sizes = {}
+    for name in LISTS:
+        in_base, in_delta = C.by_image(h, case.lists[name])
+        sizes[name] = (len(in_base), len(in_delta))
+        assert set(h.moved) <= set(in_delta.tolist()) and set(h.twins) <= set(in_base.tolist())
+        for p in case.floors:
+            for old, new, what in ((in_base, in_delta, "pending new"), (in_delta, in_base, "base new")):
+                figures = Split(truth, old, new, p, DT.LEAST).check_itself().figures()
+                print(f"{name}, floor {p}, {what}: old-old, old-new, new-new {figures}")
+                assert figures[1] >= 1 and figures[2] >= 1, (name, p, what)
+    # cluster_edges_between lets the side of fewer references sweep: the delta's on `short`, the base's on `long`
+    print(f"(in the base, in the delta) listed: {sizes}")
+    assert sizes["short"][1] < sizes["short"][0] and sizes["long"][0] < sizes["long"][1]
+
+
+def test_the_split_by_seven_has_both_images_on_both_sides_and_same_side_edges_across_them(case):
+    h, listed = case.h, case.lists["short"]
+    old, new = C.by_seven(listed)
+    for side in (old, new):
+        assert {h.image(r) for r in side.tolist() if r in h.held} == {0, 1}
+    for p in (case.floors[0], case.p_star):
+        rows = _records(case, "short", p)
+        across = rows[C.delta_ends(h, rows) == 1]
+        sides = (across[:, :2] % 7 == 0).sum(axis=1)
+        print(f"short by seven, floor {p}: base-delta edges old-old, old-new, new-new "
+              f"{[int((sides == k).sum()) for k in (0, 1, 2)]}")
+        assert (sides != 1).sum() >= 1, p                          # a same-side edge whose ends lie in different images
+        assert (sides == 1).sum() >= 1, p                          # and one across the sides as well
+        # the GPU file runs the split with the sides exchanged too: the same-side edges between two references that are
+        # no multiples of 7 are then edges among the new, which cluster_edges_extend's needles find from the higher end
+        assert (sides == 0).sum() >= 1, p
+
+
+@pytest.mark.parametrize("keys", KEYS)
+def test_cores_within_blocks_have_borders_and_the_core_tree_a_core_at_p_star(case, keys):
+    h = case.h
+    for name in LISTS:
+        listed = case.lists[name]
+        blocks = C.keys_of(keys)(listed)
+        borders = 0
+        for p in case.floors:
+            e = CoresWithinEdges(case.truth(name), listed, blocks, p, DT.LEAST)
+            for k in MIN_DEGREES:
+                t = e.cores(k)
+                borders += t.n_borders
+                if (p, k) == (case.p_star, 5):
+                    cores = int((t.kinds == CORE).sum())
+                    print(f"{name}, {keys}, floor {p}, min_degree {k}: {cores} cores, {t.n_core_edges} core edges")
+                    assert cores >= 1 or keys != "families"       # the core tree's case (p*, 5) has a core height
+        print(f"{name}, {keys}: {borders} borders over every floor and min_degree")
+        assert borders >= 1
